@@ -8,16 +8,25 @@ batch 32 per GPU, SSIMLoss(mix=.8) (MS-SSIM + L1), AdamW, 4096 synthetic-EM uint
 (``DeviceTileDataset``).  A step = one iteration of ``train_paired``'s loop: device-side pair generation (crop / rot90 / flip
 gather, Pillow-exact 4x reduction, AdditiveGaussian(13), round/clip), forward, loss, backward, (gradient all-reduce),
 optimizer update -- replayed as one hipGraph by the driver itself (pssr2_amd/fastpath.py).  The timed region is bracketed
-from inside the loop by a callback: barrier + synchronize after step W and after step W+K.
+from inside the loop by a callback: barrier + synchronize after step W and after step W+K.  An epoch of the default 4096 tiles is 115
+steps: a timed region that runs past its end also holds the driver's validation pass and the epoch's partial last batch.
 
-After the headline region rank 0 (N = 1) also times, each with its own warm-up: c2 inference through ``predict_images``
-(batch 128), the c5 sheet through ``predict_sheet``, the exact-f32 training step, and the CPU oracle.  ONE JSON line.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line.  ``--full`` adds everything else the bench measures, after
+the headline region: the instrumented roofline passes of the dominant kernels, with N > 1 the ranks' weight check and the gradient-exchange
+probe, and on rank 0 of a 1-GPU run, each with its own warm-up, c2 inference through ``predict_images`` (batch 128), the c5 sheet through
+``predict_sheet``, the exact-f32, c3 and c4 training steps, the host-fed training step and the CPU oracle.
+
+``--dump-outputs DIR`` writes what the timed path computed in its last step as ``DIR/<name>.npy`` (float32 / float64, at most 64 MB in
+all; a larger array is replaced by a fixed seeded sample of its elements, flattened).  Training: the last step's prediction ``hr_hat``,
+its ``lr`` input (made on the device by the pair generator), its ``loss``, the model's ``params`` (flattened in ``parameters()`` order) and
+floating-point ``buffers``.  Inference / sheet: the predictions of the last timed call.  Same arguments, same inputs.
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
@@ -360,6 +369,41 @@ class StepClock:
             raise _Done()
 
 
+class KeepingStepClock(StepClock):
+    """StepClock that also keeps the last timed step's tensors (--dump-outputs): a 1-argument callback receives the driver loop's locals."""
+
+    def __call__(self, loop):
+        if self.count + 1 == self.warmup + self.steps:
+            self.last = {"hr_hat": loop["hr_hat"], "lr": loop["lr"], "loss": loop["loss"]}
+        super().__call__()
+
+
+DUMP_BYTES = 63_000_000                     # the arrays of --dump-outputs; the .npy headers stay within 64 MB with them
+
+
+def dump_outputs(path, arrays):
+    """Writes ``arrays`` ({name: (tensor, cap)}) as float32 (float64 stays float64) ``path/<name>.npy``, at most DUMP_BYTES in all.  An
+    array with more elements than its share of the budget (and than its ``cap``, if given) is replaced by the elements at a fixed seeded
+    set of flat indices: the same for every run with the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    names = list(arrays)
+    esz = {k: 8 if arrays[k][0].dtype == torch.float64 else 4 for k in names}
+    want = {k: esz[k] * (arrays[k][0].numel() if arrays[k][1] is None else min(arrays[k][0].numel(), arrays[k][1])) for k in names}
+    left, keep = DUMP_BYTES, {}                # bytes; the smaller arrays are kept whole, the larger share what is left
+    for j, k in enumerate(sorted(names, key=want.get)):
+        keep[k] = min(want[k], left // (len(names) - j)) // esz[k]
+        left -= keep[k] * esz[k]
+    for k in names:
+        t = arrays[k][0].detach()
+        n = t.numel()
+        if keep[k] < n:
+            idx = np.unique(np.random.default_rng(0).integers(0, n, keep[k]))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(path, f"{k}.npy"), t.cpu().numpy())
+
+
 def spawn_ranks(n, argv):
     """``python bench.py --gpus N`` without a launcher around it: start the N ranks as a CHILD ``torch.distributed.run`` (one process per
     GPU, RCCL) before this process has made any HIP call -- counting devices does not initialise the GPU, and a process that has touched
@@ -396,12 +440,17 @@ def main():
     ap.add_argument("--model", default="resunet", choices=["resunet", "rdresunet"])
     ap.add_argument("--crappifier", default="gaussian", choices=["gaussian", "poisson"])
     ap.add_argument("--tile-workers", type=int, default=16, help="processes generating the synthetic tiles (1 under rocprofv3: no forks behind the profiler)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the infer / sheet / f32 legs that follow the headline region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region also run the roofline passes, the rank checks of N > 1, the extra legs and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the infer / sheet / f32 / c3 / c4 / host-fed legs")
     ap.add_argument("--no-graph", action="store_true", help="PSSR_GRAPH=0: every kernel launched from Python by the drivers")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -418,8 +467,8 @@ def main():
     n_tiles = args.tiles if args.mode != "sheet" else 0
     need = (args.warmup + args.steps) * args.batch
     tiles_np = make_tiles(n_tiles, hr_res, args.channels, rank_env, args.tile_workers) if n_tiles else None      # before CUDA: the pool forks
-    extras = (rank_env == 0 and world_env == 1 and args.mode == "train" and not args.no_extras and args.model == "resunet" and args.channels == 1
-              and args.lr_res == 128)
+    extras = (args.full and rank_env == 0 and world_env == 1 and args.mode == "train" and not args.no_extras and args.model == "resunet"
+              and args.channels == 1 and args.lr_res == 128)
     # BASELINE config 4: 3-frame 1024^2 HR tiles.  96 of them: 86 training tiles = 10 full batches of 8, so that the 3 + 5 steps of the leg
     # stay clear of the epoch's partial last batch (one eager step on a new engine plan: 30 ms once per run, not a step of the replayed graph)
     tiles_c4 = make_tiles(96, 1024, 3, 77, args.tile_workers) if extras else None
@@ -462,11 +511,15 @@ def main():
     loss_fn = SSIMLoss(channels=args.channels, mix=0.8)
     quiet = open(os.devnull, "w")
 
-    def run_train(model, dataset, batch, warmup, steps, dataloader_kwargs=None, loss=None):
-        """train_paired until the clock has seen warmup + steps steps; returns seconds for the timed steps (max over ranks)."""
+    last_step = {}
+
+    def run_train(model, dataset, batch, warmup, steps, dataloader_kwargs=None, loss=None, keep=False):
+        """train_paired until the clock has seen warmup + steps steps; returns seconds for the timed steps (max over ranks).  ``keep``: the
+        last timed step's tensors go to ``last_step``."""
         loss = loss_fn if loss is None else loss
         opt = FusedAdamW(model.parameters(), lr=1e-3)
-        clock = StepClock(warmup, steps, barrier)
+        clock = (KeepingStepClock if keep else StepClock)(warmup, steps, barrier)
+        random.seed(1234 + rank)        # the driver's epoch shuffle and rotation draws (Python's random, as upstream): same batches every run
         per_epoch = (len(dataset) - len(dataset.val_idx)) // world // batch
         epochs = max(1, -(-(warmup + steps) // max(per_epoch, 1)))
         old = sys.stdout
@@ -479,6 +532,8 @@ def main():
             sys.stdout = old
         if clock.elapsed is None:
             raise SystemExit(f"bench: the dataset holds fewer than {warmup + steps} batches of {batch}")
+        if keep:
+            last_step.update(clock.last)
         el = clock.elapsed
         if world > 1:
             t = torch.tensor([el], device=dev, dtype=torch.float64)
@@ -486,8 +541,9 @@ def main():
             el = t.item()
         return el, opt
 
-    def run_infer(model, dataset, batch, reps=2):
-        """predict_images twice (the first call captures the graph); returns seconds of the second call."""
+    def run_infer(model, dataset, batch, reps=2, keep=False):
+        """predict_images twice (the first call captures the graph); returns seconds of the second call.  ``keep``: its predictions go to
+        ``last_step``."""
         model.eval()
         for r in range(reps):
             barrier()
@@ -496,6 +552,8 @@ def main():
             barrier()
             el = time.perf_counter() - t0
         assert len(out) == len(dataset.val_idx)
+        if keep:
+            last_step["hr_hat"] = torch.stack([torch.as_tensor(v) for v in out.values()])
         return el
 
     res = {}
@@ -507,12 +565,12 @@ def main():
 
     if args.mode == "train":
         ds = DeviceTileDataset(tiles_dev, hr_res=hr_res, lr_scale=4, crappifier=crap, val_split=0.1, rotation=True, device=dev, seed=1234 + rank)
-        elapsed, opt = run_train(model, ds, args.batch, args.warmup, args.steps)
+        elapsed, opt = run_train(model, ds, args.batch, args.warmup, args.steps, keep=bool(args.dump_outputs))
         steps_done = args.steps
     elif args.mode == "infer":
         ds = DeviceTileDataset(tiles_dev, hr_res=hr_res, lr_scale=4, crappifier=crap, val_split=1.0, rotation=False, device=dev, seed=1234 + rank)
         ds.device_outputs = True
-        elapsed = run_infer(model, ds, args.batch)
+        elapsed = run_infer(model, ds, args.batch, keep=bool(args.dump_outputs))
         steps_done = -(-len(ds.val_idx) // args.batch)
         args.steps, args.warmup = steps_done, steps_done
     else:
@@ -526,15 +584,29 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            predict_sheet(model, sheet, tile_res=args.lr_res, overlap=32, margin=8, batch_size=args.batch, device=dev, to_numpy=False)
+            pred = predict_sheet(model, sheet, tile_res=args.lr_res, overlap=32, margin=8, batch_size=args.batch, device=dev, to_numpy=False)
         barrier()
         elapsed = time.perf_counter() - t0
         per_step, steps_done = sheet_tiles, args.steps
+        if args.dump_outputs:
+            last_step["sheet"] = pred
+        del pred
+
+    # ---- what the timed path computed in its last step, taken before anything else runs on the model
+    if args.dump_outputs and rank == 0:
+        arrays = {k: (v, None) for k, v in last_step.items()}
+        if args.mode == "train":
+            arrays["params"] = (torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]), 4_000_000)
+            arrays["buffers"] = (torch.cat([b.detach().reshape(-1).float() for b in model.buffers() if b.dtype.is_floating_point]), None)
+            arrays["loss"] = (torch.as_tensor(last_step["loss"]).detach().double().reshape(-1), None)
+        dump_outputs(args.dump_outputs, arrays)
+        del arrays
+    last_step.clear()
 
     # ---- N > 1: the ranks' parameters must be identical after the timed steps (same averaged gradients, same update kernel): a checksum
     # of the flat parameter buffer (sum and sum of magnitudes, f64) is all-gathered and compared exactly, BEFORE anything rank-specific runs
     in_sync = None
-    if world > 1 and args.mode == "train":
+    if args.full and world > 1 and args.mode == "train":
         pf = opt._flat[0]["flat"].double()
         chk = torch.stack([pf.sum(), pf.abs().sum()])
         every = [torch.zeros_like(chk) for _ in range(world)]
@@ -543,7 +615,7 @@ def main():
         del pf
     # ---- N > 1: what the gradient exchange costs and how much of it the backward pass hides
     res_comm = None
-    if world > 1 and args.mode == "train":
+    if args.full and world > 1 and args.mode == "train":
         flat = model._engine._flat_grad
         probe = torch.zeros_like(flat)
         ts = []
@@ -571,7 +643,7 @@ def main():
                            "bus_GBps": round(2 * (world - 1) / world * flat.numel() * 4 / (comm_ms * 1e-3) / 1e9, 1)}
     # ---- roofline of the dominant kernel set: the same kernels once more, one at a time on the launch stream, HIP events
     conv, hbm_objects = None, []
-    if rank == 0 and args.dtype in ("bf16", "fp16") and args.mode != "sheet":
+    if args.full and rank == 0 and args.dtype in ("bf16", "fp16") and args.mode != "sheet":
         eng = model._engine
         # (world > 1: only rank 0 runs these two extra optimizer steps -- its weights, optimizer state and BatchNorm buffers are put back
         # afterwards, so that the ranks leave the bench as they left the timed region: in sync)
@@ -774,7 +846,7 @@ def main():
             res["extras_error"] = f"{type(e).__name__}: {e}"
             import traceback
             traceback.print_exc(file=sys.stderr)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "resunet":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "resunet":
         res["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(res))

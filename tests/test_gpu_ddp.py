@@ -97,7 +97,7 @@ def test_bench_gpus_2_starts_two_ranks_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(PSSR_BENCH_FORCE_DEVICE="0", PSSR_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "3", "--tiles", "256",
-                        "--no-cpu-baseline", "--no-extras", "--tile-workers", "4"], env=env, capture_output=True, text=True, timeout=280)
+                        "--full", "--no-cpu-baseline", "--no-extras", "--tile-workers", "4"], env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, r.stdout[-1000:]
@@ -119,7 +119,7 @@ def test_bench_gpus_2_reduce_scatter_knob():
     for split in ("1", "0"):
         env["PSSR_DDP_SPLIT"] = split
         r = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "3", "--tiles", "256",
-                            "--no-cpu-baseline", "--no-extras", "--tile-workers", "4"], env=env, capture_output=True, text=True, timeout=280)
+                            "--full", "--no-cpu-baseline", "--no-extras", "--tile-workers", "4"], env=env, capture_output=True, text=True, timeout=280)
         assert r.returncode == 0, r.stderr[-2000:]
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][0])
         assert d["comm"]["weights_in_sync"] is True and d["comm"]["reduce"] == "reduce_scatter+all_gather"
