@@ -648,6 +648,40 @@ typedef struct pssr_fold_batch {
 } pssr_fold_batch;
 int pssr_f64_to_f32_batch(const pssr_fold_batch* items, int n_items, int stripes, pssr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * GradHist soft histogram (pssr/models/_blocks.py:94-112) and the crappifier loss around it (pssr/train.py:388-402), for
+ * train_crappifier (pssr/train.py:168-322).  Per image over its n = C*H*W f32 values: bins centred at
+ * c_k = lo + (hi - lo) / bins * (k + 1/2), s_k(x) = sigmoid(sigma (x - c_k)), s_{-1} = 1.  Reproducible bit for bit (no atomics);
+ * the work skipped and what it can drop are bounded in csrc/hist.hip's header comment.
+ */
+#define PSSR_HIST_CLAMP 1          /* clamp the first operand to [0, 255] on load (and mask its gradient: torch.clamp, inclusive) */
+#define PSSR_HIST_ACCUMULATE 2     /* pssr_gradhist_bwd adds into dx */
+#define PSSR_HIST_MAX_BINS 8192    /* both kernels take 1 .. 8192 bins (the backward keeps its bins' gradients in LDS) */
+int64_t pssr_gradhist_workspace_bytes(int batch, int64_t n, int bins);
+/* h0[b, j] = sum_i (s_{j-1}(x_i) - s_j(x_i)), x = a0 - b0 (b0 may be NULL: x = a0; PSSR_HIST_CLAMP clamps a0); the optional second pair
+ * (a1, b1) -> h1 in the same launch.  [batch, bins] outputs; workspace: pssr_gradhist_workspace_bytes bytes. */
+int pssr_gradhist_fwd(const float* a0, const float* b0, const float* a1, const float* b1, float* h0, float* h1, float* workspace,
+                      int64_t workspace_bytes, int batch, int64_t n, int bins, float lo, float hi, float sigma, int flags,
+                      pssr_stream_t stream);
+/* dx_i = sigma sum_k s_k (1 - s_k) (G[k+1] [k+1 < bins] - G[k]) with x = xa - xb as in the forward and
+ * G = (g - g_ref) * g_scale * dev_scale[0] (g_ref, dev_scale optional): the fused crappifier loss forms
+ * dL/dh = 2 (p - t) / (B bins W^2) * P * dL on the device. */
+int pssr_gradhist_bwd(const float* xa, const float* xb, const float* g, const float* g_ref, const float* dev_scale, float g_scale,
+                      float* dx, int batch, int64_t n, int bins, float lo, float hi, float sigma, int flags, pssr_stream_t stream);
+/* pred = clamp?(lr_hat) - ds_hr, target = lr - ds_hr (pssr/train.py:390-391; flags: PSSR_HIST_CLAMP = pssr/train.py:238-239) */
+int pssr_crappifier_profiles(const float* lr_hat, const float* lr, const float* ds_hr, float* pred, float* target, int64_t n, int flags,
+                             pssr_stream_t stream);
+/* dst = src[:, :, ::stride, ::stride] of [planes, h_in, w_in] into a dense [planes, ceil(h_in/stride), ceil(w_in/stride)] (pssr/train.py:233) */
+int pssr_subsample_f32(const float* src, float* dst, int64_t planes, int h_in, int w_in, int stride, pssr_stream_t stream);
+/* D = sum (pred_hist - target_hist)^2 * dist_scale over m values (F.mse_loss / W^2 with dist_scale = 1 / (m W^2)), P = ssim_loss[0]:
+ * out = [D * P, D, P] (pssr/train.py:397-401) */
+int pssr_crappifier_loss_combine(const float* pred_hist, const float* target_hist, int64_t m, const float* ssim_loss, float dist_scale,
+                                 float* out, pssr_stream_t stream);
+/* backward of D * P: out = [D * grad_out, P * grad_out] from parts = [L, D, P] */
+int pssr_crappifier_loss_bwd_scalars(const float* parts, const float* grad_out, float* out, pssr_stream_t stream);
+/* y = min(max(x, lo), hi), NaN kept (in place when y == x): nn.utils.clip_grad_value_ over a flat gradient buffer (pssr/train.py:244) */
+int pssr_clamp_f32(const float* x, float* y, int64_t n, float lo, float hi, pssr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,12 @@ def __getattr__(name):
     if name in ("train_paired",):
         from .train import train_paired
         return train_paired
+    if name in ("train_crappifier",):
+        from .train import train_crappifier
+        return train_crappifier
+    if name in ("GradHist",):
+        from .models import GradHist
+        return GradHist
     if name in ("predict_images",):
         from .predict import predict_images
         return predict_images

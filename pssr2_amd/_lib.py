@@ -100,6 +100,7 @@ def lib():
         _lib.pssr_last_error.restype = C.c_char_p
         _lib.pssr_packed_weight_bytes.restype = C.c_int64
         _lib.pssr_conv2d_workspace_bytes.restype = C.c_int64
+        _lib.pssr_gradhist_workspace_bytes.restype = C.c_int64
     return _lib
 
 

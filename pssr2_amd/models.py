@@ -482,3 +482,46 @@ class RDResUNetA:
                 n_blocks=[3, 3, 3, 3, 3, 3, 3], patch_size: int = 2, bottleneck: int = 4, compression: float = 0.5, drop_rate: float = 0):
         return RDResUNet(channels, hidden, scale, depth, dilations, pool_sizes, encoder_pool, rdnet_init, growth_rates, ds_blocks, ese_blocks,
                          n_blocks, patch_size, bottleneck, compression, drop_rate)
+
+
+GRADHIST_MAX_BINS = 8192          # PSSR_HIST_MAX_BINS (include/pssr_mi355.h)
+
+
+class _GradHistFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, bins, lo, hi, sigma):
+        from . import ops
+        if not x.is_cuda:
+            raise RuntimeError("pssr2_amd.GradHist runs on an MI355X (HIP) device only; there is no CPU fallback")
+        x = x.detach().contiguous().float()
+        ctx.save_for_backward(x)
+        ctx.cfg = (bins, lo, hi, sigma)
+        return ops.gradhist_fwd([(x, None)], bins, lo, hi, sigma)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import ops
+        (x,) = ctx.saved_tensors
+        bins, lo, hi, sigma = ctx.cfg
+        dx = torch.empty_like(x)
+        ops.gradhist_bwd(x, None, g.detach().contiguous().float(), dx, bins, lo, hi, sigma)
+        return dx, None, None, None, None
+
+
+class GradHist(nn.Module):
+    def __init__(self, bins: int = 512, range=(-256, 256), sigma: int = 5):
+        r"""Differentiable soft histogram per image over all its values (pssr/models/_blocks.py:94-112): ``forward(x)`` of a
+        ``[B, ...]`` f32 tensor returns ``[B, bins]``.  Forward and backward are the HIP kernels of csrc/hist.hip; the
+        ``[B, bins + 1, C*H*W]`` intermediates of the reference are never formed.
+        """
+        super().__init__()
+        assert range[1] > range[0]
+        if not 1 <= int(bins) <= GRADHIST_MAX_BINS:
+            raise ValueError(f"GradHist takes 1 to {GRADHIST_MAX_BINS} bins on the MI355X (PSSR_HIST_MAX_BINS), got {bins}")
+        self.bins, self.range = int(bins), (float(range[0]), float(range[1]))
+        self.delta = float(range[1] - range[0]) / float(bins)
+        self.centers = float(range[0]) + self.delta * (torch.arange(bins).float() + 0.5)
+        self.sigma = sigma
+
+    def forward(self, x):
+        return _GradHistFunction.apply(x, self.bins, self.range[0], self.range[1], float(self.sigma))

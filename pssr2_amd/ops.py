@@ -723,3 +723,74 @@ def bilinear_up(x, out, n, hs, ws, h, w, c, dtype, in_coff=0, out_coff=0):
 def bilinear_up_bwd(dout, din, n, hs, ws, h, w, c, dtype, do_coff=0, di_coff=0):
     L.check(L.lib().pssr_bilinear_up_bwd(L.ptr(dout), dout.shape[-1], do_coff, L.ptr(din), din.shape[-1], di_coff, n, hs, ws, h, w, c, dtype,
                                          L.stream_ptr()), "pssr_bilinear_up_bwd")
+
+
+HIST_CLAMP, HIST_ACCUMULATE = 1, 2
+
+
+def gradhist_fwd(pairs, bins, lo, hi, sigma, clamp_first=False):
+    """Soft histograms of up to two inputs in one launch (pssr_gradhist_fwd).  ``pairs``: [(a, b)] or [(a, b), (a1, b1)] of f32
+    [batch, ...] tensors (b may be None: the histogram of a itself).  Returns one [batch, bins] f32 tensor per pair."""
+    a0, b0 = pairs[0]
+    a1, b1 = pairs[1] if len(pairs) > 1 else (None, None)
+    batch, n = a0.shape[0], a0[0].numel()
+    for t in (a0, b0, a1, b1):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == batch * n)
+    lib = L.lib()
+    ws_bytes = lib.pssr_gradhist_workspace_bytes(batch, C.c_int64(n), bins)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=a0.device)
+    h0 = torch.empty(batch, bins, dtype=torch.float32, device=a0.device)
+    h1 = torch.empty(batch, bins, dtype=torch.float32, device=a0.device) if a1 is not None else None
+    L.check(lib.pssr_gradhist_fwd(L.ptr(a0), L.ptr(b0), L.ptr(a1), L.ptr(b1), L.ptr(h0), L.ptr(h1), L.ptr(ws), C.c_int64(ws_bytes), batch,
+                                  C.c_int64(n), bins, C.c_float(lo), C.c_float(hi), C.c_float(sigma), HIST_CLAMP if clamp_first else 0,
+                                  L.stream_ptr()), "pssr_gradhist_fwd")
+    return [h0] if h1 is None else [h0, h1]
+
+
+def gradhist_bwd(xa, xb, g, dx, bins, lo, hi, sigma, g_ref=None, dev_scale=None, g_scale=1.0, clamp=False, accumulate=False):
+    batch, n = xa.shape[0], xa[0].numel()
+    for t in (xa, xb, dx):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == batch * n)
+    for t in (g, g_ref):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == batch * bins)
+    flags = (HIST_CLAMP if clamp else 0) | (HIST_ACCUMULATE if accumulate else 0)
+    L.check(L.lib().pssr_gradhist_bwd(L.ptr(xa), L.ptr(xb), L.ptr(g), L.ptr(g_ref), L.ptr(dev_scale), C.c_float(g_scale), L.ptr(dx), batch,
+                                      C.c_int64(n), bins, C.c_float(lo), C.c_float(hi), C.c_float(sigma), flags, L.stream_ptr()),
+            "pssr_gradhist_bwd")
+    return dx
+
+
+def crappifier_profiles(lr_hat, lr, ds_hr, pred, target, clamp=False):
+    L.check(L.lib().pssr_crappifier_profiles(L.ptr(lr_hat), L.ptr(lr), L.ptr(ds_hr), L.ptr(pred), L.ptr(target), C.c_int64(lr.numel()),
+                                             HIST_CLAMP if clamp else 0, L.stream_ptr()), "pssr_crappifier_profiles")
+
+
+def subsample(src, stride, out=None):
+    """``src[:, :, ::stride, ::stride]`` as a dense f32 tensor (pssr_subsample_f32)."""
+    assert src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and src.dim() >= 2
+    hh, ww = src.shape[-2:]
+    shape = (*src.shape[:-2], -(-hh // stride), -(-ww // stride))
+    out = torch.empty(shape, dtype=torch.float32, device=src.device) if out is None else out
+    planes = src.numel() // (hh * ww)
+    L.check(L.lib().pssr_subsample_f32(L.ptr(src), L.ptr(out), C.c_int64(planes), hh, ww, stride, L.stream_ptr()), "pssr_subsample_f32")
+    return out
+
+
+def crappifier_loss_combine(pred_hist, target_hist, ssim_loss, dist_scale, out):
+    L.check(L.lib().pssr_crappifier_loss_combine(L.ptr(pred_hist), L.ptr(target_hist), C.c_int64(pred_hist.numel()), L.ptr(ssim_loss),
+                                                 C.c_float(dist_scale), L.ptr(out), L.stream_ptr()), "pssr_crappifier_loss_combine")
+
+
+def crappifier_loss_bwd_scalars(parts, grad_out, out):
+    L.check(L.lib().pssr_crappifier_loss_bwd_scalars(L.ptr(parts), L.ptr(grad_out), L.ptr(out), L.stream_ptr()),
+            "pssr_crappifier_loss_bwd_scalars")
+
+
+def clamp_f32(x, lo, hi, out=None):
+    """``torch.clamp(x, lo, hi)`` of a contiguous f32 tensor (in place when ``out is x``)."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+    out = torch.empty_like(x) if out is None else out
+    if x.numel():
+        L.check(L.lib().pssr_clamp_f32(L.ptr(x), L.ptr(out), C.c_int64(x.numel()), C.c_float(lo), C.c_float(hi), L.stream_ptr()),
+                "pssr_clamp_f32")
+    return out

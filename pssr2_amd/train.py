@@ -34,13 +34,18 @@ def _metric_ssim(hr_hat, hr, image_range):
 
 
 def _collage(lr, hr_hat, hr, crop_res, lr_scale):
-    """Small PIL collage of (LR | prediction | HR) rows for ``collage_dir`` (pssr/train.py:155-158)."""
+    """Small PIL collage of (LR | prediction | HR) rows for ``collage_dir`` (pssr/train.py:155-158, 316-318).  A prediction smaller
+    than HR (train_crappifier's LR-sized ``lr_hat``) is enlarged to HR size by nearest neighbour, as pssr/predict.py:227-230 does."""
     import numpy as np
     from PIL import Image
     rows = []
     for i in range(min(len(lr), 4)):
         up = np.kron(np.clip(lr[i, lr.shape[1] // 2].numpy(), 0, 255), np.ones((lr_scale, lr_scale)))
-        tiles = [up, np.clip(hr_hat[i, hr_hat.shape[1] // 2].numpy(), 0, 255), np.clip(hr[i, hr.shape[1] // 2].numpy(), 0, 255)]
+        pred = np.clip(hr_hat[i, hr_hat.shape[1] // 2].numpy(), 0, 255)
+        if pred.shape != tuple(hr.shape[-2:]):
+            ry, rx = hr.shape[-2] // pred.shape[0], hr.shape[-1] // pred.shape[1]
+            pred = np.kron(pred, np.ones((ry, rx)))
+        tiles = [up, pred, np.clip(hr[i, hr.shape[1] // 2].numpy(), 0, 255)]
         rows.append(np.concatenate([t[:crop_res, :crop_res] for t in tiles], axis=1))
     return Image.fromarray(np.concatenate(rows, axis=0).astype(np.uint8))
 
@@ -217,5 +222,153 @@ def train_paired(model: nn.Module, dataset: Dataset, batch_size: int, loss_fn: n
                 scheduler.step(val_loss) if include_metric else scheduler.step()
                 if hasattr(optim, "sync_device_lr"):
                     optim.sync_device_lr()
+
+    return train_losses, val_losses
+
+
+def _crappifier_loss(lr, lr_hat, ds_hr, hist_fn, ssim_loss, clamp: bool = False):
+    """pssr/train.py:388-402 on the device: ``mse(hist_fn(lr_hat - ds_hr), hist_fn(lr - ds_hr)) / W_lr**2 * ssim_loss(lr_hat - ds_hr,
+    lr - ds_hr)`` as one autograd node (util._CrappifierLossFunction).  ``clamp``: ``lr_hat`` is clamped to [0, 255] on load, which is
+    what pssr/train.py:238-239 does before the call."""
+    from .models import GradHist
+    from .util import SSIMLoss, _CrappifierLossFunction
+    if not isinstance(hist_fn, GradHist) or not isinstance(ssim_loss, SSIMLoss):
+        raise TypeError("the device crappifier loss takes a pssr2_amd GradHist and a pssr2_amd SSIMLoss")
+    hist_cfg = (hist_fn.bins, hist_fn.range[0], hist_fn.range[1], float(hist_fn.sigma))
+    ssim_cfg = (ssim_loss.win, float(ssim_loss.mix), bool(ssim_loss.ms), ssim_loss.K[0], ssim_loss.K[1], 1.0, ssim_loss.weights)
+    return _CrappifierLossFunction.apply(lr, lr_hat, ds_hr, hist_cfg, ssim_cfg, bool(clamp))
+
+
+def _clip_grad_value(model, clip):
+    """nn.utils.clip_grad_value_(model.parameters(), clip) (pssr/train.py:243-244).  A pssr2_amd model keeps every gradient in its
+    engine's flat buffer: one pssr_clamp_f32 launch over it (its alignment padding holds zeros, which stay zeros)."""
+    from . import ops
+    engine = getattr(model, "_engine", None)
+    grads = [p.grad for p in model.parameters() if p.grad is not None]
+    if not grads:
+        return
+    flat = getattr(engine, "_flat_grad", None) if engine is not None else None
+    if flat is not None and len(grads) == len(engine._gviews) and all(g.data_ptr() == v.data_ptr() for g, v in zip(grads, engine._gviews)):
+        ops.clamp_f32(flat, -clip, clip, out=flat)
+    elif engine is not None:
+        for g in grads:
+            ops.clamp_f32(g, -clip, clip, out=g)
+    else:                                               # a foreign nn.Module
+        nn.utils.clip_grad_value_(model.parameters(), clip)
+
+
+def train_crappifier(model: nn.Module, dataset: Dataset, batch_size: int, optim: torch.optim.Optimizer, epochs: int, sigma: int = 5,
+                     clip: float = 3, device: str = "cpu", scheduler=None, log_frequency: int = 50, checkpoint_dir: str = None,
+                     collage_dir: str = None, clamp: bool = False, dataloader_kwargs=None, callbacks=None):
+    r"""EXPERIMENTAL, NOT CURRENTLY RECOMMENDED FOR MOST WORKFLOWS!
+
+    Trains an :class:`nn.Module` model as a crappifier on high-low-resolution paired data (pssr/train.py:168-322).
+    The model must output an image the same size as the input/have a `scale` value of 1.
+    This is not necessary if you are using a :class:`Crappifier` instance as your crappifier.
+
+    Same arguments, defaults and return value ``(train_losses, val_losses)`` as the reference; ``callbacks`` (documented and read
+    by the reference's body, missing from its signature) is the trailing keyword.  The loss (GradHist distance x SSIM of the noise
+    profiles) runs as HIP kernels (util._CrappifierLossFunction), the strided subsample ``hr[:, :, ::s, ::s]`` and the gradient
+    clipping too.  A pssr2_amd model must have ``scale == 1`` (``ValueError`` before the first step) and an f32 or bf16
+    ``compute_dtype``; fp16 storage (which needs a loss scaler) and multi-process runs raise ``NotImplementedError``.
+    """
+    from . import ops
+    from .models import GradHist
+    from .util import SSIMLoss
+    rec = getattr(model, "reconstruction", None)
+    if rec is not None and getattr(rec, "scale", 1) != 1:
+        raise ValueError(f"train_crappifier needs a model with scale 1 (its output has the input's size); got scale={rec.scale}")
+    if getattr(model, "compute_dtype", None) == torch.float16:
+        raise NotImplementedError("train_crappifier with fp16 storage needs a loss scaler, which this driver does not have; "
+                                  "use compute_dtype torch.float32 or torch.bfloat16")
+    rank, world = D.rank_world()
+    if world > 1:
+        raise NotImplementedError("train_crappifier runs on one process; multi-GPU training of a crappifier is not implemented")
+    dataloader_kwargs = {} if dataloader_kwargs is None else dataloader_kwargs
+    callbacks, callback_locals = _get_callbacks(callbacks)
+    image_range = 255
+
+    train_dataloader = DataLoader(dataset, batch_size, sampler=_RandomIterIdx(_invert_idx(dataset.val_idx, len(dataset))), **dataloader_kwargs)
+    val_dataloader = DataLoader(dataset, batch_size, sampler=_RandomIterIdx(dataset.val_idx, seed=True), **dataloader_kwargs)
+    include_metric = type(scheduler) == torch.optim.lr_scheduler.ReduceLROnPlateau
+
+    model.to(device)
+
+    hist_fn = GradHist(sigma=sigma)
+    ssim_loss = SSIMLoss(ms=False)
+
+    def _subsample(hr, lr):
+        scale = int(hr.shape[-1] / lr.shape[-1])
+        hr = hr.to(device).float().contiguous()
+        if not hr.is_cuda:
+            raise RuntimeError("pssr2_amd.train_crappifier runs on an MI355X (HIP) device only; there is no CPU fallback")
+        return ops.subsample(hr, scale)
+
+    def _clamped(t):
+        return ops.clamp_f32(t.detach().contiguous(), 0, image_range) if clamp else t
+
+    train_losses, val_losses = [], []
+    for epoch in range(epochs):
+        model.train()
+        print(f"Epoch {epoch}:")
+
+        progress = tqdm(train_dataloader)
+        for batch_idx, (hr, lr) in enumerate(progress):
+            ds_hr = _subsample(hr, lr)
+
+            lr_hat = model(ds_hr)
+            loss = _crappifier_loss(lr.to(device), lr_hat, ds_hr, hist_fn, ssim_loss, clamp=clamp)
+            loss.backward()
+
+            if clip is not None and clip > 0:
+                _clip_grad_value(model, clip)
+
+            optim.step()
+            optim.zero_grad()
+
+            if batch_idx % log_frequency == 0 or batch_idx == len(progress) - 1:
+                train_losses.append(loss.item())
+                if hasattr(progress, "set_description"):
+                    progress.set_description(f"loss[{loss.item():.4f}]")
+
+            if batch_idx == max(len(progress), 2) - 2:
+                last_full = [lr.cpu(), _clamped(lr_hat).detach().cpu(), hr.cpu()]      # accessible from callbacks via locals
+
+            for idx, callback in enumerate(callbacks):
+                callback(locals()) if callback_locals[idx] else callback()
+
+        model.eval()
+        print(f"Epoch {epoch} validation...")
+
+        val_loss = []
+        progress = tqdm(val_dataloader)
+        with torch.no_grad():
+            for batch_idx, (hr, lr) in enumerate(progress):
+                ds_hr = _subsample(hr, lr)
+                lr_hat = model(ds_hr)
+                loss = _crappifier_loss(lr.to(device), lr_hat, ds_hr, hist_fn, ssim_loss, clamp=clamp)
+                val_loss.append(loss.detach().reshape(1))            # stays on the device: one sync per epoch
+
+                if batch_idx == max(len(progress), 2) - 2:
+                    last_full_val = [lr.cpu(), _clamped(lr_hat).cpu(), hr.cpu()]
+
+        val_loss = [float(v) for v in torch.cat(val_loss).cpu()]
+        val_loss = sum(val_loss) / len(val_loss)
+        val_losses.append(val_loss)
+        print(f"Epoch {epoch} validation loss: {val_loss:4f}\n")
+
+        if checkpoint_dir and epoch < epochs - 1:
+            os.makedirs(checkpoint_dir, exist_ok=True)
+            torch.save(model.state_dict(), f"{checkpoint_dir}/checkpoint{epoch}_{model.__class__.__name__}_{val_loss:.4f}.pth")
+
+        if collage_dir:
+            collage = _collage(*last_full_val, crop_res=dataset.crop_res, lr_scale=dataset.lr_scale)
+            os.makedirs(collage_dir, exist_ok=True)
+            collage.save(f"{collage_dir}/epoch{epoch}_loss{val_loss:.4f}.png")
+
+        if scheduler:
+            scheduler.step(val_loss) if include_metric else scheduler.step()
+            if hasattr(optim, "sync_device_lr"):
+                optim.sync_device_lr()
 
     return train_losses, val_losses

@@ -156,6 +156,52 @@ class SSIMLoss(nn.Module):
         return _SSIMLossFunction.apply(input, target, cfg, float(divisor))
 
 
+class _FnCtx:
+    """Stand-in autograd context: lets a Function drive another Function's forward / backward inside its own node."""
+
+    def __init__(self, needs_input_grad):
+        self.needs_input_grad = needs_input_grad
+
+
+class _CrappifierLossFunction(torch.autograd.Function):
+    """``_crappifier_loss`` (pssr/train.py:388-402) as one autograd node over HIP kernels, gradient wrt ``lr_hat`` only:
+    pred = clamp?(lr_hat) - ds_hr, target = lr - ds_hr (pssr_crappifier_profiles); both GradHist histograms in one launch;
+    D = mean((H(pred) - H(target))^2) / W_lr^2 and L = D * P (pssr_crappifier_loss_combine) with P = SSIMLoss(pred, target) through
+    _SSIMLossFunction's kernels.  Backward: the SSIM backward with grad_out = D * dL, then the histogram backward ADDS
+    P * dL * dD/dpred into the same buffer (its dL/dh = 2 (p - t) / (B bins W^2) is formed in the kernel) and masks it where the
+    clamp cut."""
+
+    @staticmethod
+    def forward(ctx, lr, lr_hat, ds_hr, hist_cfg, ssim_cfg, clamp=False):
+        if not (lr.is_cuda and lr_hat.is_cuda and ds_hr.is_cuda):
+            raise RuntimeError("pssr2_amd crappifier loss runs on an MI355X (HIP) device only; there is no CPU fallback")
+        if not (lr.shape == lr_hat.shape == ds_hr.shape):
+            raise ValueError(f"lr, lr_hat and ds_hr must have one shape, got {tuple(lr.shape)}, {tuple(lr_hat.shape)}, {tuple(ds_hr.shape)}")
+        lr, lr_hat, ds_hr = (t.detach().contiguous().float() for t in (lr, lr_hat, ds_hr))
+        bins, lo, hi, sigma = hist_cfg
+        pred, target = torch.empty_like(lr_hat), torch.empty_like(lr)
+        ops.crappifier_profiles(lr_hat, lr, ds_hr, pred, target, clamp)
+        hp, ht = ops.gradhist_fwd([(pred, None), (target, None)], bins, lo, hi, sigma)
+        sctx = _FnCtx((ctx.needs_input_grad[1], False, False, False))
+        p_loss = _SSIMLossFunction.forward(sctx, pred, target, ssim_cfg)
+        parts = torch.empty(3, dtype=torch.float32, device=lr.device)          # [L, D, P]
+        batch, w_lr = lr.shape[0], lr.shape[-1]
+        ops.crappifier_loss_combine(hp, ht, p_loss, 1.0 / (batch * bins) / (w_lr * w_lr), parts)
+        ctx.state = (lr_hat, ds_hr, hp, ht, parts, sctx, hist_cfg, bool(clamp), batch, w_lr)
+        return parts[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lr_hat, ds_hr, hp, ht, parts, sctx, (bins, lo, hi, sigma), clamp, batch, w_lr = ctx.state
+        go = grad_out.detach().float().reshape(1).contiguous()
+        sc = torch.empty(2, dtype=torch.float32, device=go.device)             # [D * dL, P * dL]
+        ops.crappifier_loss_bwd_scalars(parts, go, sc)
+        g = _SSIMLossFunction.backward(sctx, sc[0:1])[0]
+        ops.gradhist_bwd(lr_hat, ds_hr, hp, g, bins, lo, hi, sigma, g_ref=ht, dev_scale=sc[1:2], g_scale=2.0 / (batch * bins * w_lr * w_lr),
+                         clamp=clamp, accumulate=True)
+        return None, g, None, None, None, None
+
+
 def ssim(X, Y, data_range=255, win_size=11, win_sigma=1.5):
     """Mean SSIM (the in-loop metric of pssr/train.py:109), forward only."""
     cfg = (_gauss_1d(win_size, win_sigma), 1.0, False, 0.01, 0.03, float(data_range), (1.0,))
