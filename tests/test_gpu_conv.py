@@ -59,6 +59,8 @@ CASES += [
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("case", CASES)
 def test_conv_forward_and_dgrad(case, dt, pipeline_mode):
+    """The forward leg stores at out_coff=4, so it runs the generic epilogue (and never v3); tests/test_gpu_conv_exact.py covers the
+    8-channel one."""
     from pssr2_amd import ops, _lib as L
     n, cin, cout, h, w, ks = case
     g = torch.Generator().manual_seed(hash(case) % 1000)
