@@ -684,6 +684,28 @@ int pssr_crappifier_loss_bwd_scalars(const float* parts, const float* grad_out, 
 /* y = min(max(x, lo), hi), NaN kept (in place when y == x): nn.utils.clip_grad_value_ over a flat gradient buffer (pssr/train.py:244) */
 int pssr_clamp_f32(const float* x, float* y, int64_t n, float lo, float hi, pssr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Noise-profile statistics of approximate_crappifier's objective (pssr/train.py:348-386), csrc/profile.hip.
+ * Per image over its per_image = C*H*W values: v = a - b in f32 (pssr/train.py:372-373), b the reduced HR (uint8), a the crappified
+ * image (f32, not rounded, not clipped) or the real LR (uint8);
+ *   hist[image][k], k = 0 .. 510 = np.histogram(v, np.arange(-256, 256)) (pssr/train.py:375-377): -256 + k <= v < -255 + k, the last
+ *     bin also v == 255; values below -256, above 255, NaN and +-inf are counted nowhere;
+ *   sum[image] = sum of every v in f64 (pssr/train.py:382 takes the mean over the whole image).
+ * Counts are exact; the sums are added in a fixed order: bit-identical from run to run.  workspace:
+ * pssr_noise_profile_workspace_bytes(images, per_image) bytes (0 when every image is one workgroup's; NULL is accepted then).
+ */
+#define PSSR_PROFILE_BINS 511
+int64_t pssr_noise_profile_workspace_bytes(int images, int64_t per_image);
+int pssr_noise_profile_f32(const float* a, const uint8_t* b, int32_t* hist, double* sum, int images, int64_t per_image, void* workspace,
+                           int64_t workspace_bytes, pssr_stream_t stream);
+int pssr_noise_profile_u8(const uint8_t* a, const uint8_t* b, int32_t* hist, double* sum, int images, int64_t per_image, void* workspace,
+                          int64_t workspace_bytes, pssr_stream_t stream);
+/* loss[i] = mean_k((t_k - p_k)^2) / width^2 + |target_sum[i] / per_image - pred_sum[i] / per_image| (pssr/train.py:381-384; the first
+ * term from an exact integer sum and the reference's two f64 divisions: bit for bit), terms (or NULL) [images][2] = the two terms,
+ * mean[0] = mean over images (pssr/train.py:386), all f64.  per_image <= 2^25. */
+int pssr_noise_profile_loss(const int32_t* pred_hist, const double* pred_sum, const int32_t* target_hist, const double* target_sum,
+                            int images, int64_t per_image, int width, double* loss, double* terms, double* mean, pssr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,12 @@ def __getattr__(name):
     if name in ("train_crappifier",):
         from .train import train_crappifier
         return train_crappifier
+    if name in ("approximate_crappifier",):
+        from .train import approximate_crappifier
+        return approximate_crappifier
+    if name in ("PairedArrayDataset", "PairedImageDataset", "DevicePairedTileDataset"):
+        from . import data
+        return getattr(data, name)
     if name in ("GradHist",):
         from .models import GradHist
         return GradHist

@@ -101,6 +101,13 @@ def lib():
         _lib.pssr_packed_weight_bytes.restype = C.c_int64
         _lib.pssr_conv2d_workspace_bytes.restype = C.c_int64
         _lib.pssr_gradhist_workspace_bytes.restype = C.c_int64
+        # noise-profile statistics (csrc/profile.hip): full signatures, so that a Python int is never truncated or mistyped
+        _lib.pssr_noise_profile_workspace_bytes.restype = C.c_int64
+        _lib.pssr_noise_profile_workspace_bytes.argtypes = [c_int, c_i64]
+        for name in ("pssr_noise_profile_f32", "pssr_noise_profile_u8"):
+            getattr(_lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_i64, c_void_p]
+        _lib.pssr_noise_profile_loss.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p]
     return _lib
 
 

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import glob
 import random
+import warnings
 from pathlib import Path
 
 import numpy as np
@@ -81,6 +82,24 @@ def _gen_pair(hr, hr_res, lr_scale, rotation, crappifier, transforms, n_frames, 
     if crappifier is not None:
         lr = crappifier.crappify(lr) if issubclass(type(crappifier), Crappifier) else crappifier(lr)
         lr = np.clip(lr.round(), 0, 255)
+    if n_frames is not None and n_frames[0] != n_frames[1]:
+        if not n_frames[1] > hr.shape[-3]:
+            hr = _slice_center(hr, n_frames[1])
+        if not n_frames[0] > lr.shape[-3]:
+            lr = _slice_center(lr, n_frames[0])
+    return _tensor_ready(hr, transforms, compact), _tensor_ready(lr, transforms, compact)
+
+
+def _transform_pair(hr, lr, hr_res, lr_res, rotation, transforms, n_frames, compact=False):
+    """Item of a real (HR, LR) pair (pssr/data.py:497-516): each side gets ``_gen_pair``'s geometry at its own resolution, one
+    (rot90, flip) draw serves both, and no crappifier runs."""
+    sides = []
+    for image, res in ((hr, hr_res), (lr, lr_res)):
+        image = _pad_image(_square_crop(image, res), res)
+        if rotation:
+            image = np.flip(np.rot90(image, axes=(1, 2)) if rotation[0] else image, axis=rotation[1])
+        sides.append(image)
+    hr, lr = sides
     if n_frames is not None and n_frames[0] != n_frames[1]:
         if not n_frames[1] > hr.shape[-3]:
             hr = _slice_center(hr, n_frames[1])
@@ -235,6 +254,115 @@ class ImageDataset(ArrayDataset):
         self.hr_files = files
 
 
+def _paired_stacks(hr_images, lr_images, who, keep_tensors=False):
+    out = []
+    for images in (hr_images, lr_images):
+        if not torch.is_tensor(images):
+            images = np.asarray(images)
+        elif not keep_tensors:
+            images = images.cpu().numpy()
+        if images.ndim == 3:
+            images = images[:, None]
+        if images.ndim != 4 or str(images.dtype).split(".")[-1] != "uint8":
+            raise ValueError(f"{who} expects uint8 images [N, C, H, W]")
+        out.append(images)
+    if len(out[0]) != len(out[1]):
+        raise ValueError(f"Mismatch between amounts of high-low-resolution images. Found {len(out[0])} high-resolution and "
+                         f"{len(out[1])} low-resolution images.")
+    return out
+
+
+class PairedArrayDataset(Dataset):
+    """Real (HR, LR) pairs in memory, uint8 [N, C, H, W] and [N, c, h, w]: the reference's ``PairedImageDataset`` (pssr/data.py:268-346)
+    without the files -- its defaults (``val_split=1``: every item is a validation item; ``split_seed=None``: the last images), its
+    attribute protocol and its item geometry (``_transform_pair``), for ``train_crappifier``, ``approximate_crappifier``,
+    ``test_metrics`` and ``predict_images(norm=True)``.  Every pair is one item: with ``n_frames=[lr, hr]`` of different lengths the
+    centre frames of the two stacks are taken, as ``_transform_pair`` does."""
+    _keep_tensors = False
+
+    def __init__(self, hr_images, lr_images, hr_res=512, lr_scale=4, n_frames=-1, val_split=1, rotation=True, split_seed=None,
+                 transforms=None, names=None):
+        self.hr_images, self.lr_images = _paired_stacks(hr_images, lr_images, type(self).__name__, self._keep_tensors)
+        self.n_frames = _get_n_frames(n_frames)
+        self.slices = [1] * len(self.hr_images)
+        self.val_idx = _get_val_idx(self.slices, val_split, split_seed)
+        self.is_lr = False
+        self.crop_res = min(hr_res, max(self.hr_images.shape[-2:]))
+        self.extra_hr_files = None
+        self.hr_res, self.lr_scale, self.rotation, self.transforms = hr_res, lr_scale, rotation, transforms
+        self.compact = False        # see ArrayDataset.compact
+        self.names = list(names) if names is not None else [f"image{i}" for i in range(len(self.hr_images))]
+
+    def __len__(self):
+        return sum(self.slices)
+
+    def _draw_rotation(self, idx, pp=False):
+        if self.rotation and not (idx in self.val_idx or pp):
+            return [bool(random.getrandbits(1)), random.choice((1, 2, (1, 2)))]      # the reference's draws, in its order
+        return False
+
+    def __getitem__(self, idx, pp=False):
+        if idx >= len(self):
+            raise IndexError(f"Tried to retrieve invalid image. Index {idx} is not less than {len(self)} total image frame slices.")
+        return _transform_pair(self.hr_images[idx], self.lr_images[idx], self.hr_res, self.hr_res // self.lr_scale,
+                               self._draw_rotation(idx, pp), self.transforms, self.n_frames, getattr(self, "compact", False))
+
+    def __repr__(self):
+        return (f"{type(self).__name__} of {len(self.hr_images)} paired images with {len(self)} total frame slices\n"
+                f"high-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}")
+
+    def _get_name(self, idx):
+        return self.names[idx] + ("_0" if self.n_frames is not None else "")
+
+
+def _read_folder(path, files):
+    from PIL import Image
+    stacks = []
+    for f in files:
+        im = Image.open(Path(path, f))
+        frames = []
+        for k in range(getattr(im, "n_frames", 1)):
+            im.seek(k)
+            frames.append(np.asarray(im.convert("L"), dtype=np.uint8))
+        stacks.append(np.stack(frames))
+    if len({st.shape for st in stacks}) != 1:
+        raise ValueError(f'pssr2_amd.PairedImageDataset needs equally sized images in "{path}"')
+    return np.stack(stacks)
+
+
+class PairedImageDataset(PairedArrayDataset):
+    """Two folders of pre-tiled images (anything Pillow opens) holding the high- and low-resolution side of each pair in the same sorted
+    order: reference arguments, errors and warning (pssr/data.py:268-346).  The files of a side must be equally sized; tif stacks
+    sliced into several items per file and sheets are outside this build's scope."""
+
+    def __init__(self, hr_path, lr_path, hr_res=512, lr_scale=4, n_frames=-1, extension="tif", val_split=1, rotation=True,
+                 split_seed=None, transforms=None):
+        self.hr_path = Path(hr_path) if type(hr_path) is str else hr_path
+        self.lr_path = Path(lr_path) if type(lr_path) is str else lr_path
+        for path in (self.hr_path, self.lr_path):
+            if not path or not path.exists():
+                raise FileNotFoundError(f'Path "{path}" does not exist.')
+        if self.hr_path == self.lr_path:
+            warnings.warn("hr_path is equal to lr_path! Consider using ImageDataset instead.", stacklevel=2)
+        found = []
+        for path in (self.hr_path, self.lr_path):
+            files = sorted(f.split(str(path), maxsplit=1)[-1].strip("/") for f in glob.glob(f"{path}/**/*.{extension}", recursive=True))
+            if not files:
+                raise FileNotFoundError(f'No .{extension} files exist in path "{path}".')
+            found.append(files)
+        self.hr_files, self.lr_files = found
+        if len(self.hr_files) != len(self.lr_files):
+            raise FileNotFoundError(f"Mismatch between amounts of high-low-resolution images. Found {len(self.hr_files)} high-resolution "
+                                    f"and {len(self.lr_files)} low-resolution images.")
+        super().__init__(_read_folder(self.hr_path, self.hr_files), _read_folder(self.lr_path, self.lr_files), hr_res, lr_scale, n_frames,
+                         val_split, rotation, split_seed, transforms, [f.split(".")[0] for f in self.lr_files])
+        self.mode = "L"
+
+    def __repr__(self):
+        return (f'PairedImageDataset from paths "{self.hr_path}" and "{self.lr_path}"\n{len(self.hr_files)} paired files with {len(self)} '
+                f"total frame slices\nhigh-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}")
+
+
 class SlidingArrayDataset(Dataset):
     """LR-mode sliding window over in-memory sheets (pssr/data.py:132-266 with ``lr_scale=-1``): tiles are
     row-major, ``stride = hr_res - overlap``, trailing remainders are dropped."""
@@ -337,6 +465,22 @@ class DevicePairGenerator:
         return self(ops.gen_pair_geometry_u8(stacks, rotations, hr_res), tile_offset)
 
 
+def _gather_table(images, indices, rotations):
+    """int64 [n, 3] device rows (= n ``pssr_gather_item``) that point at ``images[i]`` with the given ``False`` / ``[rot, axis]`` draws."""
+    import struct
+    c, h, w = images.shape[1:]
+    base, stride = images.data_ptr(), c * h * w
+    buf = bytearray()
+    for i, rot in zip(indices, rotations):
+        axis = -1
+        if rot:
+            axis = 3 if isinstance(rot[1], (tuple, list)) else int(rot[1])
+        buf += struct.pack("<Qiiii", base + int(i) * stride, h, w, int(bool(rot and rot[0])), axis)
+    if not buf:                        # an empty order (val_split = 0, a rank without validation items): torch.frombuffer rejects b""
+        return torch.zeros(0, 3, dtype=torch.int64, device=images.device)
+    return torch.frombuffer(buf, dtype=torch.int64).view(-1, 3).to(images.device)
+
+
 class DeviceTileDataset(Dataset):
     """``ArrayDataset`` whose uint8 HR stacks live in HBM: same constructor arguments, same attribute protocol
     (``val_idx``, ``extra_hr_files``, ``crop_res``, ``lr_scale``, ``is_lr``, ``hr_res``, ``n_frames``, ``_get_name``) and the same
@@ -394,19 +538,7 @@ class DeviceTileDataset(Dataset):
     def draw_items(self, indices):
         """Gather table (int64 [n, 3] on the device = n ``pssr_gather_item``) for these dataset indices, drawing the training
         rotations exactly as ``__getitem__`` would for the same sequence of indices."""
-        import struct
-        c, h, w = self.images.shape[1:]
-        base, stride = self.images.data_ptr(), c * h * w
-        buf = bytearray()
-        for i in indices:
-            rot = self._draw_rotation(int(i))
-            axis = -1
-            if rot:
-                axis = 3 if isinstance(rot[1], (tuple, list)) else int(rot[1])
-            buf += struct.pack("<Qiiii", base + int(i) * stride, h, w, int(bool(rot and rot[0])), axis)
-        if not buf:                        # an empty order (val_split = 0, a rank without validation items): torch.frombuffer rejects b""
-            return torch.zeros(0, 3, dtype=torch.int64, device=self.images.device)
-        return torch.frombuffer(buf, dtype=torch.int64).view(-1, 3).to(self.images.device)
+        return _gather_table(self.images, indices, [self._draw_rotation(int(i)) for i in indices])
 
     def device_batch(self, items):
         """items: int64 [b, 3] device rows of ``draw_items``.  Returns float32 (hr, lr) on the device, or lr alone in LR mode.  No
@@ -427,3 +559,52 @@ class DeviceTileDataset(Dataset):
             raise IndexError(f"Tried to retrieve invalid image. Index {idx} is not less than {len(self)} total image frame slices.")
         out = self.device_batch(self.draw_items([idx]))
         return out[0] if self.is_lr else (out[0][0], out[1][0])
+
+
+class DevicePairedTileDataset(PairedArrayDataset):
+    """``PairedArrayDataset`` whose two uint8 stacks live in HBM: same arguments, attributes and item values (float32 CHW tensors, here on
+    the device), so the drivers take it like any dataset whose items need no host-to-device copy.  Whole batches come from one host
+    draw (``draw_pair_items``: the reference's rotation draws, index by index) and two launches of the ``_gen_pair`` gather kernel
+    (``device_pair_batch``: one table per side, the same (rot, flip) per item).  These are deliberately not DeviceTileDataset's
+    ``draw_items`` / ``device_batch``: the hipGraph replay of ``train_paired`` (pssr2_amd/fastpath.py) does not cover real pairs."""
+    _keep_tensors = True        # stacks already in HBM stay there
+
+    def __init__(self, hr_images, lr_images, hr_res=512, lr_scale=4, n_frames=-1, val_split=1, rotation=True, split_seed=None,
+                 transforms=None, names=None, device="cuda"):
+        if transforms is not None:
+            raise NotImplementedError("DevicePairedTileDataset applies no host transforms")
+        super().__init__(hr_images, lr_images, hr_res, lr_scale, n_frames, val_split, rotation, split_seed, None, names)
+        self.hr_images = torch.as_tensor(self.hr_images).to(device).contiguous()
+        self.lr_images = torch.as_tensor(self.lr_images).to(device).contiguous()
+        if not self.hr_images.is_cuda:
+            raise RuntimeError("DevicePairedTileDataset keeps its images on an MI355X (HIP) device; there is no CPU fallback")
+        del self.compact            # items are float32 device tensors: the host feed has nothing to compact
+
+    def draw_pair_items(self, indices, pp=False):
+        """(HR table, LR table) for these dataset indices: the training rotations are drawn exactly as ``__getitem__`` would draw them
+        for the same sequence of indices, and each draw is written to both tables."""
+        indices = [int(i) for i in indices]
+        for i in indices:
+            if i >= len(self):
+                raise IndexError(f"Tried to retrieve invalid image. Index {i} is not less than {len(self)} total image frame slices.")
+        rots = [self._draw_rotation(i, pp) for i in indices]
+        return _gather_table(self.hr_images, indices, rots), _gather_table(self.lr_images, indices, rots)
+
+    def device_pair_batch(self, tables, u8=False):
+        """tables: ``draw_pair_items``' result.  float32 (uint8 with ``u8``) (hr [b, C, R, R], lr [b, c, r, r]) on the device, no host
+        synchronisation."""
+        from . import _lib as L, ops
+        out = []
+        for table, images, res, keep in zip(tables, (self.hr_images, self.lr_images), (self.hr_res, self.hr_res // self.lr_scale), (1, 0)):
+            b, c = table.shape[0], images.shape[1]
+            side = torch.empty(b, c, res, res, dtype=torch.uint8, device=images.device)
+            if b:
+                L.check(L.lib().pssr_gen_pair_geometry_u8(L.ptr(table), b, L.ptr(side), c, res, L.stream_ptr()), "pssr_gen_pair_geometry_u8")
+            if self.n_frames is not None and self.n_frames[0] != self.n_frames[1] and not self.n_frames[keep] > c:
+                side = _slice_center(side, self.n_frames[keep]).contiguous()
+            out.append(side if u8 or not b else ops.u8_to_f32(side))
+        return tuple(out)
+
+    def __getitem__(self, idx, pp=False):
+        hr, lr = self.device_pair_batch(self.draw_pair_items([idx], pp))
+        return hr[0], lr[0]

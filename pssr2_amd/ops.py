@@ -794,3 +794,42 @@ def clamp_f32(x, lo, hi, out=None):
         L.check(L.lib().pssr_clamp_f32(L.ptr(x), L.ptr(out), C.c_int64(x.numel()), C.c_float(lo), C.c_float(hi), L.stream_ptr()),
                 "pssr_clamp_f32")
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# noise-profile statistics of approximate_crappifier's objective (csrc/profile.hip)
+PROFILE_BINS = 511
+
+
+def noise_profile(a, b):
+    """Per image (leading dimension) of ``a - b``: (int32 [images, 511] np.histogram(v, np.arange(-256, 256)) counts, float64 [images]
+    sums of every v).  ``b``: uint8 (the reduced HR); ``a``: float32 (a crappified image, unrounded) or uint8 (the real LR)."""
+    if b.dtype != torch.uint8 or a.dtype not in (torch.float32, torch.uint8) or a.shape != b.shape or not (a.is_cuda and b.is_cuda) or a.dim() < 2:
+        raise ValueError("noise_profile needs a float32 or uint8 `a` and a uint8 `b` of the same shape [images, ...] on the device")
+    a, b = a.contiguous(), b.contiguous()
+    images = a.shape[0]
+    per = a.numel() // images
+    lib = L.lib()
+    ws_bytes = lib.pssr_noise_profile_workspace_bytes(images, per)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device) if ws_bytes else None
+    hist = torch.empty(images, PROFILE_BINS, dtype=torch.int32, device=a.device)
+    total = torch.empty(images, dtype=torch.float64, device=a.device)
+    fn, name = (lib.pssr_noise_profile_f32, "pssr_noise_profile_f32") if a.dtype == torch.float32 else (lib.pssr_noise_profile_u8, "pssr_noise_profile_u8")
+    L.check(fn(L.ptr(a), L.ptr(b), L.ptr(hist), L.ptr(total), images, per, L.ptr(ws), ws_bytes, L.stream_ptr()), name)
+    return hist, total
+
+
+def noise_profile_loss(pred_hist, pred_sum, target_hist, target_sum, per_image, width, terms=False):
+    """(float64 [images] losses, float64 [1] mean over images[, float64 [images, 2] histogram and value terms]) of
+    ``mean_k((t_k - p_k)**2) / width**2 + |mean(T) - mean(P)|`` (pssr/train.py:381-386)."""
+    images = pred_hist.shape[0]
+    for h, s in ((pred_hist, pred_sum), (target_hist, target_sum)):
+        if h.dtype != torch.int32 or s.dtype != torch.float64 or tuple(h.shape) != (images, PROFILE_BINS) or s.numel() != images \
+                or not (h.is_cuda and s.is_cuda and h.is_contiguous() and s.is_contiguous()):
+            raise ValueError("noise_profile_loss needs contiguous int32 [images, 511] histograms and float64 [images] sums on the device")
+    loss = torch.empty(images, dtype=torch.float64, device=pred_hist.device)
+    mean = torch.empty(1, dtype=torch.float64, device=pred_hist.device)
+    parts = torch.empty(images, 2, dtype=torch.float64, device=pred_hist.device) if terms else None
+    L.check(L.lib().pssr_noise_profile_loss(L.ptr(pred_hist), L.ptr(pred_sum), L.ptr(target_hist), L.ptr(target_sum), images, per_image, width,
+                                            L.ptr(loss), L.ptr(parts), L.ptr(mean), L.stream_ptr()), "pssr_noise_profile_loss")
+    return (loss, mean, parts) if terms else (loss, mean)

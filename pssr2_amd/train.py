@@ -9,6 +9,7 @@ averaged over ranks, and only rank 0 writes checkpoints / collages.
 from __future__ import annotations
 
 import os
+import random
 
 import torch
 import torch.nn as nn
@@ -372,3 +373,117 @@ def train_crappifier(model: nn.Module, dataset: Dataset, batch_size: int, optim:
                 optim.sync_device_lr()
 
     return train_losses, val_losses
+
+
+def _crappify_unrounded(x, crappifier, seed, tile_offset):
+    """``crappifier.crappify`` on the device for float32 tiles [n, C, h, w], as the objective calls it (pssr/train.py:368): no rounding
+    and no final clip to [0, 255] (kernel flags 0); a ``MultiCrappifier(clip=True)`` clips after each of its stages, as its ``crappify``
+    does.  Tile ``i`` draws from the Philox stream (seed, tile_offset + i)."""
+    from . import ops
+    from .data import DevicePairGenerator
+    spec = crappifier.device_spec()             # NotImplementedError for a subclass without a device path
+    stage = DevicePairGenerator(crappifier=None)._stage
+    if not isinstance(spec, list):
+        return stage(x, spec, seed, tile_offset, 0)
+    flags = ops.CLIP if spec[0][0] == "clip" else 0
+    for i, st in enumerate(spec[1:]):
+        if isinstance(st, list):
+            raise NotImplementedError("nested MultiCrappifier has no MI355X device path")
+        x = stage(x, st, seed + 7919 * i, tile_offset, flags)
+    return x
+
+
+class _Crappifier_Objective:
+    """The noise-profile objective of ``approximate_crappifier`` (pssr/train.py:348-386) on the device.
+
+    Once, at construction: every pair goes to HBM as uint8 (a ``DevicePairedTileDataset`` is gathered in place; any other paired
+    dataset is read item by item), HR is reduced to the LR size by the Pillow-exact kernel, and the histogram and sum of the real
+    profile ``lr - ds_hr`` are taken per pair -- none of this depends on the parameters, while the reference redoes it on every call.
+    Per ``sample(params)``: the reference's ``random.shuffle`` of the indices and its first ``n_samples``; ``crappifier(*params)`` run
+    through its device path (Philox seed ``seed``, tile offset advancing by ``n_samples`` per call); one profile launch over
+    ``lr_hat``; the loss kernels; one float64 comes back.
+
+    Deviations: items are materialised without the training rotation (the statistic is invariant under a joint rot90 / flip of the
+    pair but for the rounding of the reduction); the noise is the device generator's, so values agree with the reference
+    statistically, not bit for bit; the two means are taken in float64 (float32 upstream)."""
+
+    def __init__(self, crappifier, dataset, n_samples, device="cuda", seed=0):
+        from . import ops
+        from .data import DevicePairedTileDataset
+        if torch.device(device).type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("pssr2_amd.approximate_crappifier runs on an MI355X (HIP) device only; there is no CPU fallback")
+        if getattr(dataset, "is_lr", False):
+            raise ValueError("Dataset must be paired with high-low-resolution images.")
+        self.crappifier, self.dataset, self.n_samples, self.seed = crappifier, dataset, n_samples, int(seed)
+        self.calls = 0
+        n = len(dataset)
+        if n == 0 or n_samples <= 0:
+            raise ValueError("approximate_crappifier needs at least one pair")
+        if isinstance(dataset, DevicePairedTileDataset):
+            hr, lr = dataset.device_pair_batch(dataset.draw_pair_items(range(n), pp=True), u8=True)
+            hr, lr = hr.to(device), lr.to(device)
+        else:
+            hr, lr = self._read_items(dataset, device)
+        if hr.shape[1] != lr.shape[1]:
+            raise ValueError(f"the objective compares equal stacks: HR items have {hr.shape[1]} frames, LR items {lr.shape[1]}")
+        self.lr_shape = tuple(lr.shape[1:])
+        self.ds_hr = ops.bilinear_down_u8(hr.contiguous(), lr.shape[-2], lr.shape[-1])          # pssr/train.py:365
+        self.target_hist, self.target_sum = ops.noise_profile(lr.contiguous(), self.ds_hr)       # pssr/train.py:373, 377, 382
+        self.per_image = self.ds_hr[0].numel()
+
+    @staticmethod
+    def _read_items(dataset, device):
+        rotation = getattr(dataset, "rotation", None)
+        if rotation:
+            dataset.rotation = False
+        try:
+            sides = ([], [])
+            for i in range(len(dataset)):
+                for side, item in zip(sides, dataset[i]):
+                    item = torch.as_tensor(item)
+                    if item.dtype != torch.uint8:
+                        u8 = item.to(torch.uint8)
+                        if not torch.equal(u8.to(item.dtype), item):          # NaN, fractions and values outside [0, 255] all fail
+                            raise ValueError(f"item {i} of the dataset holds values that are not integers in [0, 255]; the objective "
+                                             "works on uint8 images")
+                        item = u8
+                    side.append(item.cpu())
+        finally:
+            if rotation:
+                dataset.rotation = rotation
+        return torch.stack(sides[0]).to(device), torch.stack(sides[1]).to(device)
+
+    def sample(self, params):
+        from . import ops
+        sample_idx = list(range(len(self.dataset)))
+        random.shuffle(sample_idx)
+        idx = torch.tensor(sample_idx[:self.n_samples], device=self.ds_hr.device)
+        ds_hr = self.ds_hr.index_select(0, idx)
+        lr_hat = _crappify_unrounded(ops.u8_to_f32(ds_hr), self.crappifier(*params), self.seed, self.calls * self.n_samples)
+        self.calls += 1
+        pred_hist, pred_sum = ops.noise_profile(lr_hat, ds_hr)
+        _, mean = ops.noise_profile_loss(pred_hist, pred_sum, self.target_hist.index_select(0, idx), self.target_sum.index_select(0, idx),
+                                         self.per_image, self.lr_shape[-1])
+        return float(mean.item())
+
+
+def approximate_crappifier(crappifier, space, dataset: Dataset, max_images=None, opt_kwargs=None, *, device: str = "cuda", seed: int = 0,
+                           minimizer=None):
+    r"""Approximates :class:`Crappifier` parameters from ground truth paired images by Bayesian optimisation of a noise-profile
+    objective (pssr/train.py:324-346): same arguments and return value (the optimiser's result: ``x``, ``fun``, ``x_iters``,
+    ``func_vals``).  ``crappifier`` is a class or any callable that builds a :class:`Crappifier` from ``*params``; it needs a device
+    path (``device_spec``), and the objective runs on the MI355X (:class:`_Crappifier_Objective`).
+
+    Keyword-only additions: ``device``; ``seed`` of the device noise generator; ``minimizer`` (a callable with ``gp_minimize``'s
+    interface).  Without it ``skopt.gp_minimize`` is used when scikit-optimize is installed, else ``pssr2_amd.bayes.gp_minimize``.
+    """
+    space = [space] if type(space) is not list else space
+    n_samples = len(dataset) if max_images is None else min(max_images, len(dataset))
+    opt_kwargs = {} if opt_kwargs is None else opt_kwargs
+    if minimizer is None:
+        try:
+            from skopt import gp_minimize as minimizer
+        except ImportError:
+            from .bayes import gp_minimize as minimizer
+    objective = _Crappifier_Objective(crappifier, dataset, n_samples, device=device, seed=seed).sample
+    return minimizer(objective, space, **opt_kwargs)
