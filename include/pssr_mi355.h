@@ -339,7 +339,11 @@ int pssr_ssim_level_fwd_adj(const float* x, const float* y, float in_div, int pl
 /* `sums` / `l1_sum` of pssr_ssim_level_fwd_adj are 2 x `stripes` copies `stripe_stride` doubles apart (a workgroup adds the two exact
  * pieces of each of its sums -- see PSSR_STAT_ROWS -- to copy s and copy stripes + s:
  * a 512^2 x 32 level ends with 8192 workgroups); pssr_msssim_weights_striped folds them in a fixed order into `folded`
- * ([levels * planes * 2 + 1] doubles) before doing what pssr_msssim_weights does. */
+ * ([levels * planes * 2 + 1] doubles) before doing what pssr_msssim_weights does.  It folds for every stripes >= 1: with one stripe
+ * the two pieces of a sum still lie stripe_stride apart (pssr_msssim_weights, which does not fold, is for sums that
+ * pssr_ssim_level_fwd wrote, or pssr_ssim_level_fwd_adj with stripes = 1 and stripe_stride = 0).
+ * The L1 term's border mass S(q) is summed from the taps as they are indexed, which is the zero-padded window mass only for a
+ * symmetric window (win[t] == win[k-1-t]); the SSIM maps and their gradient take any window (a correlation, as F.conv2d). */
 int pssr_msssim_weights_striped(const double* sums, int stripes, int64_t stripe_stride, double* folded, int levels, int planes,
                                 const double* nvalid, const float* level_weights, int ms, float mix, const double* l1_sum,
                                 double l1_numel, const float* grad_out, float* loss_out, float* wts, float* l1_coef,

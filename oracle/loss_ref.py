@@ -53,18 +53,18 @@ def _ssim_maps(x, y, g, data_range, K=(0.01, 0.03)):
     return ssim_map.flatten(2).mean(-1), cs_map.flatten(2).mean(-1)   # (N, C) each
 
 
-def ssim(x, y, data_range=255.0, win_size=11, win_sigma=1.5, size_average=True):
-    s, _ = _ssim_maps(x, y, gauss_1d(win_size, win_sigma), data_range)
+def ssim(x, y, data_range=255.0, win_size=11, win_sigma=1.5, size_average=True, K=(0.01, 0.03)):
+    s, _ = _ssim_maps(x, y, gauss_1d(win_size, win_sigma), data_range, K)
     return s.mean() if size_average else s.mean(1)
 
 
-def ms_ssim(x, y, data_range=255.0, win_size=11, win_sigma=1.5, size_average=True, weights=MS_WEIGHTS):
+def ms_ssim(x, y, data_range=255.0, win_size=11, win_sigma=1.5, size_average=True, weights=MS_WEIGHTS, K=(0.01, 0.03)):
     assert min(x.shape[-2:]) > (win_size - 1) * 2 ** 4, "image too small for 5-level MS-SSIM"
     g = gauss_1d(win_size, win_sigma)
     w = torch.tensor(weights, dtype=x.dtype)
     vals = []
     for lvl in range(len(weights)):
-        s, cs = _ssim_maps(x, y, g, data_range)
+        s, cs = _ssim_maps(x, y, g, data_range, K)
         if lvl < len(weights) - 1:
             vals.append(torch.relu(cs))
             pad = [d % 2 for d in x.shape[2:]]
@@ -84,9 +84,10 @@ def gaussian_l1(x, y, win_size=11, win_sigma=1.5):
     return F.conv2d((x - y).abs(), win, groups=c, padding=(win_size - 1) // 2).mean()
 
 
-def ssim_loss(x, y, mix=0.8, win_size=11, win_sigma=1.5, ms=True):
-    """SSIMLoss.forward (pssr/util.py:45-52) with data_range=1 (pssr/util.py:30)."""
-    s = ms_ssim(x, y, 1.0, win_size, win_sigma) if ms else ssim(x, y, 1.0, win_size, win_sigma)
+def ssim_loss(x, y, mix=0.8, win_size=11, win_sigma=1.5, ms=True, weights=MS_WEIGHTS, K=(0.01, 0.03)):
+    """SSIMLoss.forward (pssr/util.py:45-52) with data_range=1 (pssr/util.py:30); ``weights`` / ``K`` are the pytorch_msssim options
+    that SSIMLoss passes through as ``kwargs``."""
+    s = ms_ssim(x, y, 1.0, win_size, win_sigma, weights=weights, K=K) if ms else ssim(x, y, 1.0, win_size, win_sigma, K=K)
     loss = 1 - s
     if mix < 1:
         loss = mix * loss + (1 - mix) * gaussian_l1(x, y, win_size, win_sigma)

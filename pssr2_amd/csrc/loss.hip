@@ -130,11 +130,12 @@ __global__ void avgpool_kernel(const float* __restrict__ in0, float* __restrict_
 __global__ void weights_kernel(const double* sums_in, int levels, int planes, const double* nvalid, const float* lvl_w, int ms,
                                float mix, const double* l1_sum_in, double l1_numel, const float* grad_out,
                                float* loss_out, float* wts /*[levels][planes]*/, float* l1_coef, int stripes, long stripe_stride,
-                               double* folded /* [levels * planes * 2 + 1] scratch when stripes > 1 */) {
-    // striped sums (ssim_fwd_adj_k): fold the copies first, in a fixed order
+                               double* folded /* [levels * planes * 2 + 1] scratch of the striped entry, else null */) {
+    // striped sums (ssim_fwd_adj_k): fold the copies first, in a fixed order -- with one stripe too: that kernel writes every sum as
+    // two pieces whatever the stripe count
     const double* sums = sums_in;
     const double* l1_sum = l1_sum_in;
-    if (stripes > 1) {
+    if (folded) {
         // (fixed order; the loads of a value are independent and issued together: the serial loop cost 24 us on the step's chain)
         const int nvals = levels * planes * 2;
         for (int i = threadIdx.x; i <= nvals; i += 256) {
