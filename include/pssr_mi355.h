@@ -429,6 +429,16 @@ int pssr_gaussian_blur_tiles(const float* in, float* tmp, float* out, int tiles,
  * order; out is uint8 [n_items][c][res][res]. */
 typedef struct pssr_gather_item { const uint8_t* src; int sh, sw, rot, flip_axis; } pssr_gather_item;
 int pssr_gen_pair_geometry_u8(const pssr_gather_item* items_dev, int n_items, uint8_t* out, int c, int res, pssr_stream_t stream);
+/* Sliding windows of image sheets resident in HBM (pssr/data.py:629-660 `_sliding_window` / `_slice_image`, then the rot90 / flip of
+ * `_gen_pair`): out[i][f] = sheet[frame0 + f][y0 : y0 + res, x0 : x0 + res] of sheets_dev[items_dev[i].sheet], np.rot90 in the
+ * image plane when rot != 0, np.flip along flip_axis (as pssr_gather_item).  Sheets are uint8 [frames][h][w], contiguous, of any
+ * size each; both tables live on the device; out is uint8 [n_items][c][res][res].  Windows are always whole: an item whose sheet
+ * index, frame range [frame0, frame0 + c) or window leaves its sheet is written as zeros and reads nothing.  n_items <= 65535.
+ * 16-byte stores when res % 16 == 0 and out is 16-byte aligned (sheet rows may be misaligned); byte accesses otherwise. */
+typedef struct pssr_sheet_desc { const uint8_t* base; int frames, h, w, reserved; } pssr_sheet_desc;      /* 24 bytes */
+typedef struct pssr_window_item { int sheet, frame0, y0, x0, rot, flip_axis; } pssr_window_item;           /* 24 bytes */
+int pssr_gather_windows_u8(const pssr_sheet_desc* sheets_dev, int n_sheets, const pssr_window_item* items_dev, int n_items,
+                           uint8_t* out, int c, int res, pssr_stream_t stream);
 
 
 /* ---------------------------------------------------------------------------------------------

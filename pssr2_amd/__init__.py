@@ -30,6 +30,10 @@ def __getattr__(name):
     if name in ("PairedArrayDataset", "PairedImageDataset", "DevicePairedTileDataset"):
         from . import data
         return getattr(data, name)
+    if name in ("SlidingSheetDataset", "SlidingDataset", "PairedSlidingArrayDataset", "PairedSlidingDataset", "DeviceSlidingDataset",
+                "DevicePairedSlidingDataset"):
+        from . import data
+        return getattr(data, name)
     if name in ("GradHist",):
         from .models import GradHist
         return GradHist

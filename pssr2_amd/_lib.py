@@ -59,6 +59,16 @@ class GatherItem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("sh", C.c_int), ("sw", C.c_int), ("rot", C.c_int), ("flip_axis", C.c_int)]
 
 
+class SheetDesc(C.Structure):
+    """struct pssr_sheet_desc (include/pssr_mi355.h)"""
+    _fields_ = [("base", C.c_void_p), ("frames", C.c_int), ("h", C.c_int), ("w", C.c_int), ("reserved", C.c_int)]
+
+
+class WindowItem(C.Structure):
+    """struct pssr_window_item (include/pssr_mi355.h)"""
+    _fields_ = [("sheet", C.c_int), ("frame0", C.c_int), ("y0", C.c_int), ("x0", C.c_int), ("rot", C.c_int), ("flip_axis", C.c_int)]
+
+
 COPY_BATCH_MAX = 16
 
 
@@ -108,6 +118,7 @@ def lib():
             getattr(_lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_i64, c_void_p]
         _lib.pssr_noise_profile_loss.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p,
                                                  c_void_p]
+        _lib.pssr_gather_windows_u8.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]
     return _lib
 
 

@@ -10,6 +10,10 @@ Two ways to produce (HR, LR) training pairs from uint8 HR tiles:
   ~1 ms/tile host stage that would otherwise cap multi-GPU training.
 
 File decoding (tif/czi) is out of scope: ``ImageDataset`` reads what Pillow reads.
+
+Image sheets (the reference's ``SlidingDataset`` / ``PairedSlidingDataset``) follow the same three steps: ``SlidingSheetDataset`` /
+``PairedSlidingArrayDataset`` over sheets in memory, the file classes on top of them (Pillow, multi-page tifs included), and
+``DeviceSlidingDataset`` / ``DevicePairedSlidingDataset`` with the sheets in HBM and the windows cut by ``pssr_gather_windows_u8``.
 """
 from __future__ import annotations
 
@@ -396,6 +400,257 @@ class SlidingArrayDataset(Dataset):
         return f"{self.names[s]}_{t}_0"
 
 
+# --------------------------------------------------------------------------------------- sheets
+def _get_image_idx(idx, slices, tiles=None):
+    """(sheet, index inside the sheet) of a dataset index (pssr/data.py:697-706)."""
+    tiles = [1] * len(slices) if tiles is None else tiles
+    for image_idx, (s, t) in enumerate(zip(slices, tiles)):
+        if idx < s * t:
+            return image_idx, idx
+        idx -= s * t
+    return None
+
+
+def _window_origin(sheet, size, stride, n_frames, n_slices, idx, slide):
+    """(frame0, y0, x0) of the window ``_sliding_window`` cuts for the in-sheet index ``idx`` (pssr/data.py:629-660): tiles row-major,
+    ``tile = idx // n_slices``; frame slice ``idx % n_slices``, times ``n_frames`` unless the stack is slid over."""
+    _, ty = _n_tiles(sheet, size, stride)
+    tile = idx // n_slices
+    frame0 = 0 if n_frames is None else idx % n_slices * (1 if slide else n_frames)
+    return frame0, tile // ty * stride, tile % ty * stride
+
+
+def _sliding_window(sheet, size, stride, n_frames, n_slices, idx, slide):
+    frame0, y0, x0 = _window_origin(sheet, size, stride, n_frames, n_slices, idx, slide)
+    window = sheet[..., y0:y0 + size, x0:x0 + size]
+    return window if n_frames is None else window[frame0:frame0 + n_frames]
+
+
+def _sheet_list(sheets, who, keep_tensors=False):
+    out = []
+    for s in sheets:
+        if not torch.is_tensor(s):
+            s = np.asarray(s)
+        elif not keep_tensors:
+            s = s.cpu().numpy()
+        if s.ndim == 2:
+            s = s[None]
+        if s.ndim != 3 or str(s.dtype).split(".")[-1] != "uint8":
+            raise ValueError(f"{who} expects uint8 sheets [F, H, W]")
+        out.append(s)
+    return out
+
+
+def _tiles_slices(sheets, size, stride, n_frames, slide):
+    """Windows per sheet and frame slices per window (pssr/data.py:205-210)."""
+    tiles, slices = [], []
+    for s in sheets:
+        tx, ty = _n_tiles(s, size, stride)
+        tiles.append(tx * ty)
+        slices.append(1 if n_frames is None else ((s.shape[0] - max(n_frames) + 1) if slide else (s.shape[0] // max(n_frames))))
+    return tiles, slices
+
+
+def _in_val(dataset, idx):
+    # ``idx in dataset.val_idx`` as upstream, with the list hashed once per assignment / length change (see DeviceTileDataset._draw_rotation)
+    key = (id(dataset.val_idx), len(dataset.val_idx))
+    if key != getattr(dataset, "_val_key", None):
+        dataset._val_set, dataset._val_key = set(dataset.val_idx), key
+    return idx in dataset._val_set
+
+
+def _check_stride(hr_res, overlap):
+    overlap = 0 if overlap is None else overlap
+    if not hr_res > overlap:
+        raise ValueError(f"hr_res must be greater than overlap. Given values are {hr_res} and {overlap} respectively.")
+    return hr_res - overlap
+
+
+class SlidingSheetDataset(Dataset):
+    """Training dataset over in-memory image sheets (uint8 [F, H, W] each, 2-D accepted, of any sizes): the reference's
+    ``SlidingDataset`` (pssr/data.py:132-266) without the files.  Same arithmetic -- ``stride = hr_res - overlap``, whole windows only,
+    row-major; per sheet ``tiles`` windows times ``slices`` frame slices (``frames - max(n_frames) + 1`` with ``slide``, else
+    ``frames // max(n_frames)``); the validation split is taken over windows (``_get_val_idx(slices, split, seed, tiles)``); item
+    ``idx`` of a sheet is window ``idx // slices``, frame slice ``idx % slices`` -- the same attribute protocol, names
+    (``{name}_{window}_{slice}``), ``__getitem__(idx, pp=False)`` and LR mode (``lr_scale=-1``, ``hr_res`` = LR resolution)."""
+
+    def __init__(self, sheets, hr_res=512, lr_scale=4, crappifier=Poisson(), overlap=128, n_frames=-1, slide=False, val_split=0.1,
+                 rotation=True, split_seed=0, transforms=None, names=None):
+        self.sheets = _sheet_list(sheets, type(self).__name__, getattr(self, "_keep_tensors", False))
+        self.stride = _check_stride(hr_res, overlap)
+        lr_scale = None if lr_scale == -1 else lr_scale
+        self.n_frames, self.slide = _get_n_frames(n_frames), slide
+        self.tiles, self.slices = _tiles_slices(self.sheets, hr_res, self.stride, self.n_frames, slide)
+        self.val_idx = _get_val_idx(self.slices, val_split, split_seed, self.tiles)
+        self.crop_res = hr_res
+        self.is_lr = lr_scale is None
+        if self.is_lr:
+            print("LR mode is enabled, dataset will load only unmodified low-resolution images.")
+            if val_split < 1:
+                warnings.warn("val_split is less than 1, not all low-resolution images will be used in prediciton.", stacklevel=2)
+        self.hr_res, self.lr_scale = hr_res, lr_scale if lr_scale is not None else 1
+        self.crappifier, self.rotation, self.transforms = crappifier, rotation, transforms
+        self.extra_hr_files = None
+        self.compact = False        # see ArrayDataset.compact
+        self.names = list(names) if names is not None else [f"sheet{i}" for i in range(len(self.sheets))]
+
+    def __len__(self):
+        return sum(t * s for t, s in zip(self.tiles, self.slices))
+
+    def _check_idx(self, idx):
+        if idx >= len(self):
+            raise IndexError(f"Tried to retrieve invalid image. Index {idx} is not less than {len(self)} total image frame slices.")
+
+    def _draw_rotation(self, idx, pp=False):
+        if self.rotation and not (_in_val(self, idx) or pp):
+            return [bool(random.getrandbits(1)), random.choice((1, 2, (1, 2)))]      # the reference's draws, in its order
+        return False
+
+    def _window(self, idx):
+        """Host window [frames, hr_res, hr_res] of a dataset index, ``max(n_frames)`` frames deep."""
+        image_idx, local = _get_image_idx(idx, self.slices, self.tiles)
+        return _sliding_window(self.sheets[image_idx], self.hr_res, self.stride, max(self.n_frames) if self.n_frames is not None else None,
+                               self.slices[image_idx], local, self.slide)
+
+    def __getitem__(self, idx, pp=False):
+        self._check_idx(idx)
+        hr, rot, compact = self._window(idx), self._draw_rotation(idx, pp), getattr(self, "compact", False)
+        if self.is_lr:
+            return _ready_lr(hr, self.hr_res, self.transforms, compact)
+        return _gen_pair(hr, self.hr_res, self.lr_scale, rot, self.crappifier, self.transforms, self.n_frames, compact)
+
+    def _res_line(self):
+        return f"low-res: {self.hr_res}" if self.is_lr else f"high-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}"
+
+    def __repr__(self):
+        return f"{type(self).__name__} of {len(self.sheets)} sheets with {len(self)} total frame slices\n{self._res_line()}"
+
+    def _get_name(self, idx):
+        image_idx, local = _get_image_idx(idx, self.slices, self.tiles)
+        return f"{self.names[image_idx]}_{local // self.slices[image_idx]}_{local % self.slices[image_idx]}"
+
+
+def _sheet_files(path, extension):
+    path = Path(path) if type(path) is str else path
+    if not path or not path.exists():
+        raise FileNotFoundError(f'Path "{path}" does not exist.')
+    if extension.lower() == "czi":
+        raise NotImplementedError("czi sheets are not supported by pssr2_amd (czifile is not a dependency): export them to tif")
+    files = sorted(f.split(str(path), maxsplit=1)[-1].strip("/") for f in glob.glob(f"{path}/**/*.{extension}", recursive=True))
+    if not files:
+        raise FileNotFoundError(f'No .{extension} files exist in path "{path}".')
+    return path, files
+
+
+def _read_sheets(path, files):
+    """Every file as a uint8 stack [F, H, W] through Pillow (multi-page tifs: one frame per page), sizes free."""
+    from PIL import Image
+    sheets = []
+    for f in files:
+        with Image.open(Path(path, f)) as im:
+            frames = []
+            for k in range(getattr(im, "n_frames", 1)):
+                im.seek(k)
+                frames.append(np.asarray(im.convert("L"), dtype=np.uint8))
+        sheets.append(np.stack(frames))
+    return sheets
+
+
+class SlidingDataset(SlidingSheetDataset):
+    """Folder of image sheets: reference arguments, errors and warning (pssr/data.py:132-266).  Files are read through Pillow
+    (multi-page tifs included).  ``preload`` is accepted for compatibility: the sheets are held in host memory either way.  czi files
+    (``extension="czi"``, with them ``stack``) and ``extra_path`` raise ``NotImplementedError``."""
+
+    def __init__(self, path, hr_res=512, lr_scale=4, crappifier=Poisson(), overlap=128, n_frames=-1, slide=False, stack="TZ",
+                 extension="tif", preload=True, val_split=0.1, rotation=True, split_seed=0, extra_path=None, extra_scale=1,
+                 transforms=None):
+        self.path, self.hr_files = _sheet_files(path, extension)
+        if extra_path is not None:
+            raise NotImplementedError("extra_path is not supported by pssr2_amd.SlidingDataset")
+        self.stack, self.mode, self.preload, self.extra_path, self.extra_scale = stack.upper(), "L", preload, None, extra_scale
+        _check_stride(hr_res, overlap)          # before any file is read, as upstream
+        super().__init__(_read_sheets(self.path, self.hr_files), hr_res, lr_scale, crappifier, overlap, n_frames, slide, val_split, rotation,
+                         split_seed, transforms, [f.split(".")[0] for f in self.hr_files])
+
+    def __repr__(self):
+        return f'SlidingDataset from path "{self.path}"\n{len(self.hr_files)} files with {len(self)} total frame slices\n{self._res_line()}'
+
+
+class PairedSlidingArrayDataset(Dataset):
+    """Real (HR, LR) sheet pairs in memory (uint8 [F, H, W] / [f, h, w] each): the reference's ``PairedSlidingDataset``
+    (pssr/data.py:348-444) without the files -- its defaults (``val_split=1``, ``split_seed=None``), attribute protocol and item geometry
+    (``_transform_pair``), for ``train_crappifier``, ``approximate_crappifier`` and ``test_metrics``.  Windows, slices and the split are
+    counted on the HR sheets.  As upstream, the LR side runs its own sliding window with ``hr_res // lr_scale`` and
+    ``stride // lr_scale`` and takes its windows-per-row from the LR sheet, not from the HR sheet; and with ``n_frames=[lr, hr]`` each
+    side takes its own number of frames from the slice's first frame on."""
+
+    def __init__(self, hr_sheets, lr_sheets, hr_res=512, lr_scale=4, overlap=128, n_frames=-1, slide=False, val_split=1, rotation=True,
+                 split_seed=None, transforms=None, names=None):
+        keep = getattr(self, "_keep_tensors", False)
+        self.hr_sheets, self.lr_sheets = _sheet_list(hr_sheets, type(self).__name__, keep), _sheet_list(lr_sheets, type(self).__name__, keep)
+        if len(self.hr_sheets) != len(self.lr_sheets):
+            raise ValueError(f"Mismatch between amounts of high-low-resolution images. Found {len(self.hr_sheets)} high-resolution and "
+                             f"{len(self.lr_sheets)} low-resolution images.")
+        self.stride = _check_stride(hr_res, overlap)
+        self.n_frames, self.slide = _get_n_frames(n_frames), slide
+        self.tiles, self.slices = _tiles_slices(self.hr_sheets, hr_res, self.stride, self.n_frames, slide)
+        self.val_idx = _get_val_idx(self.slices, val_split, split_seed, self.tiles)
+        self.is_lr, self.crop_res, self.extra_hr_files = False, hr_res, None
+        self.hr_res, self.lr_scale, self.rotation, self.transforms = hr_res, lr_scale, rotation, transforms
+        self.compact = False        # see ArrayDataset.compact
+        self.names = list(names) if names is not None else [f"sheet{i}" for i in range(len(self.hr_sheets))]
+
+    __len__ = SlidingSheetDataset.__len__
+    _check_idx = SlidingSheetDataset._check_idx
+    _draw_rotation = SlidingSheetDataset._draw_rotation
+    _get_name = SlidingSheetDataset._get_name
+
+    def _side_args(self, idx):
+        """Per side (HR, LR): (sheet, size, stride, frames, slices of the sheet, in-sheet index, slide) as ``_sliding_window`` takes them."""
+        image_idx, local = _get_image_idx(idx, self.slices, self.tiles)
+        nf = self.n_frames
+        return ((self.hr_sheets[image_idx], self.hr_res, self.stride, nf[1] if nf is not None else None, self.slices[image_idx], local, self.slide),
+                (self.lr_sheets[image_idx], self.hr_res // self.lr_scale, self.stride // self.lr_scale, nf[0] if nf is not None else None,
+                 self.slices[image_idx], local, self.slide))
+
+    def __getitem__(self, idx, pp=False):
+        self._check_idx(idx)
+        hr_args, lr_args = self._side_args(idx)
+        return _transform_pair(_sliding_window(*hr_args), _sliding_window(*lr_args), self.hr_res, self.hr_res // self.lr_scale,
+                               self._draw_rotation(idx, pp), self.transforms, self.n_frames, getattr(self, "compact", False))
+
+    def __repr__(self):
+        return (f"{type(self).__name__} of {len(self.hr_sheets)} paired sheets with {len(self)} total frame slices\n"
+                f"high-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}")
+
+
+class PairedSlidingDataset(PairedSlidingArrayDataset):
+    """Two folders of image sheets holding the high- and low-resolution side of each pair in the same sorted order: reference
+    arguments, errors and warning (pssr/data.py:348-444); items are named after the LR files.  Files as in :class:`SlidingDataset`
+    (Pillow; ``preload`` accepted, sheets held in host memory either way; czi raises ``NotImplementedError``)."""
+
+    def __init__(self, hr_path, lr_path, hr_res=512, lr_scale=4, overlap=128, n_frames=-1, slide=False, stack="TZ", extension="tif",
+                 preload=True, val_split=1, rotation=True, split_seed=None, transforms=None):
+        for path in (hr_path, lr_path):
+            path = Path(path) if type(path) is str else path
+            if not path or not path.exists():
+                raise FileNotFoundError(f'Path "{path}" does not exist.')
+        if (Path(hr_path) if type(hr_path) is str else hr_path) == (Path(lr_path) if type(lr_path) is str else lr_path):
+            warnings.warn("hr_path is equal to lr_path! Consider using SlidingDataset instead.", stacklevel=2)
+        (self.hr_path, self.hr_files), (self.lr_path, self.lr_files) = _sheet_files(hr_path, extension), _sheet_files(lr_path, extension)
+        if len(self.hr_files) != len(self.lr_files):
+            raise FileNotFoundError(f"Mismatch between amounts of high-low-resolution images. Found {len(self.hr_files)} high-resolution "
+                                    f"and {len(self.lr_files)} low-resolution images.")
+        self.stack, self.mode, self.preload = stack.upper(), "L", preload
+        _check_stride(hr_res, overlap)
+        super().__init__(_read_sheets(self.hr_path, self.hr_files), _read_sheets(self.lr_path, self.lr_files), hr_res, lr_scale, overlap,
+                         n_frames, slide, val_split, rotation, split_seed, transforms, [f.split(".")[0] for f in self.lr_files])
+
+    def __repr__(self):
+        return (f'PairedSlidingDataset from paths "{self.hr_path}" and "{self.lr_path}"\n{len(self.hr_files)} paired files with {len(self)} '
+                f"total frame slices\nhigh-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}")
+
+
 def synthetic_em_tile(index, res=512, channels=1):
     """Seeded synthetic EM-like uint8 tile: band-limited noise + white noise."""
     rng = np.random.default_rng(1234 + index)
@@ -603,6 +858,162 @@ class DevicePairedTileDataset(PairedArrayDataset):
             if self.n_frames is not None and self.n_frames[0] != self.n_frames[1] and not self.n_frames[keep] > c:
                 side = _slice_center(side, self.n_frames[keep]).contiguous()
             out.append(side if u8 or not b else ops.u8_to_f32(side))
+        return tuple(out)
+
+    def __getitem__(self, idx, pp=False):
+        hr, lr = self.device_pair_batch(self.draw_pair_items([idx], pp))
+        return hr[0], lr[0]
+
+
+def _window_rows(entries):
+    """int64 [n, 3] rows (= n ``pssr_window_item``) from (sheet, frame0, y0, x0, rotation draw) entries; host tensor."""
+    import struct
+    buf = bytearray()
+    for sheet, frame0, y0, x0, rot in entries:
+        axis = -1
+        if rot:
+            axis = 3 if isinstance(rot[1], (tuple, list)) else int(rot[1])
+        buf += struct.pack("<iiiiii", sheet, frame0, y0, x0, int(bool(rot and rot[0])), axis)
+    if not buf:                        # an empty order: torch.frombuffer rejects b""
+        return torch.zeros(0, 3, dtype=torch.int64)
+    return torch.frombuffer(buf, dtype=torch.int64).view(-1, 3)
+
+
+class _SheetBank:
+    """uint8 sheets [F, H, W] in HBM and their device table of ``pssr_sheet_desc`` {base, frames, h, w, reserved}."""
+
+    def __init__(self, sheets, device, who):
+        import struct
+        self.sheets = [torch.as_tensor(s).to(device).contiguous() for s in sheets]
+        if not self.sheets or not all(s.is_cuda for s in self.sheets):
+            raise RuntimeError(f"{who} keeps its sheets on an MI355X (HIP) device; there is no CPU fallback")
+        self.device = self.sheets[0].device
+        buf = bytearray()
+        for s in self.sheets:
+            buf += struct.pack("<Qiiii", s.data_ptr(), *s.shape, 0)
+        self.table = torch.frombuffer(buf, dtype=torch.int64).view(-1, 3).to(self.device)
+
+    def check(self, sheet, frame0, y0, x0, c, res):
+        """The host's half of the bounds check (the kernel zero-fills what fails its own): no launch with a window outside its sheet."""
+        f, h, w = self.sheets[sheet].shape
+        if not (0 <= frame0 and frame0 + c <= f and 0 <= y0 and y0 + res <= h and 0 <= x0 and x0 + res <= w):
+            raise ValueError(f"window (frames {frame0}:{frame0 + c}, rows {y0}:{y0 + res}, columns {x0}:{x0 + res}) leaves sheet {sheet} "
+                             f"of shape {(f, h, w)}")
+
+    def gather(self, items, c, res):
+        from . import ops
+        return ops.gather_windows_u8(self.table, len(self.sheets), items, c, res)
+
+
+def _uniform_frames(sheets, who):
+    frames = {s.shape[0] for s in sheets}
+    if len(frames) != 1:
+        raise ValueError(f"{who}: n_frames=-1 needs sheets with the same number of frames (a batch has one depth); found {sorted(frames)}")
+    return frames.pop()
+
+
+class DeviceSlidingDataset(SlidingSheetDataset):
+    """``SlidingSheetDataset`` whose sheets live in HBM: same arguments, attributes and item values (float32 CHW tensors, here on the
+    device).  Like ``DeviceTileDataset`` it makes whole batches without touching the host -- ``draw_items`` (the reference's rotation
+    draws, index by index, and each window's origin: one ``pssr_window_item`` per index) and ``device_batch`` (one window gather out of
+    the sheets, then the Pillow-exact reduction and the crappifier on device Philox streams) -- so ``train_paired`` replays a whole
+    training step over sheets as one hipGraph (pssr2_amd/fastpath.py).  With ``n_frames=-1`` every sheet must have the same number of
+    frames (a batch has one depth); host transforms are not applied."""
+    _keep_tensors = True        # sheets already in HBM stay there
+
+    def __init__(self, sheets, hr_res=512, lr_scale=4, crappifier=Poisson(), overlap=128, n_frames=-1, slide=False, val_split=0.1,
+                 rotation=True, split_seed=0, transforms=None, names=None, device="cuda", seed=0):
+        if transforms is not None:
+            raise NotImplementedError("DeviceSlidingDataset applies no host transforms")
+        super().__init__(sheets, hr_res, lr_scale, crappifier, overlap, n_frames, slide, val_split, rotation, split_seed, None, names)
+        self.depth = max(self.n_frames) if self.n_frames is not None else _uniform_frames(self.sheets, type(self).__name__)
+        self.bank = _SheetBank(self.sheets, device, type(self).__name__)
+        self.sheets = self.bank.sheets
+        del self.compact            # items are float32 device tensors: the host feed has nothing to compact
+        self.tile_counter = torch.zeros(1, dtype=torch.int64, device=self.bank.device)
+        self.gen = DevicePairGenerator(self.lr_scale, crappifier, seed=seed, tile_counter=self.tile_counter)
+        self._item_bytes = 24             # struct pssr_window_item {sheet, frame0, y0, x0, rot, flip_axis}
+
+    def draw_items(self, indices, pp=False):
+        """Window table (int64 [n, 3] on the device = n ``pssr_window_item``) for these dataset indices, drawing the training rotations
+        exactly as ``__getitem__`` would for the same sequence of indices.  Every window is checked against its sheet here."""
+        entries = []
+        for idx in indices:
+            idx = int(idx)
+            self._check_idx(idx)
+            image_idx, local = _get_image_idx(idx, self.slices, self.tiles)
+            origin = _window_origin(self.sheets[image_idx], self.hr_res, self.stride, None if self.n_frames is None else self.depth,
+                                    self.slices[image_idx], local, self.slide)
+            self.bank.check(image_idx, *origin, self.depth, self.hr_res)
+            entries.append((image_idx, *origin, self._draw_rotation(idx, pp)))
+        return _window_rows(entries).to(self.bank.device)
+
+    def device_batch(self, items):
+        """items: int64 [b, 3] device rows of ``draw_items``.  Returns float32 (hr, lr) on the device, or lr alone in LR mode.  No host
+        synchronisation, no host-side data: capturable in a hipGraph (the Philox tile counter advances on the device)."""
+        from . import ops
+        out = self.bank.gather(items, self.depth, self.hr_res)
+        if self.is_lr:
+            return ops.u8_to_f32(out)
+        hr, lr = self.gen(out)
+        ops.counter_add(self.tile_counter, items.shape[0])
+        nf = self.n_frames
+        if nf is not None and nf[0] != nf[1]:           # centre frames of each side, as _gen_pair
+            if not nf[1] > hr.shape[-3]:
+                hr = _slice_center(hr, nf[1]).contiguous()
+            if not nf[0] > lr.shape[-3]:
+                lr = _slice_center(lr, nf[0]).contiguous()
+        return hr, lr
+
+    def __getitem__(self, idx, pp=False):
+        out = self.device_batch(self.draw_items([idx], pp))
+        return out[0] if self.is_lr else (out[0][0], out[1][0])
+
+
+class DevicePairedSlidingDataset(PairedSlidingArrayDataset):
+    """``PairedSlidingArrayDataset`` whose sheets live in HBM: same arguments, attributes and item values (float32 CHW tensors, here on
+    the device).  Whole batches come from one host draw (``draw_pair_items``) and two window gathers (``device_pair_batch``: one sheet
+    table and one item table per side, the same (rot, flip) per item), as ``DevicePairedTileDataset`` does for pre-cut pairs."""
+    _keep_tensors = True
+
+    def __init__(self, hr_sheets, lr_sheets, hr_res=512, lr_scale=4, overlap=128, n_frames=-1, slide=False, val_split=1, rotation=True,
+                 split_seed=None, transforms=None, names=None, device="cuda"):
+        if transforms is not None:
+            raise NotImplementedError("DevicePairedSlidingDataset applies no host transforms")
+        super().__init__(hr_sheets, lr_sheets, hr_res, lr_scale, overlap, n_frames, slide, val_split, rotation, split_seed, None, names)
+        who, nf = type(self).__name__, self.n_frames
+        self.depths = (nf[1], nf[0]) if nf is not None else (_uniform_frames(self.hr_sheets, who), _uniform_frames(self.lr_sheets, who))
+        self.banks = (_SheetBank(self.hr_sheets, device, who), _SheetBank(self.lr_sheets, device, who))
+        self.hr_sheets, self.lr_sheets = self.banks[0].sheets, self.banks[1].sheets
+        del self.compact
+
+    def draw_pair_items(self, indices, pp=False):
+        """(HR table, LR table) for these dataset indices: the training rotations are drawn exactly as ``__getitem__`` would draw them for
+        the same sequence of indices, and each draw is written to both tables.  Every window is checked against its sheet here."""
+        entries = ([], [])
+        for idx in indices:
+            idx = int(idx)
+            self._check_idx(idx)
+            image_idx, _ = _get_image_idx(idx, self.slices, self.tiles)
+            rot = self._draw_rotation(idx, pp)
+            for side, bank, depth, (sheet, size, stride, frames, n_slices, local, slide) in zip(entries, self.banks, self.depths, self._side_args(idx)):
+                origin = _window_origin(sheet, size, stride, frames, n_slices, local, slide)
+                bank.check(image_idx, *origin, depth, size)
+                side.append((image_idx, *origin, rot))
+        return tuple(_window_rows(side).to(bank.device) for side, bank in zip(entries, self.banks))
+
+    def device_pair_batch(self, tables, u8=False):
+        """tables: ``draw_pair_items``' result.  float32 (uint8 with ``u8``) (hr [b, C, R, R], lr [b, c, r, r]) on the device, no host
+        synchronisation.  Each side is gathered at its own depth (``n_frames[1]`` / ``n_frames[0]``), which ``_transform_pair``'s
+        centre-frame slicing leaves as it is."""
+        from . import ops
+        out = []
+        for table, bank, depth, res in zip(tables, self.banks, self.depths, (self.hr_res, self.hr_res // self.lr_scale)):
+            if table.shape[0]:
+                side = bank.gather(table, depth, res)
+            else:
+                side = torch.empty(0, depth, res, res, dtype=torch.uint8, device=bank.device)
+            out.append(side if u8 or not table.shape[0] else ops.u8_to_f32(side))
         return tuple(out)
 
     def __getitem__(self, idx, pp=False):

@@ -601,6 +601,18 @@ def gen_pair_geometry_u8(stacks, rotations, res):
     return out
 
 
+def gather_windows_u8(sheet_table, n_sheets, items, c, res):
+    """Windows [n, c, res, res] (uint8) out of uint8 sheets resident on the device: ``sheet_table`` holds ``n_sheets``
+    ``pssr_sheet_desc`` and ``items`` n ``pssr_window_item`` (24 bytes each, any dtype), both on the device."""
+    for t, size in ((sheet_table, n_sheets), (items, None)):
+        if not t.is_cuda or not t.is_contiguous() or (t.numel() * t.element_size()) % 24 or (size is not None and t.numel() * t.element_size() != 24 * size):
+            raise ValueError("gather_windows_u8 needs contiguous device tables of 24-byte records")
+    n = items.numel() * items.element_size() // 24
+    out = torch.empty(n, c, res, res, dtype=torch.uint8, device=items.device)
+    L.check(L.lib().pssr_gather_windows_u8(L.ptr(sheet_table), n_sheets, L.ptr(items), n, L.ptr(out), c, res, L.stream_ptr()), "pssr_gather_windows_u8")
+    return out
+
+
 def normalize_preds_u8(hr, hr_hat, pmin=0.1, pmax=99.9):
     """uint8 device tensors [..., H, W] of equal shape -> (hr_norm, hr_hat_norm) uint8, as pssr.util.normalize_preds (bit-exact)."""
     if hr.dtype != torch.uint8 or hr_hat.dtype != torch.uint8 or hr.shape != hr_hat.shape or not hr.is_cuda:

@@ -396,8 +396,8 @@ def _crappify_unrounded(x, crappifier, seed, tile_offset):
 class _Crappifier_Objective:
     """The noise-profile objective of ``approximate_crappifier`` (pssr/train.py:348-386) on the device.
 
-    Once, at construction: every pair goes to HBM as uint8 (a ``DevicePairedTileDataset`` is gathered in place; any other paired
-    dataset is read item by item), HR is reduced to the LR size by the Pillow-exact kernel, and the histogram and sum of the real
+    Once, at construction: every pair goes to HBM as uint8 (a ``DevicePairedTileDataset`` / ``DevicePairedSlidingDataset`` is gathered
+    in place; any other paired dataset is read item by item), HR is reduced to the LR size by the Pillow-exact kernel, and the histogram and sum of the real
     profile ``lr - ds_hr`` are taken per pair -- none of this depends on the parameters, while the reference redoes it on every call.
     Per ``sample(params)``: the reference's ``random.shuffle`` of the indices and its first ``n_samples``; ``crappifier(*params)`` run
     through its device path (Philox seed ``seed``, tile offset advancing by ``n_samples`` per call); one profile launch over
@@ -409,7 +409,7 @@ class _Crappifier_Objective:
 
     def __init__(self, crappifier, dataset, n_samples, device="cuda", seed=0):
         from . import ops
-        from .data import DevicePairedTileDataset
+        from .data import DevicePairedSlidingDataset, DevicePairedTileDataset
         if torch.device(device).type != "cuda" or not torch.cuda.is_available():
             raise RuntimeError("pssr2_amd.approximate_crappifier runs on an MI355X (HIP) device only; there is no CPU fallback")
         if getattr(dataset, "is_lr", False):
@@ -419,7 +419,7 @@ class _Crappifier_Objective:
         n = len(dataset)
         if n == 0 or n_samples <= 0:
             raise ValueError("approximate_crappifier needs at least one pair")
-        if isinstance(dataset, DevicePairedTileDataset):
+        if isinstance(dataset, (DevicePairedTileDataset, DevicePairedSlidingDataset)):
             hr, lr = dataset.device_pair_batch(dataset.draw_pair_items(range(n), pp=True), u8=True)
             hr, lr = hr.to(device), lr.to(device)
         else:
