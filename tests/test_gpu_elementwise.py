@@ -1,5 +1,7 @@
-"""Element-wise / layout kernels with vectorised fast paths (csrc/elementwise.hip) vs torch on the CPU: bit-exact data movement,
-statistics within f32 summation noise."""
+"""The loader-fused and vectorised forms of csrc/elementwise.hip (pixel shuffle, relu_bwd_stats with the max-pool backward or the
+inverse pixel shuffle in its loader, the batched f32 copy) vs torch on the CPU: bit-exact data movement, statistics within f32
+summation noise.  The other entry points of that file (BatchNorm statistics / finalisation / backward, the input stage, max-pool,
+channel sums, layout changes, clip, stripe folds) are tested one by one against f64 references in tests/test_gpu_elementwise_ops.py."""
 import numpy as np
 import pytest
 import torch
