@@ -199,6 +199,7 @@ class ResUNet(nn.Module):
         self.compute_dtype = torch.float32
         self.infer_dtype = None       # storage type of eval-mode forwards; None: float16 for a bfloat16 model, else compute_dtype (Engine.storage_dtype)
         self.autograd_grads = False   # True: return parameter gradients to autograd (torch.autograd.grad, gradient hooks) instead of publishing .grad
+        self.sync_bn = False          # True (data-parallel runs): BatchNorm statistics over the global batch (Engine.bn_stats_count)
         self._engine = Engine(self)
 
     # ---- hidden widths that are not multiples of 16 (pssr/models/resunet.py:8-17 accepts any)
@@ -461,6 +462,7 @@ class RDResUNet(nn.Module):
         self.compute_dtype = torch.float32
         self.infer_dtype = None       # storage type of eval-mode forwards; None: float16 for a bfloat16 model, else compute_dtype (Engine.storage_dtype)
         self.autograd_grads = False   # True: return parameter gradients to autograd (torch.autograd.grad, gradient hooks) instead of publishing .grad
+        self.sync_bn = False          # True (data-parallel runs): BatchNorm statistics over the global batch (Engine.bn_stats_count)
         from .rd_engine import RDEngine
         self._engine = RDEngine(self)
 

@@ -72,7 +72,7 @@ def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batc
     compact = False
     if host_fast:
         # host batches (any dataset through a DataLoader): one captured forward over a static input buffer per (dataset, batch size)
-        cache = model._engine.__dict__.setdefault("_eval_steppers", {})
+        cache = model._engine._eval_steppers
         evaler = cache.get((id(dataset), batch_size, "host"))
         if evaler is None or evaler.dataset is not dataset:
             if len(cache) >= 4:
@@ -87,7 +87,7 @@ def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batc
         dataloader = DataLoader(dataset, batch_size, sampler=idx, **dataloader_kwargs)
     elif fast:
         # one stepper (and one captured graph) per (dataset, batch size): a second call over the same dataset only replays
-        cache = model._engine.__dict__.setdefault("_eval_steppers", {})
+        cache = model._engine._eval_steppers
         evaler = cache.get((id(dataset), batch_size))
         if evaler is None or evaler.dataset is not dataset or len(idx) > evaler.cur.table.shape[0]:
             if len(cache) >= 4:           # each stepper pins a captured graph and its memory pool: keep the most recent few

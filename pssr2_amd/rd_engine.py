@@ -16,20 +16,16 @@ The reference runs ``RDResUNet.forward`` (pssr/models/rdresunet.py:104-130) and 
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
+
 import torch
 
 from . import _lib as L
+from . import atrous as A
 from . import ops
-from .engine import Engine, _Arena, _BNState, _Conv, _blocked_order
+from .engine import Engine, _Arena
 
 LN_EPS = 1e-6
-
-
-def _obj(**kw):
-    o = type("O", (), {})()
-    o.__dict__.update(kw)
-    return o
-
 
 
 class _ZeroArena:
@@ -67,28 +63,22 @@ class _ZeroArena:
 
 
 class RDEngine(Engine):
-    _z64 = None
-    _z32 = None
+    def __init__(self, model):
+        super().__init__(model)
+        self.ps = self.pc = self.stage_level = self.skip_of_stage = self.n_levels = None       # static structure (_structure)
+        # zero-initialised scratch of a backward pass (f64 sums, f32 side tensors)
+        self._z64, self._z32 = _ZeroArena(torch.float64), _ZeroArena(torch.float32)
 
     # ------------------------------------------------------------------ static structure
     def _structure(self, device):
         m = self.model
-        if getattr(self, "_built_for", None) == device:
+        if self._built_for == device:
             return
         enc = m.encoder
-        self.cin, self.cout = m.channels
         self.hidden = list(m.hidden)
-        self.atrous = m.norm is None          # pssr/models/rdresunet.py:80
-        self.r = m.reconstruction.scale
-        self.blk, self.explicit_shuffle = _blocked_order(self.r)
+        self._head_structure(device, self.hidden[-1] // m.ratios[-1] ** 2)       # (atrous: pssr/models/rdresunet.py:80)
         self.ps = enc.patch_size
-        self.xc = ops.pad_to(9 * self.cin, 16)
         self.pc = ops.pad_to(self.cin * self.ps * self.ps, 16)
-        self.h0 = self.hidden[-1] // m.ratios[-1] ** 2
-        h0, r2 = self.h0, self.r * self.r
-        idx = torch.arange(r2 * h0)
-        self.pre_perm = (idx if self.explicit_shuffle else (idx % h0) * r2 + idx // h0).to(torch.int32).to(device)
-        self.pre_perm_long = self.pre_perm.long()
         # stages: spatial level (number of down-samplings after the stem), skip index into the decoder (or None)
         ns = enc.num_stages
         lvl, levels = 0, []
@@ -100,10 +90,9 @@ class RDEngine(Engine):
         skip_stages = [i for i in range(ns) if i + 1 == ns or enc.ds_blocks[i + 1]]
         self.skip_of_stage = {s: len(skip_stages) - 1 - j for j, s in enumerate(skip_stages)}     # decoder index k fed by stage s
         self.n_levels = lvl + 1
-        self._convs = {}
         self._built_for = device
 
-    def _check_supported_rd(self, code, h, w, train):
+    def _check_supported(self, code, h, w, train):
         enc, m = self.model.encoder, self.model
         kch = 8 if code == L.F32 else 16
         g_align = 4 if code == L.F32 else 8
@@ -134,63 +123,33 @@ class RDEngine(Engine):
         if p is not None:
             return p
         m, enc = self.model, self.model.encoder
-        code = ops.dtype_code(dt)
         hid, nd = self.hidden, len(self.hidden)
-        p = _obj(n=n, h=h, w=w, dt=dt, code=code, bwd=None)
-        f32, f64 = _Arena(), _Arena()
+        p = self._new_plan(n, h, w, dt, device)
         p.small = _Arena()          # f32 [N, C] side tensors of the ESE gates (means are accumulated with atomics: zeroed per forward)
-
-        def buf(hh, ww, c):
-            return torch.zeros(n, hh, ww, ops.pad_to(c, 16), dtype=dt, device=device)
 
         p.enc_dims = [(h // self.ps >> l, w // self.ps >> l) for l in range(self.n_levels)]
         # decoder block k runs at the resolution of skip k: deepest first
         p.dims = [p.enc_dims[self.n_levels - 1 - k] for k in range(nd)]
-        p.bn_in = _BNState(self.cin, f32, f64)
-        p.xcol = buf(h, w, self.xc)
-        p.xpatch = buf(*p.enc_dims[0], self.pc)
+        p.xpatch = self._buf(p, *p.enc_dims[0], self.pc)
         # decoder concat buffers: cat[k] = [pixel_shuffle(decoder k-1 output) | skip k]; cat[0] is the last stage itself
         p.shuf_c = [0] + [hid[k - 1] // m.ratios[k] ** 2 for k in range(1, nd)]
-        p.cat = [buf(*p.dims[k], p.shuf_c[k] + m.skips[k]) for k in range(nd)]
-        nl = max(m.depth, 0) + 1
-        p.dec = []
-        from . import atrous as A
-        from .models import ResBlockA
-        for k in range(nd):
-            b = _obj(level=k, c=hid[k], a=None)
-            if isinstance(m.decoder[k], ResBlockA):
-                b.a = A.make_ablock_state(m.decoder[k], n, *p.dims[k], p.shuf_c[k] + m.skips[k], dt, device)
-                b.y, b.bn = [], []
-            else:
-                b.y = [buf(*p.dims[k], hid[k]) for _ in range(nl)]
-                b.act = None
-                b.bn = [_BNState(hid[k], f32, f64) for _ in range(nl)]
-            b.out = buf(*p.dims[k], hid[k])
-            p.dec.append(b)
-        p.feat = buf(h, w, self.h0)
-        p.xin = None
-        p.epool = p.rpool = None
-        if getattr(m, "encoder_pool", None) is not None:         # acts on the deepest skip (rdresunet.py:112-113)
-            p.epool = A.make_psp_state(m.encoder_pool, n, *p.dims[0], dt, device)
-            p.epool_out = buf(*p.dims[0], m.skips[0])
-        if getattr(m, "reconstruction_pool", None) is not None:
-            p.rpool = A.make_psp_state(m.reconstruction_pool, n, h, w, dt, device)
-            p.rpool_out = buf(h, w, self.h0)
-        r2 = self.r * self.r
-        p.pre = torch.zeros(n, h, w, r2 * self.h0, dtype=dt, device=device)
+        p.cat = [self._buf(p, *p.dims[k], p.shuf_c[k] + m.skips[k]) for k in range(nd)]
+        p.dec = [self._block_state(p, m.decoder[k], k, hid[k], p.shuf_c[k] + m.skips[k]) for k in range(nd)]
+        p.feat = self._buf(p, h, w, self.h0)
+        self._finish_plan(p, p.dec, p.dims[0], (h, w))      # (encoder_pool acts on the deepest skip: rdresunet.py:112-113)
         # encoder stages
-        p.stem_y = buf(*p.enc_dims[0], enc.n_init_features)
+        p.stem_y = self._buf(p, *p.enc_dims[0], enc.n_init_features)
         p.stem_stat = [torch.empty(n * p.enc_dims[0][0] * p.enc_dims[0][1], dtype=torch.float32, device=device) for _ in range(2)]
         p.stages = []
         for i in range(enc.num_stages):
             hh, ww = p.enc_dims[self.stage_level[i]]
             npix = n * hh * ww
-            st = _obj(idx=i, h=hh, w=ww, npix=npix, c_in=enc.stage_in[i], c_out=enc.stage_out[i], g=enc.growth_rates[i], ese=enc.ese_blocks[i])
+            st = SimpleNamespace(idx=i, h=hh, w=ww, npix=npix, c_in=enc.stage_in[i], c_out=enc.stage_out[i], g=enc.growth_rates[i], ese=enc.ese_blocks[i])
             k = self.skip_of_stage.get(i)
             if k is not None:
                 st.F, st.coff, st.skip = p.cat[k], p.shuf_c[k], k
             else:
-                st.F, st.coff, st.skip = buf(hh, ww, st.c_out), 0, None
+                st.F, st.coff, st.skip = self._buf(p, hh, ww, st.c_out), 0, None
             if i:
                 ph, pw = p.enc_dims[self.stage_level[i - 1]]
                 st.ds = bool(enc.ds_blocks[i])
@@ -203,11 +162,11 @@ class RDEngine(Engine):
             for b in range(enc.n_blocks[i]):
                 mod = self._stage_module(i)[b]
                 inter = mod.layers.layers[2].weight.shape[0]
-                bk = _obj(c_in=c, inter=inter, off=c, mod=mod)
-                bk.dw = buf(hh, ww, c)
-                bk.ln = buf(hh, ww, c)
-                bk.z = buf(hh, ww, inter)
-                bk.t = buf(hh, ww, st.g)
+                bk = SimpleNamespace(c_in=c, inter=inter, off=c, mod=mod)
+                bk.dw = self._buf(p, hh, ww, c)
+                bk.ln = self._buf(p, hh, ww, c)
+                bk.z = self._buf(p, hh, ww, inter)
+                bk.t = self._buf(p, hh, ww, st.g)
                 bk.stat = [torch.empty(npix, dtype=torch.float32, device=device) for _ in range(2)]
                 bk.wp = torch.empty(49, c, dtype=torch.float32, device=device)
                 bk.wpf = torch.empty(49, c, dtype=torch.float32, device=device)
@@ -216,19 +175,11 @@ class RDEngine(Engine):
                 st.blocks.append(bk)
                 c += st.g
             p.stages.append(st)
-        p.f32 = f32.build(torch.float32, device)
-        p.f64 = f64.build(torch.float64, device)
         p.small.build(torch.float32, device)
-        p.bn_in.bind(f32, f64)
-        for b in p.dec:
-            for s in b.bn:
-                s.bind(f32, f64)
         for st in p.stages:
             for bk in st.blocks:
                 if st.ese:
                     bk.s_mean, bk.u, bk.gate = (p.small.views[i].view(n, st.g) for i in (bk.s_mean, bk.u, bk.gate))
-        p.ones_pre = torch.ones(r2 * self.h0, dtype=torch.float32, device=device)
-        p.zeros_pre = torch.zeros(r2 * self.h0, dtype=torch.float32, device=device)
         self.plans[key] = p
         return p
 
@@ -236,33 +187,15 @@ class RDEngine(Engine):
         """The DenseStage (nn.Sequential of DenseBlocks) of stage i."""
         return self.model.encoder.dense_stages[i][-1]
 
-    def _bwd_buffers(self, p, device):
+    def _bwd_buffers(self, p):
         if p.bwd is not None:
             return p.bwd
-        n, dt, hid, nd = p.n, p.dt, self.hidden, len(self.hidden)
-        m, enc = self.model, self.model.encoder
-        b = _obj()
-
-        def buf(hh, ww, c):
-            return torch.zeros(n, hh, ww, ops.pad_to(c, 16), dtype=dt, device=device)
+        n, enc = p.n, self.model.encoder
 
         # decoder working buffers, indexed by decoder block k (Engine._block_backward indexes them by blk.level)
-        b.dz = [buf(*p.dims[k], hid[k]) for k in range(nd)]
-        b.dy = [buf(*p.dims[k], hid[k]) for k in range(nd)]
-        b.dy2 = [buf(*p.dims[k], hid[k]) for k in range(nd)] if self.side_wgrad else b.dy
-        b.dy3 = [buf(*p.dims[k], hid[k]) for k in range(nd)] if self.side_wgrad else b.dy
-        b.g = [buf(*p.dims[k], hid[k]) for k in range(nd)]
-        b.dout = [buf(*p.dims[k], hid[k]) for k in range(nd)]
-        b.dcat = [buf(*p.dims[k], p.shuf_c[k] + m.skips[k]) for k in range(nd)]
-        b.dfeat = buf(p.h, p.w, self.h0)
-        b.drpool = buf(p.h, p.w, self.h0) if p.rpool is not None else None
-        b.depool = buf(*p.dims[0], m.skips[0]) if p.epool is not None else None
-        b.dxcol_b = buf(p.h, p.w, self.xc)
-        b.dxpatch = buf(*p.enc_dims[0], self.pc)
-        r = self.r
-        b.g_hr = torch.zeros(n, p.h * r, p.w * r, 16, dtype=dt, device=device)
-        b.dpre = torch.zeros(n, p.h, p.w, r * r * self.h0, dtype=dt, device=device)
-        b.sum64 = torch.zeros(ops.STAT_STRIPES * max(16, r * r * self.h0), dtype=torch.float64, device=device)
+        b = self._new_bwd_buffers(p)
+        b.dfeat = self._buf(p, p.h, p.w, self.h0)
+        b.dxpatch = self._buf(p, *p.enc_dims[0], self.pc)
         # encoder: gradient buffers with the layout of the stage buffers; per-stage scratch shared by its blocks
         b.G, b.scr = [], []
         small = _Arena()
@@ -272,18 +205,18 @@ class RDEngine(Engine):
             if st.skip is not None:
                 b.G.append((b.dcat[st.skip], st.coff))
             else:
-                b.G.append((buf(st.h, st.w, st.c_out), 0))
+                b.G.append((self._buf(p, st.h, st.w, st.c_out), 0))
             cmax = st.blocks[-1].c_in
             imax = st.blocks[-1].inter
-            sc = _obj(ddw=buf(st.h, st.w, cmax), dln=buf(st.h, st.w, cmax), dz=buf(st.h, st.w, imax), dt=buf(st.h, st.w, st.g))
+            sc = SimpleNamespace(ddw=self._buf(p, st.h, st.w, cmax), dln=self._buf(p, st.h, st.w, cmax), dz=self._buf(p, st.h, st.w, imax), dt=self._buf(p, st.h, st.w, st.g))
             if st.idx:
                 sc.dtr = torch.zeros_like(st.tr_ln)
             sc.A, sc.du, sc.add = (small.take(n * st.g) for _ in range(3))
             b.scr.append(sc)
             maxc = max(maxc, st.c_out, imax)
-        b.dstem = buf(*p.enc_dims[0], enc.n_init_features)
-        b.stat_ln = torch.zeros(ops.STAT_STRIPES * 2 * max(maxc, enc.n_init_features), dtype=torch.float64, device=device)
-        small.build(torch.float32, device)
+        b.dstem = self._buf(p, *p.enc_dims[0], enc.n_init_features)
+        b.stat_ln = torch.zeros(ops.STAT_STRIPES * 2 * max(maxc, enc.n_init_features), dtype=torch.float64, device=p.device)
+        small.build(torch.float32, p.device)
         b.small = small
         for st, sc in zip(p.stages, b.scr):
             sc.A, sc.du, sc.add = (small.views[i].view(n, st.g) for i in (sc.A, sc.du, sc.add))
@@ -291,15 +224,6 @@ class RDEngine(Engine):
         return b
 
     # ------------------------------------------------------------------ small helpers
-    def _pw(self, module, name, code, **spec):
-        """Packed weight of a conv module under a named packing spec (cached per parameter version)."""
-        c = self._convs.get(id(module))
-        if c is None:
-            c = self._convs[id(module)] = _Conv(module, {}, self._wepoch)
-        if name not in c.specs:
-            c.specs[name] = spec
-        return c.get(name, code)
-
     def _ln_grads(self, bw, grads, ln_module, c, s64):
         iw, ib = self._gindex[id(ln_module.weight)], self._gindex[id(ln_module.bias)]
         if self._goffs[ib] == self._goffs[iw] + c:
@@ -312,7 +236,7 @@ class RDEngine(Engine):
 
     def _fold64(self, s64, dst):
         """Striped f64 sums -> f32 parameter gradient: queued for one batched launch (Engine._fold) when the sums sit in the arena."""
-        if self._z64 is not None and self._z64.owns(s64):
+        if self._z64.owns(s64):
             self._fold(s64, dst)
         else:
             ops.f64_to_f32(s64, dst)
@@ -333,7 +257,7 @@ class RDEngine(Engine):
             s64 = torch.zeros(ops.STAT_STRIPES * c, dtype=torch.float64, device=bw.stat_ln.device)
             # allocated on the launch stream, used on the second one: kept alive until the streams have joined (a block freed when the
             # closure dies goes back to the launch stream's pool and can be handed out again while the side kernels still read it)
-            self.__dict__.setdefault("_keepalive", []).append(s64)
+            self._keepalive.append(s64)
         g = self._gbuf(bias)
         grads[id(bias)] = g
 
@@ -342,49 +266,12 @@ class RDEngine(Engine):
             ops.f64_to_f32(s64, g)
         return run
 
-    def _wgrad1x1(self, p, grads, conv_module, dy, cout, dy_coff, src, cin_pad, hh, ww, *, mode=0, gelu_in=False, first=None):
-        code = p.code
-        esz = 4 if code == L.F32 else 2
-        rows = cout if (cout * esz) % 16 == 0 else ops.pad_to(cout, 16)
-        w = conv_module.weight
-        slot = grads[id(w)] = self._gbuf(w)
-
-        def run():
-            if first is not None:
-                first()
-            dwp = ops.conv2d_wgrad_parts(dy, rows, src, cin_pad, 1, n=p.n, h=hh, w=ww, dtype=code, dy_coff=dy_coff, gelu_in=gelu_in)
-            ops.unpack_conv_wgrad(dwp, slot, mode=mode, k_pad=cin_pad, accumulate=True)     # slot zeroed at the start of backward
-        if self._side_on:
-            self._on_side([dy], run)       # second stream: see Engine._on_side / _before_write
-        else:
-            run()
-
     # ------------------------------------------------------------------ forward
     def forward(self, x, train):
         m, enc = self.model, self.model.encoder
-        if not x.is_cuda:
-            raise RuntimeError("pssr2_amd.RDResUNet runs on an MI355X (HIP) device only; there is no CPU fallback")
-        x = x.contiguous().float()
-        self._structure(x.device)
-        n, c, h, w = x.shape
-        if c != self.cin:
-            raise ValueError(f"expected {self.cin} input channels, got {c}")
-        dt = self.storage_dtype(train)
-        code = ops.dtype_code(dt)
-        self._check_supported_rd(code, h, w, train)
-        p = self._plan(n, h, w, dt, x.device)
-        self._repack_all(code)
+        x, p = self._forward_begin(x, train)
+        n, code = p.n, p.code
         hid, nd = self.hidden, len(self.hidden)
-        if train:
-            p.f64.buf.zero_()
-            self._count_batches()
-        if self.atrous:
-            p.bn_in.scale.fill_(1.0), p.bn_in.shift.zero_()          # no input BatchNorm
-        else:
-            if train:
-                ops.channel_stats_nchw(x, p.bn_in.stats, 1 / 128, -1.0)
-            self._bn_forward(p, p.bn_in, m.norm, float(n * h * w), train)
-        ops.input_im2col(x, p.xcol, p.bn_in.scale, p.bn_in.shift, code)
         ops.input_patchify(x, p.xpatch, p.bn_in.scale, p.bn_in.shift, self.ps, code)
         p.small.buf.zero_()
         # ---- stem: conv(k = s = patch) as a 1x1 conv over patches, then LayerNorm2d into stage 0's buffer
@@ -428,7 +315,6 @@ class RDEngine(Engine):
                     gate = bk.gate
                 ops.scale_nc(bk.t, gate, bk.mod.gamma, None, st.F, n, st.h * st.w, st.g, code, out_coff=st.coff + bk.off)
         # ---- decoder
-        from . import atrous as A
         for k in range(nd):
             blk = p.dec[k]
             src = p.cat[k]
@@ -458,24 +344,24 @@ class RDEngine(Engine):
         dwc, ln, c1, c2 = lay[0], lay[1], lay[2], lay[4]
         g = st.g
         # ---- layer scale (+ ESE gate): dt, dgamma (, d fc)
-        A = self._z32.take(n * g, sc.A.view(-1)).view(n, g)
-        ops.image_channel_dot(G, bk.t, n, hw, g, 1.0, A, code, a_coff=gcoff + bk.off)
+        dots = self._z32.take(n * g, sc.A.view(-1)).view(n, g)
+        ops.image_channel_dot(G, bk.t, n, hw, g, 1.0, dots, code, a_coff=gcoff + bk.off)
         dgam = self._gbuf(bk.mod.gamma)
         if st.ese:
             fc = lay[5].fc
             dbfc = self._gbuf(fc.bias)
             dwfc = self._gbuf(fc.weight)
-            ops.ese_bwd(A, bk.gate, bk.u, bk.mod.gamma, bk.s_mean, fc.weight, hw, sc.du, dgam, dbfc, dwfc, sc.add)
+            ops.ese_bwd(dots, bk.gate, bk.u, bk.mod.gamma, bk.s_mean, fc.weight, hw, sc.du, dgam, dbfc, dwfc, sc.add)
             grads[id(fc.weight)], grads[id(fc.bias)] = dwfc, dbfc
             self._before_write(sc.dt)
             ops.scale_nc(G, bk.gate, bk.mod.gamma, sc.add, sc.dt, n, hw, g, code, t_coff=gcoff + bk.off)
         else:
-            ops.ese_bwd(A, None, None, bk.mod.gamma, None, None, hw, None, dgam, None, None, None)
+            ops.ese_bwd(dots, None, None, bk.mod.gamma, None, None, hw, None, dgam, None, None, None)
             self._before_write(sc.dt)
             ops.scale_nc(G, None, bk.mod.gamma, None, sc.dt, n, hw, g, code, t_coff=gcoff + bk.off)
         grads[id(bk.mod.gamma)] = dgam
         # ---- second 1x1 conv (input = gelu(z))
-        self._wgrad1x1(p, grads, c2, sc.dt, g, 0, bk.z, bk.inter, st.h, st.w, gelu_in=True,
+        self._wgrad1x1(grads, c2, sc.dt, g, 0, bk.z, bk.inter, n, st.h, st.w, code, side=True, gelu_in=True,
                        first=self._bias_grad_job(bw, grads, c2.bias, sc.dt, st.npix, g, code))
         s64 = self._z64.take(ops.STAT_STRIPES * 2 * bk.inter, bw.stat_ln)
         self._before_write(sc.dz)
@@ -486,7 +372,7 @@ class RDEngine(Engine):
         grads[id(c1.bias)] = sums[:bk.inter]
         # ---- first 1x1 conv (input = LayerNorm output)
         cpad = bk.ln.shape[-1]
-        self._wgrad1x1(p, grads, c1, sc.dz, bk.inter, 0, bk.ln, cpad, st.h, st.w)
+        self._wgrad1x1(grads, c1, sc.dz, bk.inter, 0, bk.ln, cpad, n, st.h, st.w, code, side=True)
         ops.conv2d(sc.dz, bk.inter, self._pw(c1, "dgrad", code, mode=1), sc.dln, bk.c_in, n=n, h=st.h, w=st.w)
         # ---- LayerNorm2d
         s64 = self._z64.take(ops.STAT_STRIPES * 2 * bk.c_in, bw.stat_ln)
@@ -516,22 +402,19 @@ class RDEngine(Engine):
         return self._goffs[self._gindex[id(first)]]
 
     def backward(self, dout, split_cb=None):
-        if self._z64 is None:
-            self._z64, self._z32 = _ZeroArena(torch.float64), _ZeroArena(torch.float32)
         if self.saved is None:
             raise RuntimeError("backward called without a training-mode forward (or called twice)")
         p, x = self.saved
         self.saved = None
         m, enc = self.model, self.model.encoder
         dev = x.device
-        bw = self._bwd_buffers(p, dev)
-        n, h, w, code = p.n, p.h, p.w, p.code
-        hid, nd, r, h0 = self.hidden, len(self.hidden), self.r, self.h0
+        bw = self._bwd_buffers(p)
+        n, code = p.n, p.code
+        hid, nd, h0 = self.hidden, len(self.hidden), self.h0
         grads = {}
         self._begin_backward(dev)
         for arena in (self._z64, self._z32):
             arena.begin(dev)
-        from . import atrous as A
         if p.rpool is not None:
             self._head_backward(p, bw, grads, dout, p.rpool_out, bw.drpool)
             A.psp_backward(self, p.rpool, m.reconstruction_pool, grads, p.feat, 0, n, code, p.rpool_out, 0, bw.drpool, 0, bw.dfeat, 0)
@@ -555,10 +438,7 @@ class RDEngine(Engine):
                 self._block_backward(p, bw, grads, blk, m.decoder[k], p.cat[k], p.cat[k].shape[-1], False, blk.out, 0, bw.dout[k], bw.dcat[k],
                                      p.shuf_c[k] + m.skips[k], dout_from=dfrom)
         if split_cb is not None:       # reconstruction + decoder gradients (the tail of the flat buffer) are final
-            self._flush_folds()
-            self._flush_moves()
-            self._side_join()
-            split_cb()
+            self._split(split_cb)
         # ---- encoder, last stage first
         bw.small.buf.zero_()
         for i in range(len(p.stages) - 1, -1, -1):
@@ -571,7 +451,7 @@ class RDEngine(Engine):
                 seq = enc.dense_stages[i]
                 ln, conv = seq[0], seq[1]
                 kc = st.tr_ln.shape[-1]
-                self._wgrad1x1(p, grads, conv, G, st.c_in, gcoff, st.tr_ln, kc, st.h, st.w, mode=4 if st.ds else 0,
+                self._wgrad1x1(grads, conv, G, st.c_in, gcoff, st.tr_ln, kc, n, st.h, st.w, code, side=True, mode=4 if st.ds else 0,
                                first=self._bias_grad_job(bw, grads, conv.bias, G, st.npix, st.c_in, code, coff=gcoff))
                 # the dgrad reads the first c_in channels of G at its offset (K padded to 16: the packed weight rows beyond
                 # c_in are zero and the gradient buffer holds finite values there)
@@ -593,18 +473,9 @@ class RDEngine(Engine):
                             g_coff=g0o, c_pad=c0)
         self._ln_grads(bw, grads, stem_ln, c0, s64)
         self._bias_grad(bw, grads, stem_conv.bias, bw.dstem, st0.npix, c0, code)
-        self._wgrad1x1(p, grads, stem_conv, bw.dstem, c0, 0, p.xpatch, self.pc, st0.h, st0.w, mode=2)
+        self._wgrad1x1(grads, stem_conv, bw.dstem, c0, 0, p.xpatch, self.pc, n, st0.h, st0.w, code, side=True, mode=2)
         ops.conv2d(bw.dstem, ops.pad_to(c0, 16), self._pw(stem_conv, "dgrad", code, mode=3), bw.dxpatch, self.pc, n=n, h=st0.h, w=st0.w)
         self._ready(grads, list(enc.stem.parameters()))
-        if self.atrous:                 # no input BatchNorm
-            return self._finish_backward(grads)
         # ---- input BatchNorm parameters (gradient sources: head im2col + stem patches)
-        stn = p.bn_in
-        stn.bstats.zero_()
-        self._before_write(bw.dxcol_b)          # (its producer may have run on the second stream: Engine._head_backward)
-        ops.input_norm_bwd2(None, bw.dxcol_b, bw.dxpatch, self.ps, x, stn.mean, stn.invstd, stn.bstats, code)
-        dgam, dbet = self._gbuf(m.norm.weight), self._gbuf(m.norm.bias)
-        self.bn_coefs(stn.bstats, float(n * h * w), m.norm.weight, stn.mean, stn.invstd, stn.ca, stn.cb, stn.cc, dgam, dbet)
-        grads[id(m.norm.weight)], grads[id(m.norm.bias)] = dgam, dbet
-        self._ready(grads, list(m.norm.parameters()))
-        return self._finish_backward(grads)
+        return self._finish_input_norm(p, bw, grads, lambda stn: ops.input_norm_bwd2(None, bw.dxcol_b, bw.dxpatch, self.ps, x, stn.mean, stn.invstd,
+                                                                                      stn.bstats, code))

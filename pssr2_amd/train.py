@@ -248,7 +248,7 @@ def _clip_grad_value(model, clip):
     grads = [p.grad for p in model.parameters() if p.grad is not None]
     if not grads:
         return
-    flat = getattr(engine, "_flat_grad", None) if engine is not None else None
+    flat = engine._flat_grad if engine is not None else None
     if flat is not None and len(grads) == len(engine._gviews) and all(g.data_ptr() == v.data_ptr() for g, v in zip(grads, engine._gviews)):
         ops.clamp_f32(flat, -clip, clip, out=flat)
     elif engine is not None:
