@@ -440,6 +440,22 @@ typedef struct pssr_window_item { int sheet, frame0, y0, x0, rot, flip_axis; } p
 int pssr_gather_windows_u8(const pssr_sheet_desc* sheets_dev, int n_sheets, const pssr_window_item* items_dev, int n_items,
                            uint8_t* out, int c, int res, pssr_stream_t stream);
 
+/* Collage rows of predict_collage (pssr/predict.py:85-142; `_collage_preds` / `_image_stack`, pssr/predict.py:213-243): for each of
+ * n_images images one row of n_panels (1..3) panels of h x w pixels side by side in a uint8 canvas resident in HBM,
+ *   canvas[(row0 + i) * h + y][p * w + x] = panel_p(i)[yi_p[y]][xi_p[x]],
+ * canvas rows canvas_pitch >= n_panels * w bytes apart; the caller provides (row0 + n_images) * h of them.  `panels` is a HOST array
+ * (it travels as a kernel argument).  A panel is a strided view: `src` points at pixel (0, 0) of image 0 (it already selects channel,
+ * frame and crop), image i lies image_stride elements further, rows row_pitch elements apart; src_h x src_w is what may be read.
+ * Pixels are uint8, or (is_f32) float32 turned into fminf(fmaxf(v, 0), 255) truncated toward zero as pssr_clip_u8 does.  yi / xi:
+ * device int32 tables of h / w source indices (PIL.Image.resize(NEAREST): pssr/predict.py:228), both NULL = the identity.  An index
+ * outside [0, src_h) / [0, src_w) writes 0 for that byte and reads nothing.  n_images <= 65535.  16-byte stores when w % 16 == 0 and
+ * canvas and canvas_pitch are 16-byte aligned (16-byte loads for identity panels whose source rows are); byte accesses otherwise. */
+typedef struct pssr_collage_panel {
+    const void* src; int64_t image_stride; int32_t row_pitch, src_h, src_w, is_f32; const int32_t* yi; const int32_t* xi;
+} pssr_collage_panel;                                                                                       /* 48 bytes */
+int pssr_collage_rows_u8(const pssr_collage_panel* panels, int n_panels, uint8_t* canvas, int64_t canvas_pitch, int row0, int n_images,
+                         int h, int w, pssr_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * Atrous / PSP-pooling model variants (pssr/models/_blocks.py:43-92 ResBlockA, PSP_Pooling).

@@ -40,6 +40,12 @@ def __getattr__(name):
     if name in ("predict_images",):
         from .predict import predict_images
         return predict_images
+    if name in ("predict_collage",):
+        from .predict import predict_collage
+        return predict_collage
+    if name in ("preprocess_dataset",):
+        from .data import preprocess_dataset
+        return preprocess_dataset
     if name in ("FusedAdamW",):
         from .optim import FusedAdamW
         return FusedAdamW

@@ -69,6 +69,12 @@ class WindowItem(C.Structure):
     _fields_ = [("sheet", C.c_int), ("frame0", C.c_int), ("y0", C.c_int), ("x0", C.c_int), ("rot", C.c_int), ("flip_axis", C.c_int)]
 
 
+class CollagePanel(C.Structure):
+    """struct pssr_collage_panel (include/pssr_mi355.h)"""
+    _fields_ = [("src", C.c_void_p), ("image_stride", C.c_int64), ("row_pitch", C.c_int32), ("src_h", C.c_int32), ("src_w", C.c_int32),
+                ("is_f32", C.c_int32), ("yi", C.c_void_p), ("xi", C.c_void_p)]
+
+
 COPY_BATCH_MAX = 16
 
 
@@ -119,6 +125,7 @@ def lib():
         _lib.pssr_noise_profile_loss.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p,
                                                  c_void_p]
         _lib.pssr_gather_windows_u8.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]
+        _lib.pssr_collage_rows_u8.argtypes = [c_void_p, c_int, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p]
     return _lib
 
 

@@ -213,10 +213,10 @@ class ArrayDataset(Dataset):
     def __len__(self):
         return len(self.images)
 
-    def __getitem__(self, idx):
+    def __getitem__(self, idx, pp=False):
         if idx >= len(self):
             raise IndexError(f"Tried to retrieve invalid image. Index {idx} is not less than {len(self)} total image frame slices.")
-        is_val = idx in self.val_idx
+        is_val = idx in self.val_idx or pp        # pp: preprocess_dataset's items are never rotated (pssr/data.py:103)
         rot = [bool(random.getrandbits(1)), random.choice((1, 2, (1, 2)))] if self.rotation and not is_val else False
         hr = self.images[idx]
         if self.is_lr:
@@ -651,6 +651,64 @@ class PairedSlidingDataset(PairedSlidingArrayDataset):
                 f"total frame slices\nhigh-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}")
 
 
+def _save_stack(path, stack):
+    """uint8 [C, H, W] as a tif with one page per frame through Pillow, as ``predict_images`` writes its outputs."""
+    from PIL import Image
+    frames = [Image.fromarray(f) for f in np.ascontiguousarray(stack)]
+    frames[0].save(path, save_all=len(frames) > 1, append_images=frames[1:])
+
+
+def preprocess_dataset(dataset: Dataset, preprocess_hr: bool = False, out_dir: str = "preprocess", *, batch_size: int = 64):
+    r"""Saves the processed frame slices of a dataset -- cropping / padding and crappification as its arguments specify, rotation
+    disabled -- to ``{out_dir}/lr/{name}.tif`` and, with ``preprocess_hr``, ``{out_dir}/hr/{name}.tif`` for every index
+    (pssr/data.py:446-467: same arguments and file names; multi-page tifs through Pillow instead of tifffile).
+
+    Host datasets go item by item through ``dataset.__getitem__(idx, pp=True)``, as upstream.  Datasets that make their batches on the
+    MI355X (``draw_items`` + ``device_batch``, or ``draw_pair_items`` + ``device_pair_batch``) go ``batch_size`` items at a time: one
+    draw with ``pp=True``, the batch method, ``pssr_clip_u8`` (exact: these classes apply no transforms, every value is an integer in
+    [0, 255]) and one device-to-host copy per batch and side; their Philox tile counter advances as for any other batch.  An LR-mode
+    dataset has no pairs and raises ``ValueError`` (upstream fails there while unpacking the item)."""
+    import os
+    if getattr(dataset, "is_lr", False):
+        raise ValueError("Dataset must be paired with high-low-resolution images for preprocessing: an LR-mode dataset has no pairs.")
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be positive, got {batch_size}")
+    os.makedirs(f"{out_dir}/lr", exist_ok=True)
+    if preprocess_hr:
+        os.makedirs(f"{out_dir}/hr", exist_ok=True)
+
+    def save(idx, hr, lr):
+        name = dataset._get_name(idx)
+        _save_stack(f"{out_dir}/lr/{name}.tif", lr)
+        if preprocess_hr:
+            _save_stack(f"{out_dir}/hr/{name}.tif", hr)
+
+    if hasattr(dataset, "draw_items") and hasattr(dataset, "device_batch"):
+        draw, batch = dataset.draw_items, dataset.device_batch
+    elif hasattr(dataset, "draw_pair_items") and hasattr(dataset, "device_pair_batch"):
+        draw, batch = dataset.draw_pair_items, dataset.device_pair_batch
+    else:
+        for idx in range(len(dataset)):
+            hr, lr = dataset.__getitem__(idx, pp=True)
+            save(idx, np.asarray(hr, dtype=np.uint8) if preprocess_hr else None, np.asarray(lr, dtype=np.uint8))
+        return
+
+    from . import ops
+
+    def to_host(x):
+        x = x.contiguous().float()
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+        ops.clip_u8(x, out)
+        return out.cpu().numpy()
+
+    for first in range(0, len(dataset), batch_size):
+        indices = list(range(first, min(first + batch_size, len(dataset))))
+        hr, lr = batch(draw(indices, pp=True))
+        hr, lr = to_host(hr) if preprocess_hr else None, to_host(lr)
+        for k, idx in enumerate(indices):
+            save(idx, hr[k] if preprocess_hr else None, lr[k])
+
+
 def synthetic_em_tile(index, res=512, channels=1):
     """Seeded synthetic EM-like uint8 tile: band-limited noise + white noise."""
     rng = np.random.default_rng(1234 + index)
@@ -780,20 +838,20 @@ class DeviceTileDataset(Dataset):
     def _get_name(self, idx):
         return self.names[idx]
 
-    def _draw_rotation(self, idx):
+    def _draw_rotation(self, idx, pp=False):
         # ``idx in self.val_idx`` as upstream (pssr/data.py:103), with the list hashed once per assignment / length change: users enlarge
         # val_idx after training to predict every image
         key = (id(self.val_idx), len(self.val_idx))
         if key != self._val_key:
             self._val_set, self._val_key = set(self.val_idx), key
-        if self.rotation and idx not in self._val_set:
+        if self.rotation and not (idx in self._val_set or pp):
             return [bool(random.getrandbits(1)), random.choice((1, 2, (1, 2)))]      # the reference's draws, in its order
         return False
 
-    def draw_items(self, indices):
+    def draw_items(self, indices, pp=False):
         """Gather table (int64 [n, 3] on the device = n ``pssr_gather_item``) for these dataset indices, drawing the training
-        rotations exactly as ``__getitem__`` would for the same sequence of indices."""
-        return _gather_table(self.images, indices, [self._draw_rotation(int(i)) for i in indices])
+        rotations exactly as ``__getitem__`` would for the same sequence of indices (none with ``pp``)."""
+        return _gather_table(self.images, indices, [self._draw_rotation(int(i), pp) for i in indices])
 
     def device_batch(self, items):
         """items: int64 [b, 3] device rows of ``draw_items``.  Returns float32 (hr, lr) on the device, or lr alone in LR mode.  No
@@ -809,10 +867,10 @@ class DeviceTileDataset(Dataset):
         ops.counter_add(self.tile_counter, b)
         return hr, lr
 
-    def __getitem__(self, idx):
+    def __getitem__(self, idx, pp=False):
         if idx >= len(self):
             raise IndexError(f"Tried to retrieve invalid image. Index {idx} is not less than {len(self)} total image frame slices.")
-        out = self.device_batch(self.draw_items([idx]))
+        out = self.device_batch(self.draw_items([idx], pp))
         return out[0] if self.is_lr else (out[0][0], out[1][0])
 
 

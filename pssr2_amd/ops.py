@@ -613,6 +613,72 @@ def gather_windows_u8(sheet_table, n_sheets, items, c, res):
     return out
 
 
+def nearest_index(src, dst):
+    """int32 [dst]: the source index of every output pixel of ``PIL.Image.resize(NEAREST)`` from ``src`` to ``dst`` pixels along one
+    axis (pssr/predict.py:228).  Pillow's affine nearest-neighbour path accumulates the source coordinate in double --
+    ``xo = 0.5 * a; for x: idx = (int) xo; xo += a`` with ``a = src / dst`` -- and that accumulation is restated here: the closed form
+    ``floor((x + 0.5) * src / dst)`` rounds differently for many non-integer ratios.  Host only (numpy)."""
+    import numpy as np
+    if src < 1 or dst < 1:
+        raise ValueError(f"nearest_index needs positive sizes, got {src} -> {dst}")
+    a = float(src) / float(dst)
+    xo, out = 0.5 * a, np.empty(dst, dtype=np.int32)
+    for x in range(dst):
+        out[x] = int(xo)
+        xo += a
+    return out
+
+
+_NEAREST_TABLES = {}
+
+
+def nearest_table(src, dst, device):
+    """``nearest_index(src, dst)`` as an int32 tensor on ``device``, made once per (src, dst, device)."""
+    key = (int(src), int(dst), str(torch.device(device)))
+    t = _NEAREST_TABLES.get(key)
+    if t is None:
+        t = _NEAREST_TABLES[key] = torch.from_numpy(nearest_index(int(src), int(dst))).to(device)
+    return t
+
+
+def collage_rows_u8(panels, canvas, row0=0):
+    """Composes collage rows into ``canvas`` (uint8 [rows, columns] on the device, unit column stride): pssr_collage_rows_u8.
+    ``panels``: 1..3 entries ``src`` or ``(src, yi, xi)``; ``src`` is a uint8 or float32 device tensor [n, src_h, src_w] (any view with
+    unit column stride), ``yi`` [h] / ``xi`` [w] int32 device index tables (``nearest_table``), both None = identity (h x w = the
+    source size).  All panels share n, h and w; image i fills canvas rows (row0 + i) * h .. + h - 1, panel p columns p * w .. + w - 1.
+    float32 pixels are clipped to [0, 255] and truncated (``clip_u8``); a table entry outside the source gives 0."""
+    if not 1 <= len(panels) <= 3:
+        raise ValueError("collage_rows_u8 takes 1 to 3 panels")
+    if canvas.dtype != torch.uint8 or not canvas.is_cuda or canvas.dim() != 2 or canvas.stride(1) != 1:
+        raise ValueError("collage_rows_u8 needs a uint8 device canvas [rows, columns] with unit column stride")
+    descs, keep, size, n = (L.CollagePanel * len(panels))(), [], None, None
+    for d, panel in zip(descs, panels):
+        src, yi, xi = panel if isinstance(panel, (tuple, list)) else (panel, None, None)
+        if src.dtype not in (torch.uint8, torch.float32) or src.dim() != 3 or src.device != canvas.device or min(src.shape) < 1:
+            raise ValueError("collage_rows_u8: a panel source is a non-empty uint8 or float32 tensor [n, h, w] on the canvas's device")
+        if src.stride(2) != 1 or src.stride(1) < src.shape[2] or src.stride(0) < 0:
+            src = src.contiguous()
+        if (yi is None) != (xi is None):
+            raise ValueError("collage_rows_u8: a panel has one index table but not the other")
+        for t in (yi, xi):
+            if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or t.device != canvas.device or not t.is_contiguous()):
+                raise ValueError("collage_rows_u8: index tables are contiguous int32 vectors on the canvas's device")
+        hw = tuple(src.shape[1:]) if yi is None else (yi.numel(), xi.numel())
+        if size not in (None, hw) or n not in (None, src.shape[0]):
+            raise ValueError(f"collage_rows_u8: panels differ in output size or image count ({size} / {hw}, {n} / {src.shape[0]})")
+        size, n = hw, src.shape[0]
+        d.src, d.image_stride, d.row_pitch, d.src_h, d.src_w = src.data_ptr(), src.stride(0), src.stride(1), src.shape[1], src.shape[2]
+        d.is_f32, d.yi, d.xi = int(src.dtype == torch.float32), None if yi is None else yi.data_ptr(), None if xi is None else xi.data_ptr()
+        keep.append((src, yi, xi))
+    h, w = size
+    if row0 < 0 or (row0 + n) * h > canvas.shape[0] or len(panels) * w > canvas.shape[1]:
+        raise ValueError(f"collage_rows_u8: {n} rows of {len(panels)} panels {h} x {w} from row {row0} do not fit a canvas {tuple(canvas.shape)}")
+    pitch = canvas.stride(0) if canvas.shape[0] > 1 else canvas.shape[1]
+    L.check(L.lib().pssr_collage_rows_u8(C.cast(descs, C.c_void_p), len(panels), L.ptr(canvas), pitch, row0, n, h, w, L.stream_ptr()),
+            "pssr_collage_rows_u8")
+    return canvas
+
+
 def normalize_preds_u8(hr, hr_hat, pmin=0.1, pmax=99.9):
     """uint8 device tensors [..., H, W] of equal shape -> (hr_norm, hr_hat_norm) uint8, as pssr.util.normalize_preds (bit-exact)."""
     if hr.dtype != torch.uint8 or hr_hat.dtype != torch.uint8 or hr.shape != hr_hat.shape or not hr.is_cuda:

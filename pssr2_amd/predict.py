@@ -1,5 +1,6 @@
 """``predict_images`` with the reference's signature (pssr/predict.py:11-83): batched no-grad forward,
-clip + uint8 truncation on the device (csrc/elementwise.hip: pssr_clip_u8), crop, dict or file output."""
+clip + uint8 truncation on the device (csrc/elementwise.hip: pssr_clip_u8), crop, dict or file output; ``predict_collage``
+(pssr/predict.py:85-142) with its picture composed in HBM (csrc/collage.hip: pssr_collage_rows_u8); ``predict_sheet``; ``test_metrics``."""
 from __future__ import annotations
 
 import os
@@ -125,6 +126,101 @@ def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batc
             cur_idx += batch_size
     if out_dir is None:
         return outs
+
+
+def _center_crop_view(t: torch.Tensor, rows: int, cols: int):
+    """[1, rows', cols'] view of the centre frame ``C // 2`` of a [1, C, H, W] tensor cut to at most ``rows`` x ``cols`` (numpy slicing:
+    a smaller image stays as it is), without a copy."""
+    return t[:, t.shape[1] // 2, :rows, :cols]
+
+
+def _collage_row(canvas: torch.Tensor, row: int, lr: torch.Tensor, hr_hat: torch.Tensor, hr, norm: bool, crop_res: int, lr_scale: int):
+    """One collage row on the device: ``_collage_preds(lr, hr_hat, hr, norm, 1, crop_res, lr_scale)`` (pssr/predict.py:213-232) written
+    into rows ``row * crop_res ...`` of the uint8 device ``canvas``.  ``lr`` / ``hr_hat`` / ``hr`` (None in LR mode): float32 device
+    tensors [1, C, H, W].  Centre frame of each, LR cut to ``crop_res // lr_scale`` and prediction / HR to ``crop_res``; with ``norm``
+    prediction and HR go through ``normalize_preds`` and LR through ``normalize_preds`` against the normalised HR (all three stay in
+    HBM); LR is enlarged to the prediction's size by Pillow's NEAREST map; one ``pssr_collage_rows_u8`` launch places the panels.
+    Without ``norm`` that launch reads the float32 tensors directly (clip + truncation as ``_pred_array``)."""
+    tensors = [lr, hr_hat] + ([] if hr is None else [hr])
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("pssr2_amd.predict runs on an MI355X (HIP) device only; there is no CPU fallback")
+        if t.dim() != 4 or t.shape[0] != 1:
+            raise ValueError(f"_collage_row takes single items [1, C, H, W], got {tuple(t.shape)}")
+    views = [_center_crop_view(t.detach().float(), res, res) for t, res in zip(tensors, [crop_res // lr_scale, crop_res, crop_res])]
+    h, w = views[1].shape[1:]
+    if hr is not None and views[2].shape != views[1].shape:
+        raise ValueError(f"Cropped prediction and high-resolution image differ in size ({tuple(views[1].shape[1:])} and "
+                         f"{tuple(views[2].shape[1:])}): the model's scale does not match the dataset's lr_scale. (The reference resizes "
+                         "and pastes such panels; pssr2_amd does not.)")
+    if (h, w) != (crop_res, crop_res):
+        raise ValueError(f"The cropped prediction is {h}x{w} but a collage row is crop_res = {crop_res} pixels high and each panel as wide.")
+    if norm:
+        u8 = []
+        for v in views:
+            v = v.contiguous()
+            out = torch.empty(v.shape, dtype=torch.uint8, device=v.device)
+            ops.clip_u8(v, out)
+            u8.append(out)
+        lr_u8, hat_u8, hr_u8 = u8
+        hr_u8, hat_u8 = ops.normalize_preds_u8(hr_u8, hat_u8)
+        if lr_u8.shape == hr_u8.shape:
+            _, lr_u8 = ops.normalize_preds_u8(hr_u8, lr_u8)
+        else:
+            _, lr_u8 = ops.normalize_preds_resized_u8(hr_u8, lr_u8)
+        views = [lr_u8, hat_u8, hr_u8]
+    sh, sw = views[0].shape[1:]
+    tables = (None, None) if (sh, sw) == (h, w) else (ops.nearest_table(sh, h, canvas.device), ops.nearest_table(sw, w, canvas.device))
+    ops.collage_rows_u8([(views[0], *tables)] + views[1:], canvas, row)
+
+
+def predict_collage(model: nn.Module, dataset: Dataset, device: str = "cpu", norm: bool = True, n_images: int = None, prefix: str = None,
+                    out_dir: str = "preds", callbacks=None):
+    r"""Saves ``{out_dir}/{prefix_}collage_{n_images}.png``: vertically stacked rows of the low-resolution input (enlarged, nearest
+    neighbour), the prediction and the high-resolution image side by side (pssr/predict.py:85-142: same arguments, order of the
+    images, file name and pixel values).  In LR mode there is no high-resolution panel.  Only the centre frame of each item is shown;
+    only validation images are used; rows for which no validation item exists stay black.
+
+    Items are predicted one by one as upstream.  Clipping, (``norm``) the two ``normalize_preds`` passes, the nearest-neighbour
+    enlargement and the placement of the panels run on the MI355X (csrc/collage.hip); the canvas lives in HBM and comes to the host
+    once, to be saved through Pillow as mode ``"L"``.
+
+    Two deviations: upstream's callback loop overwrites the row counter that ends its outer loop, so with callbacks it may stop early
+    or late; here the loop ends after ``n_images`` rows whatever the callbacks.  And ``collage`` in the locals a callback receives is
+    the uint8 device canvas, not a PIL image.  Panels of different sizes (a model whose scale is not the dataset's ``lr_scale``) raise
+    ``ValueError``; upstream pastes them as they are."""
+    if norm and dataset.is_lr:
+        raise ValueError("Dataset must be paired with high-low-resolution images for normalization.")
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("pssr2_amd.predict runs on an MI355X (HIP) device only; there is no CPU fallback")
+    from .data import _RandomIterIdx
+    callbacks, callback_locals = _get_callbacks(callbacks)
+    n_images = min(50, len(dataset)) if n_images is None else n_images
+
+    model.to(device)
+    model.eval()
+
+    crop_res = dataset.crop_res
+    collage = torch.zeros(crop_res * n_images, crop_res * (2 if dataset.is_lr else 3), dtype=torch.uint8, device=device)
+    with torch.no_grad():
+        # only shuffled if val_split < 1 (pssr/predict.py:119-120)
+        order = _RandomIterIdx(dataset.val_idx, seed=True) if len(dataset.val_idx) < len(dataset) else dataset.val_idx
+        for idx, data_idx in enumerate(order):
+            if idx >= n_images:
+                break
+            if dataset.is_lr:
+                hr, lr = None, dataset[data_idx].to(device).unsqueeze(0)
+            else:
+                hr, lr = dataset[data_idx]
+                hr, lr = hr.to(device).unsqueeze(0), lr.to(device).unsqueeze(0)
+            hr_hat = model(lr)
+            _collage_row(collage, idx, lr, hr_hat, hr, norm, crop_res, dataset.lr_scale)
+            for i, callback in enumerate(callbacks):
+                callback(locals()) if callback_locals[i] else callback()
+
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    Image.fromarray(collage.cpu().numpy()).save(f"{out_dir}/{prefix + '_' if prefix else ''}collage_{n_images}.png")
 
 
 def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 32, margin: int = 0, batch_size: int = 128,
