@@ -456,6 +456,28 @@ typedef struct pssr_collage_panel {
 int pssr_collage_rows_u8(const pssr_collage_panel* panels, int n_panels, uint8_t* canvas, int64_t canvas_pitch, int row0, int n_images,
                          int h, int w, pssr_stream_t stream);
 
+/* Shifted-window attention of SwinIR (pssr/models/swinir.py:345-385 SwinTransformerBlock.forward, :563-594 WindowAttention.forward)
+ * on the un-rolled, un-windowed token tensor.  qkv [B, H, W, 3C] contiguous, channel which * C + head * hd + d (which = 0 q, 1 k,
+ * 2 v; hd = C / heads): the qkv Linear applied per token.  out [B, H, W, C], channel head * hd + d, original token order, dtype of
+ * qkv.  lse [B, heads, H, W] float32: the log-sum-exp of every query row.  Per (window, head):
+ *   S = (q * scale) k^T + bias_table[rel(i, j)] + mask(i, j),  P = softmax_j S,  O = P v,
+ * bias_table [(2 ws - 1)^2, heads] float32, rel(i, j) = (ri - rj + ws - 1) (2 ws - 1) + (ci - cj + ws - 1).  The cyclic shift
+ * (-shift, -shift), the window partition (row-major tokens inside a window), its reverse and the shift back are addressing; the mask
+ * of calculate_mask is computed from the coordinates: -100.0f is added where the regions of the two tokens differ and shift > 0.
+ * Takes 1 <= ws <= 8, H % ws == W % ws == 0, 0 <= shift < ws, C % heads == 0, hd <= 32, dtype PSSR_F32 or PSSR_BF16 (S, the softmax,
+ * all sums and lse in float32 for both); PSSR_ERR_ARG otherwise.  16-byte loads when hd * sizeof(element) is a multiple of 16 and the
+ * tensors are 16-byte aligned, element loads otherwise.
+ * Backward: P is recomputed from q, k and lse.  dqkv [B, H, W, 3C] (dtype of qkv) is written in full; dbias_table
+ * [(2 ws - 1)^2, heads] float32 is written (not accumulated): per-workgroup sums go to `workspace`
+ * (pssr_window_attn_workspace_bytes(...) bytes, 4-byte aligned) and a second launch adds them in a fixed order -- no atomics, the same
+ * bits on every run. */
+int64_t pssr_window_attn_workspace_bytes(int B, int H, int W, int heads, int ws);        /* negative = PSSR_ERR_ARG */
+int pssr_window_attn_fwd(const void* qkv, const float* bias_table, void* out, float* lse, int B, int H, int W, int C, int heads, int ws,
+                         int shift, float scale, int dtype, pssr_stream_t stream);
+int pssr_window_attn_bwd(const void* qkv, const float* bias_table, const float* lse, const void* dout, void* dqkv, float* dbias_table,
+                         void* workspace, int64_t workspace_bytes, int B, int H, int W, int C, int heads, int ws, int shift, float scale,
+                         int dtype, pssr_stream_t stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * Atrous / PSP-pooling model variants (pssr/models/_blocks.py:43-92 ResBlockA, PSP_Pooling).

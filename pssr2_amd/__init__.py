@@ -15,6 +15,9 @@ def __getattr__(name):
     if name in ("ResUNetA", "RDResUNetA"):
         from . import models
         return getattr(models, name)
+    if name in ("SwinIR",):
+        from .swinir import SwinIR
+        return SwinIR
     if name in ("SSIMLoss",):
         from .util import SSIMLoss
         return SSIMLoss

@@ -126,6 +126,11 @@ def lib():
                                                  c_void_p]
         _lib.pssr_gather_windows_u8.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]
         _lib.pssr_collage_rows_u8.argtypes = [c_void_p, c_int, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p]
+        # shifted-window attention (csrc/window_attn.hip)
+        _lib.pssr_window_attn_workspace_bytes.restype = c_i64
+        _lib.pssr_window_attn_workspace_bytes.argtypes = [c_int] * 5
+        _lib.pssr_window_attn_fwd.argtypes = [c_void_p] * 4 + [c_int] * 7 + [c_float, c_int, c_void_p]
+        _lib.pssr_window_attn_bwd.argtypes = [c_void_p] * 7 + [c_i64] + [c_int] * 7 + [c_float, c_int, c_void_p]
     return _lib
 
 

@@ -679,6 +679,55 @@ def collage_rows_u8(panels, canvas, row0=0):
     return canvas
 
 
+def window_attn_supported(dtype, h, w, c, heads, ws, shift=0):
+    """The shapes pssr_window_attn_fwd / _bwd take (include/pssr_mi355.h)."""
+    return (dtype in (torch.float32, torch.bfloat16) and 1 <= ws <= 8 and h % ws == 0 and w % ws == 0 and 0 <= shift < ws
+            and heads > 0 and c % heads == 0 and c // heads <= 32)
+
+
+def _window_attn_args(qkv, bias_table, heads):
+    if qkv.dim() != 4 or qkv.shape[3] % 3 or not qkv.is_cuda or not qkv.is_contiguous() or qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("window attention needs a contiguous float32 or bfloat16 device tensor qkv [B, H, W, 3C]")
+    if bias_table.dtype != torch.float32 or not bias_table.is_contiguous() or bias_table.device != qkv.device or bias_table.dim() != 2 \
+            or bias_table.shape[1] != heads:
+        raise ValueError("window attention needs a contiguous float32 bias_table [(2 ws - 1)^2, heads] on qkv's device")
+    b, h, w, c3 = qkv.shape
+    return b, h, w, c3 // 3
+
+
+def window_attn_fwd(qkv, bias_table, heads, ws, shift, scale):
+    """Shifted-window attention (pssr_window_attn_fwd): qkv [B, H, W, 3C] -> (out [B, H, W, C] in qkv's dtype, lse [B, heads, H, W]
+    float32).  Shapes are checked by the library (RuntimeError on PSSR_ERR_ARG)."""
+    b, h, w, c = _window_attn_args(qkv, bias_table, heads)
+    if bias_table.shape[0] != (2 * ws - 1) ** 2:
+        raise ValueError(f"bias_table has {bias_table.shape[0]} rows, window size {ws} needs {(2 * ws - 1) ** 2}")
+    out = torch.empty(b, h, w, c, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(b, heads, h, w, dtype=torch.float32, device=qkv.device)
+    L.check(L.lib().pssr_window_attn_fwd(L.ptr(qkv), L.ptr(bias_table), L.ptr(out), L.ptr(lse), b, h, w, c, heads, ws, shift, float(scale),
+                                         dtype_code(qkv.dtype), L.stream_ptr()), "pssr_window_attn_fwd")
+    return out, lse
+
+
+def window_attn_bwd(qkv, bias_table, lse, dout, heads, ws, shift, scale):
+    """Backward of ``window_attn_fwd`` (pssr_window_attn_bwd): -> (dqkv like qkv, dbias_table like bias_table).  No atomics: the same
+    bits on every call."""
+    b, h, w, c = _window_attn_args(qkv, bias_table, heads)
+    if bias_table.shape[0] != (2 * ws - 1) ** 2:
+        raise ValueError(f"bias_table has {bias_table.shape[0]} rows, window size {ws} needs {(2 * ws - 1) ** 2}")
+    if dout.shape != (b, h, w, c) or dout.dtype != qkv.dtype or dout.device != qkv.device or not dout.is_contiguous():
+        raise ValueError("window_attn_bwd: dout must be contiguous [B, H, W, C] with qkv's dtype and device")
+    if lse.shape != (b, heads, h, w) or lse.dtype != torch.float32 or lse.device != qkv.device or not lse.is_contiguous():
+        raise ValueError("window_attn_bwd: lse must be the contiguous float32 [B, heads, H, W] tensor window_attn_fwd returned")
+    dqkv = torch.empty_like(qkv)
+    dbias = torch.empty_like(bias_table)
+    nbytes = L.lib().pssr_window_attn_workspace_bytes(b, h, w, heads, ws)
+    work = torch.empty(max(int(nbytes), 4) // 4, dtype=torch.float32, device=qkv.device)
+    L.check(L.lib().pssr_window_attn_bwd(L.ptr(qkv), L.ptr(bias_table), L.ptr(lse), L.ptr(dout), L.ptr(dqkv), L.ptr(dbias), L.ptr(work),
+                                         work.numel() * 4, b, h, w, c, heads, ws, shift, float(scale), dtype_code(qkv.dtype), L.stream_ptr()),
+            "pssr_window_attn_bwd")
+    return dqkv, dbias
+
+
 def normalize_preds_u8(hr, hr_hat, pmin=0.1, pmax=99.9):
     """uint8 device tensors [..., H, W] of equal shape -> (hr_norm, hr_hat_norm) uint8, as pssr.util.normalize_preds (bit-exact)."""
     if hr.dtype != torch.uint8 or hr_hat.dtype != torch.uint8 or hr.shape != hr_hat.shape or not hr.is_cuda:
