@@ -511,13 +511,13 @@ def head_conv_fwd(act, blk, weight, bias, out, n, h, w, cin, cout, out_scale, ou
                                        C.c_float(out_scale), C.c_float(out_shift), dtype, L.stream_ptr()), "pssr_head_conv_fwd")
 
 
-def head_conv_dgrad(g, g_scale, weight, act, dact, blk, n, h, w, cin, cout, dtype):
-    L.check(L.lib().pssr_head_conv_dgrad(L.ptr(g), C.c_float(g_scale), L.ptr(weight), L.ptr(act), act.shape[-1], 0, L.ptr(dact), dact.shape[-1], 0,
+def head_conv_dgrad(g, g_scale, weight, act, dact, blk, n, h, w, cin, cout, dtype, *, act_coff=0, dact_coff=0):
+    L.check(L.lib().pssr_head_conv_dgrad(L.ptr(g), C.c_float(g_scale), L.ptr(weight), L.ptr(act), act.shape[-1], act_coff, L.ptr(dact), dact.shape[-1], dact_coff,
                                          blk, n, h, w, cin, cout, dtype, L.stream_ptr()), "pssr_head_conv_dgrad")
 
 
-def head_conv_wgrad(g, g_scale, act, blk, dw, n, h, w, cin, cout, dtype):
-    L.check(L.lib().pssr_head_conv_wgrad(L.ptr(g), C.c_float(g_scale), L.ptr(act), act.shape[-1], 0, blk, L.ptr(dw), n, h, w, cin, cout, dtype,
+def head_conv_wgrad(g, g_scale, act, blk, dw, n, h, w, cin, cout, dtype, *, act_coff=0):
+    L.check(L.lib().pssr_head_conv_wgrad(L.ptr(g), C.c_float(g_scale), L.ptr(act), act.shape[-1], act_coff, blk, L.ptr(dw), n, h, w, cin, cout, dtype,
                                          L.stream_ptr()), "pssr_head_conv_wgrad")
 
 
@@ -541,9 +541,9 @@ def patch_tiles_u8(tiles, n_rows, n_cols, overlap, margin):
     return out
 
 
-def head_conv_bwd(g, g_scale, weight, act, dact, blk, dw, bias_sum, n, h, w, cin, cout, dtype):
+def head_conv_bwd(g, g_scale, weight, act, dact, blk, dw, bias_sum, n, h, w, cin, cout, dtype, *, act_coff=0, dact_coff=0):
     """dgrad + wgrad (+ the bias sums of the pixel-shuffle conv in front) in one pass over the activation."""
-    L.check(L.lib().pssr_head_conv_bwd(L.ptr(g), C.c_float(g_scale), L.ptr(weight), L.ptr(act), act.shape[-1], 0, L.ptr(dact), dact.shape[-1], 0,
+    L.check(L.lib().pssr_head_conv_bwd(L.ptr(g), C.c_float(g_scale), L.ptr(weight), L.ptr(act), act.shape[-1], act_coff, L.ptr(dact), dact.shape[-1], dact_coff,
                                        blk, L.ptr(dw), L.ptr(bias_sum), n, h, w, cin, cout, dtype, L.stream_ptr()), "pssr_head_conv_bwd")
 
 
@@ -557,9 +557,10 @@ def head_q_gather(q, bias, out, n, h, w, out_scale, out_shift):
             "pssr_head_q_gather")
 
 
-def head_conv_bwd_rows(g, g_scale, weight, act, dact, blk, dw_rows, bias_rows, n, h, w, cin, cout, dtype):
-    """head_conv_bwd with order-independent sums: dw_rows / bias_rows are zeroed f64 [STAT_STRIPES (rows)][...] buffers, folded by f64_to_f32."""
-    L.check(L.lib().pssr_head_conv_bwd_rows(L.ptr(g), C.c_float(g_scale), L.ptr(weight), L.ptr(act), act.shape[-1], 0, L.ptr(dact), dact.shape[-1], 0,
+def head_conv_bwd_rows(g, g_scale, weight, act, dact, blk, dw_rows, bias_rows, n, h, w, cin, cout, dtype, *, act_coff=0, dact_coff=0):
+    """head_conv_bwd with order-independent sums: dw_rows / bias_rows are zeroed f64 buffers of PSSR_STAT_ROWS = 64 rows ([STAT_STRIPES][cout * cin * 9]
+    and [STAT_STRIPES][4^blk * cin]: 32 workgroup stripes of multiple-of-2^-20 pieces, then their 32 remainder rows), folded by f64_to_f32."""
+    L.check(L.lib().pssr_head_conv_bwd_rows(L.ptr(g), C.c_float(g_scale), L.ptr(weight), L.ptr(act), act.shape[-1], act_coff, L.ptr(dact), dact.shape[-1], dact_coff,
                                             blk, L.ptr(dw_rows), L.ptr(bias_rows), n, h, w, cin, cout, dtype, L.stream_ptr()), "pssr_head_conv_bwd_rows")
 
 

@@ -10,7 +10,9 @@ arithmetic on such grids and fails when an intermediate value could need more th
 from __future__ import annotations
 
 import contextlib
+import functools
 import re
+from pathlib import Path
 from typing import NamedTuple
 
 import pytest
@@ -205,17 +207,187 @@ def is_conv_kernel(parsed):
     return parsed is not None and parsed[0].startswith("conv_") and parsed[0].endswith("_kernel")
 
 
-def launched_kernels(fn):
-    """Run fn() under torch.profiler; returns (its result, the sorted (family, ints) of this library's convolution kernels that ran).
-    Fails -- never skips -- when the profiler reports none."""
+def is_head_kernel(parsed):
+    """the templated kernels of csrc/head_conv.hip (the two head_q_gather kernels have no template arguments: see plain_kernel_names)"""
+    return parsed is not None and parsed[0].startswith("head_") and parsed[0].endswith("_kernel")
+
+
+_SYMBOL = re.compile(rb"_ZN[0-9A-Za-z_]*?_kernelI[0-9A-Za-z_]+")
+
+
+def kernel_name_table(symbols, demangle):
+    """{name as a profiler may report it: (family, ints)} for mangled kernel symbols.  A profiler reports a kernel under its mangled
+    name or under what its demangler makes of it, and an old demangler garbles some names beyond parsing: it reads the `DF16b` of
+    __bf16 followed by a small integer literal as a fixed-point type (head_fwd_kernel<__bf16, 1, 1> comes out as
+    head_fwd_kernel<bool _Accum, int, E, 1>).  So every symbol is passed through the same demangler and looked up by the result; a
+    name that two different kernels share maps to None."""
+    table = {}
+    for s in symbols:
+        p = parse_kernel_name(s)
+        if p is None:
+            continue
+        for name in {s, demangle(s)}:
+            if table.setdefault(name, p) != p:
+                table[name] = None
+    return table
+
+
+@functools.lru_cache(maxsize=None)
+def library_kernel_table():
+    """kernel_name_table of the template kernels in the built library, through this process's demangler"""
+    from pssr2_amd import _lib as L
+    data = Path(L._LIB_PATH).read_bytes()
+    return kernel_name_table(sorted({m.group(0).decode() for m in _SYMBOL.finditer(data)}), torch._C._demangle)
+
+
+def launched_kernels(fn, select=is_conv_kernel):
+    """Run fn() under torch.profiler; returns (its result, the sorted (family, ints) of this library's kernels that ran and that the
+    predicate `select` accepts: the convolution kernels unless told otherwise).  Fails -- never skips -- when the profiler reports none."""
     from torch.profiler import ProfilerActivity, profile
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
         res = fn()
         torch.cuda.synchronize()
     names = [e.name for e in prof.events()]
-    ks = sorted(p for p in (parse_kernel_name(n) for n in names) if is_conv_kernel(p))
-    assert ks, f"the profiler reported no convolution kernel of this library (events: {sorted(set(names))[:20]})"
+    table = library_kernel_table()
+    parsed = []
+    for n in names:
+        assert table.get(n, ()) is not None, f"the profiler's name {n!r} stands for more than one kernel of the library"
+        parsed.append(table[n] if n in table else parse_kernel_name(n))
+    ks = sorted(p for p in parsed if select(p))
+    assert ks, f"the profiler reported no selected kernel of this library (events: {sorted(set(names))[:20]})"
     return res, ks
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the Reconstruction head (csrc/head_conv.hip): grids, premise, references
+HEAD_TS = 16                    # tile edge of every head kernel
+HEAD_BWD_GRID, HEAD_WGRAD_GRID = 512, 1024      # workgroup caps of the persistent kernels (head_conv_bwd_impl, pssr_head_conv_wgrad)
+STAT_ROWS, STAT_HI_ROWS = 64, 32                # PSSR_STAT_ROWS; rows [0, 32) hold the multiple-of-2^-20 pieces, [32, 64) the remainders
+
+
+def scaled(g: Grid, s: float) -> Grid:
+    """The grid of g's values times the exact scalar s = k * 2**j (k an odd integer).  The significant bits are counted, not
+    magnitude / step: a power of two shifts the exponent (k = 1, units() unchanged), any other scale costs the bits of k."""
+    assert s != 0 and s == float(s)
+    k, j = abs(float(s)), 0
+    while k != int(k):
+        k, j = k * 2, j - 1
+    while int(k) % 2 == 0:
+        k, j = k / 2, j + 1
+    return Grid(g.e - j, g.m * abs(s))
+
+
+def head_weight_grid(dt) -> Grid:
+    """head weights: (storage bits - 1) fractional bits in [-1/2, 1/2] -- exactly representable, and the products need rounding often"""
+    return Grid(STORAGE_BITS[dt] - 1, 0.5)
+
+
+class HeadGrids(NamedTuple):
+    out: Grid       # forward output (conv + bias) * 128 + 128
+    dP: Grid        # data gradient before the 16-bit store
+    dW: Grid        # weight gradient (without the pre-existing gradient)
+
+
+def assert_head_premise(cin, cout, pixels, g_scale, *, dt, x=X_GRID, g=X_GRID, bias=B_GRID) -> HeadGrids:
+    """Walk the arithmetic of the head kernels on the grids of the tests: activations x, weights head_weight_grid(dt), gradient g times
+    g_scale (an f32 product, then -- dgrad, fused backward -- converted to dt), `pixels` = n * h * w terms per weight-gradient sum."""
+    w = head_weight_grid(dt)
+    out = assert_exact_premise(9 * cin, x, w, dt=torch.float32, bias=bias, final=(Grid(-7, 128.0), Grid(-7, 128.0)))
+    _storable(x, dt, "activation")
+    _storable(w, dt, "weight")
+    gs = scaled(g, g_scale)
+    _fits(gs, F32_BITS, "g * g_scale")
+    _storable(gs, dt, "g * g_scale")
+    dP = (gs * w).sum(9 * cout)
+    _fits(dP, F32_BITS, "dP accumulator")
+    if dt == torch.float16:
+        assert dP.m <= F16_MAX, f"dP {dP} overflows float16"
+    dW = (gs * x).sum(pixels)
+    _fits(dW, F32_BITS, f"dW accumulator ({pixels} pixels)")
+    return HeadGrids(out, dP, dW)
+
+
+def stored_grid(g: Grid, dt) -> Grid:
+    """the grid of g's values after the 16-bit store: still multiples of g's step, the largest magnitude rounded like any other"""
+    return Grid(g.e, float(torch.tensor(g.m, dtype=torch.float64).to(dt)))
+
+
+def assert_headq_premise(k, x: Grid, w: Grid, b: Grid, hw: Grid, hb: Grid, *, dt):
+    """The fused head of `pre` (conv_headq_epilogue + pssr_head_q_gather): relu(acc + b) of a convolution with dot products of length
+    k, rounded to dt; times the head weights hw (converted to dt), summed over the 64 channels of a sub-pixel in f32 (a tap plane);
+    nine planes and the head bias hb summed, * 128 + 128.  Returns the grids (activation, tap plane, output)."""
+    acc = assert_exact_premise(k, x, w, dt=dt, bias=b)
+    act = stored_grid(acc, dt)
+    _storable(hw, dt, "head weight")
+    plane = (act * hw).sum(64)
+    _fits(plane, F32_BITS, "tap plane")
+    out = plane.sum(9) + hb
+    _fits(out, F32_BITS, "gathered sum + bias")
+    out = out * Grid(-7, 128.0) + Grid(-7, 128.0)
+    _fits(out, F32_BITS, "output")
+    return act, plane, out
+
+
+def sum_fits(g: Grid, count) -> bool:
+    """an f32 sum of `count` values of grid g is exact whatever its order"""
+    return g.sum(count).units() <= 2.0 ** F32_BITS
+
+
+def needs_rounding(ref: torch.Tensor, dt) -> float:
+    """share of the float64 values that the storage type cannot hold (the 16-bit store has to round them)"""
+    return float((ref.to(dt).double() != ref).double().mean())
+
+
+def storage_ulp(ref: torch.Tensor, dt) -> torch.Tensor:
+    """spacing of the storage type at |ref| (float64), the subnormal spacing below the smallest normal number"""
+    emin = {torch.bfloat16: -126, torch.float16: -14, torch.float32: -126}[dt]
+    _, e = torch.frexp(ref.abs().clamp_min(2.0 ** emin))          # |ref| = m 2^e, m in [0.5, 1)
+    return torch.exp2((e - STORAGE_BITS[dt]).double())
+
+
+def head_refs(act, wt, g):
+    """float64 references of the three head operations on NCHW / OIHW float64 operands (g already scaled): the 3x3 convolution of
+    act, the data gradient (no mask) and the weight gradient"""
+    import torch.nn.functional as F
+    conv = F.conv2d(act, wt, padding=1)
+    dP = F.conv_transpose2d(g, wt, padding=1)
+    dW = torch.nn.grad.conv2d_weight(act, wt.shape, g, padding=1)
+    return conv, dP, dW
+
+
+def head_tiles(n, h, w):
+    tx, ty = -(-w // HEAD_TS), -(-h // HEAD_TS)
+    return n * ty * tx, ty, tx
+
+
+def later_trip_mask(n, h, w, grid):
+    """[n, 1, h, w] mask of the pixels in tiles whose index (img, tile row, tile column) is >= grid: the tiles a persistent kernel of
+    `grid` workgroups reaches on its second and later trips"""
+    _, ty, tx = head_tiles(n, h, w)
+    img = torch.arange(n).view(n, 1, 1)
+    yy = (torch.arange(h) // HEAD_TS).view(1, h, 1)
+    xx = (torch.arange(w) // HEAD_TS).view(1, 1, w)
+    return (((img * ty + yy) * tx + xx) >= grid).view(n, 1, h, w)
+
+
+def fold_stat_rows(rows: torch.Tensor, addends: int) -> torch.Tensor:
+    """rows: float64 [STAT_ROWS, ...] as stat_add (csrc/common.h) leaves them, every slot having received at most `addends` values.
+    Checks the two pieces -- rows [0, 32) multiples of 2^-20, rows [32, 64) multiples of 2^-64 of magnitude below 2^-21 per addend --
+    and returns the float64 sum over the rows."""
+    r = rows.detach().cpu().reshape(STAT_ROWS, -1)
+    hi, lo = r[:STAT_HI_ROWS], r[STAT_HI_ROWS:]
+    assert torch.equal(hi * 2.0 ** 20, (hi * 2.0 ** 20).round()), "a stripe row holds something finer than 2^-20"
+    assert torch.equal(lo * 2.0 ** 64, (lo * 2.0 ** 64).round()), "a remainder row holds something finer than 2^-64"
+    assert float(lo.abs().max()) <= addends * 2.0 ** -21, "a remainder row holds more than its addends can bring"
+    return r.sum(0).reshape(rows.shape[1:])
+
+
+def mask_edge_values(dt):
+    """activations around the ReLU mask's decision, built from their bit patterns: +0, -0, +-smallest subnormal, +-smallest normal,
+    -1, +1, largest finite"""
+    bits = {torch.bfloat16: [0x0000, 0x8000, 0x0001, 0x8001, 0x0080, 0x8080, 0xBF80, 0x3F80, 0x7F7F],
+            torch.float16: [0x0000, 0x8000, 0x0001, 0x8001, 0x0400, 0x8400, 0xBC00, 0x3C00, 0x7BFF]}[dt]
+    return torch.tensor([b - 65536 if b >= 32768 else b for b in bits], dtype=torch.int16).view(dt)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

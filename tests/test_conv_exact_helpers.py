@@ -6,8 +6,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _conv_exact import (B_GRID, PRODUCTION_TUNABLES, SCALE_GRID, SHIFT_GRID, W_GRID, X_GRID, Grid, assert_exact_premise, dyadic,
-                         expected, from_blocked, parse_kernel_name, pix_index, shuf2_perm, to_blocked)
+from _conv_exact import (B_GRID, PRODUCTION_TUNABLES, SCALE_GRID, SHIFT_GRID, STAT_ROWS, W_GRID, X_GRID, Grid, assert_exact_premise,
+                         assert_head_premise, assert_headq_premise, dyadic, expected, fold_stat_rows, from_blocked, head_refs, head_tiles,
+                         head_weight_grid, is_conv_kernel, is_head_kernel, kernel_name_table, later_trip_mask, mask_edge_values, needs_rounding,
+                         parse_kernel_name, pix_index, scaled, shuf2_perm, storage_ulp, stored_grid, sum_fits, to_blocked)
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -119,3 +121,131 @@ def test_production_tunables_match_the_table_defaults():
         assert table[k] == v, (k, table[k], v)
     conv = {k for k in table if k.startswith(("IGEMM_", "CONV_", "WGRAD_")) and k != "IGEMM_DBG"}
     assert conv == set(PRODUCTION_TUNABLES), conv ^ set(PRODUCTION_TUNABLES)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the helpers of tests/test_gpu_head_exact.py
+def test_scaled_counts_significant_bits():
+    # a power of two shifts the exponent: 128 g keeps the three bits of g and stays storable in bf16
+    assert scaled(X_GRID, 128.0) == Grid(-5, 128.0) and scaled(X_GRID, 128.0).units() == X_GRID.units()
+    assert scaled(X_GRID, 0.25) == Grid(4, 0.25)
+    # 1.5 = 3 * 2^-1 costs the bits of 3
+    assert scaled(X_GRID, 1.5) == Grid(3, 1.5) and scaled(X_GRID, 1.5).units() == 12
+    assert scaled(X_GRID, -3.0) == Grid(2, 3.0)
+    g = torch.Generator().manual_seed(2)
+    for s in (128.0, 1.5, 0.375):
+        v = dyadic(g, (512,), X_GRID) * s
+        q = v * 2.0 ** scaled(X_GRID, s).e
+        assert torch.equal(q, q.round()) and float(v.abs().max()) <= scaled(X_GRID, s).m
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+def test_head_premise_holds_at_the_sizes_of_the_tests_and_fails_beyond(dt):
+    w = head_weight_grid(dt)
+    g = torch.Generator().manual_seed(3)
+    assert torch.equal(dyadic(g, (4096,), w).to(dt).double(), dyadic(torch.Generator().manual_seed(3), (4096,), w))    # storable
+    for gs in (128.0, 1.5):
+        grids = assert_head_premise(128, 3, 528 * 512, gs, dt=dt)
+        assert max(grids.out.units(), grids.dP.units(), grids.dW.units()) <= 2 ** 24
+    with pytest.raises(AssertionError, match="premise"):
+        assert_head_premise(128, 3, 4 * 528 * 512, 1.5, dt=dt)              # too many pixels for an exact f32 dW
+    with pytest.raises(AssertionError, match="premise"):
+        assert_head_premise(32, 1, 256, 1.0 + 2.0 ** -9, dt=dt)             # g * g_scale does not survive the conversion to 16 bits
+    # the stored dP keeps its step; few of them sum exactly, many do not
+    dP = stored_grid(assert_head_premise(32, 1, 256, 1.5, dt=dt).dP, dt)
+    assert dP.e == scaled(X_GRID, 1.5).e + w.e and dP.m == 6.75
+    assert sum_fits(dP, 16) and not sum_fits(dP, 1 << 20)
+
+
+def test_headq_premise():
+    ok = (Grid(1, 1.0), Grid(2, 0.5), Grid(3, 64.0), Grid(5, 0.5), B_GRID)
+    act, plane, out = assert_headq_premise(288, *ok, dt=torch.bfloat16)
+    assert act.units() > 2 ** 8 and out.units() <= 2 ** 24           # the activation needs rounding, the output is exact
+    with pytest.raises(AssertionError, match="premise"):
+        assert_headq_premise(288, X_GRID, W_GRID, B_GRID, head_weight_grid(torch.bfloat16), B_GRID, dt=torch.bfloat16)
+
+
+def test_head_references_against_autograd():
+    g = torch.Generator().manual_seed(4)
+    act = dyadic(g, (2, 5, 6, 7), X_GRID).requires_grad_(True)
+    wt = dyadic(g, (3, 5, 3, 3), W_GRID).requires_grad_(True)
+    dy = dyadic(g, (2, 3, 6, 7), X_GRID)
+    out = F.conv2d(act, wt, padding=1)
+    out.backward(dy)
+    conv, dP, dW = head_refs(act.detach(), wt.detach(), dy)
+    assert torch.equal(conv, out.detach()) and torch.equal(dP, act.grad) and torch.equal(dW, wt.grad)
+
+
+@pytest.mark.parametrize("dt,bits", [(torch.bfloat16, 8), (torch.float16, 11)])
+def test_rounding_share_and_storage_ulp(dt, bits):
+    u = 2.0 ** (1 - bits)
+    ref = torch.tensor([1.0, 1 + u, 1 + u / 2, 3.0, 0.0, 2 + u], dtype=torch.float64)
+    assert needs_rounding(ref, dt) == 2 / 6
+    assert storage_ulp(torch.tensor([1.0, 1.5, 2.0, -4.0, 0.75], dtype=torch.float64), dt).tolist() == [u, u, 2 * u, 4 * u, u / 2]
+    tiny = 2.0 ** (-126 if dt == torch.bfloat16 else -14)
+    assert storage_ulp(torch.tensor([0.0, tiny / 4], dtype=torch.float64), dt).tolist() == [tiny * u, tiny * u]
+
+
+def test_later_trip_mask_marks_the_tiles_beyond_the_grid():
+    assert head_tiles(1, 368, 368) == (529, 23, 23) and head_tiles(3, 17, 33) == (18, 2, 3)
+    m = later_trip_mask(2, 20, 36, 7)                       # tiles (img, ty, tx) in 2 x 2 x 3, index 7 = image 1, row 0, column 1
+    assert m.shape == (2, 1, 20, 36) and not bool(m[0].any())
+    assert not bool(m[1, 0, :16, :16].any()) and bool(m[1, 0, :16, 16:].all()) and bool(m[1, 0, 16:].all())
+    assert int(later_trip_mask(1, 368, 368, 512).sum()) == 17 * 256
+
+
+def test_fold_stat_rows_checks_the_two_pieces():
+    rows = torch.zeros(STAT_ROWS, 3, dtype=torch.float64)
+    rows[1, 0], rows[33, 0] = 5 * 2.0 ** -20, 3 * 2.0 ** -64
+    rows[7, 2], rows[39, 2] = -2.0, -(2.0 ** -21)
+    assert fold_stat_rows(rows, 1).tolist() == [5 * 2.0 ** -20 + 3 * 2.0 ** -64, 0.0, -2.0 - 2.0 ** -21]
+    bad = rows.clone()
+    bad[2, 1] = 2.0 ** -21
+    with pytest.raises(AssertionError, match="finer than 2\\^-20"):
+        fold_stat_rows(bad, 1)
+    bad = rows.clone()
+    bad[40, 1] = 2.0 ** -20
+    with pytest.raises(AssertionError, match="more than its addends"):
+        fold_stat_rows(bad, 1)
+    fold_stat_rows(bad, 2)
+    bad = rows.clone()
+    bad[40, 1] = 2.0 ** -70
+    with pytest.raises(AssertionError, match="finer than 2\\^-64"):
+        fold_stat_rows(bad, 1)
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+def test_mask_edge_values(dt):
+    v = mask_edge_values(dt)
+    fi = torch.finfo(dt)
+    sub = fi.smallest_normal * fi.eps
+    assert v.dtype == dt and v.double().tolist() == [0.0, -0.0, sub, -sub, fi.smallest_normal, -fi.smallest_normal, -1.0, 1.0, fi.max]
+    assert (v.double() > 0).tolist() == [False, False, True, False, True, False, False, True, True]
+    assert torch.signbit(v.float())[1] and not torch.signbit(v.float())[0]
+
+
+def test_head_kernel_names_and_predicates():
+    bwd = parse_kernel_name("_ZN12_GLOBAL__N_115head_bwd_kernelI14__hip_bfloat16Li4ELb1ELb0EEEvNS_8HeadArgsEiPfPjPdS4_")
+    assert bwd == ("head_bwd_kernel", (4, 1, 0)) and is_head_kernel(bwd) and not is_conv_kernel(bwd)
+    assert parse_kernel_name("void (anonymous namespace)::head_bwd_kernel<_Float16, 8, false, true>(HeadArgs, int, float*)") == \
+        ("head_bwd_kernel", (8, 0, 1))
+    assert parse_kernel_name("_ZN12_GLOBAL__N_115head_fwd_kernelIDF16_Li2ELi3EEEvNS_8HeadArgsE") == ("head_fwd_kernel", (2, 3))
+    assert parse_kernel_name("_ZN12_GLOBAL__N_117head_wgrad_kernelIDF16bLi3EEEvNS_8HeadArgsEi") == ("head_wgrad_kernel", (3,))
+    conv = parse_kernel_name("conv_igemm_kernel<__hip_bfloat16, 64, 0, 9>")
+    assert is_conv_kernel(conv) and not is_head_kernel(conv) and not is_head_kernel(None)
+    assert not is_head_kernel(parse_kernel_name("_ZN12_GLOBAL__N_120head_q_gather4_kernelEPKfS1_Pfiiiff"))
+
+
+def test_kernel_name_table_survives_a_demangler_that_garbles_names():
+    a = "_ZN12_GLOBAL__N_115head_fwd_kernelIDF16bLi1ELi1EEEvNS_8HeadArgsE"
+    b = "_ZN12_GLOBAL__N_115head_fwd_kernelIDF16bLi2ELi1EEEvNS_8HeadArgsE"
+    c = "_ZN12_GLOBAL__N_115head_fwd_kernelIDF16_Li2ELi1EEEvNS_8HeadArgsE"
+    garbled = {a: "void (anonymous namespace)::head_fwd_kernel<bool _Accum, int, E, 1>((anonymous namespace)::HeadArgs)",
+               b: "void (anonymous namespace)::head_fwd_kernel<bool _Accum, int, EL, int, E>((anonymous namespace)::HeadArgs)"}
+    assert parse_kernel_name(garbled[a]) == ("head_fwd_kernel", (1,))           # what the parser alone makes of it: wrong
+    t = kernel_name_table([a, b, c, "_ZN3foo3barEv"], lambda s: garbled.get(s, s))
+    assert t[garbled[a]] == t[a] == ("head_fwd_kernel", (1, 1)) and t[garbled[b]] == t[b] == ("head_fwd_kernel", (2, 1))
+    assert t[c] == ("head_fwd_kernel", (2, 1)) and "_ZN3foo3barEv" not in t
+    # two kernels under one reported name: marked, so that launched_kernels fails instead of guessing
+    assert kernel_name_table([a, b], lambda s: "head_fwd_kernel<E>")["head_fwd_kernel<E>"] is None
+    assert kernel_name_table([b, c], lambda s: "head_fwd_kernel<2, 1>")["head_fwd_kernel<2, 1>"] == ("head_fwd_kernel", (2, 1))
