@@ -30,6 +30,9 @@ def __getattr__(name):
     if name in ("approximate_crappifier",):
         from .train import approximate_crappifier
         return approximate_crappifier
+    if name in ("ArrayDataset", "ImageDataset", "DeviceTileDataset"):
+        from . import data
+        return getattr(data, name)
     if name in ("PairedArrayDataset", "PairedImageDataset", "DevicePairedTileDataset"):
         from . import data
         return getattr(data, name)

@@ -185,22 +185,59 @@ class _RandomIterIdx:
 
 
 # --------------------------------------------------------------------------------------- datasets
+def _tile_stacks(images, who, keep_tensors=False):
+    """The stacks of a tile dataset: one uint8 array / tensor [N, C, H, W] (``[N, H, W]``: one frame each) as it came, or a sequence of uint8
+    stacks [C_i, H_i, W_i] (2-D: one frame) of any depths and sizes -- stacked into one array when every shape agrees, else a list."""
+    if torch.is_tensor(images):
+        single = images if keep_tensors else images.cpu().numpy()
+    elif isinstance(images, np.ndarray) and images.dtype != object:
+        single = images
+    else:
+        stacks = [s if torch.is_tensor(s) and keep_tensors else (s.cpu().numpy() if torch.is_tensor(s) else np.asarray(s)) for s in images]
+        if len(stacks) and len({tuple(s.shape) for s in stacks}) == 1:
+            single = torch.stack(stacks) if torch.is_tensor(stacks[0]) else np.stack(stacks)
+        else:
+            stacks = [s[None] if s.ndim == 2 else s for s in stacks]
+            if any(s.ndim != 3 or str(s.dtype).split(".")[-1] != "uint8" for s in stacks):
+                raise ValueError(f"{who} expects uint8 images")
+            return stacks
+    if single.ndim == 3:
+        single = single[:, None]
+    if str(single.dtype).split(".")[-1] != "uint8":
+        raise ValueError(f"{who} expects uint8 images")
+    return single
+
+
+def _stack_shapes(images):
+    """(frames, H, W) per file of what ``_tile_stacks`` returned."""
+    return [tuple(s.shape) for s in images] if isinstance(images, list) else [tuple(images.shape[1:])] * len(images)
+
+
+def _stack_slices(shapes, n_frames):
+    """Frame slices per file (pssr/data.py:70-74): 1 with ``n_frames=-1``, else ``frames // max(n_frames)`` -- none for a file that is too shallow."""
+    return [1 if n_frames is None else s[0] // max(n_frames) for s in shapes]
+
+
+def _max_extent(shapes):
+    return max((max(s[-2:]) for s in shapes), default=0)
+
+
 class ArrayDataset(Dataset):
-    """In-memory HR stacks (uint8 [N, C, H, W]) with the attribute protocol the drivers consume
-    (``val_idx``, ``extra_hr_files``, ``crop_res``, ``lr_scale``, ``is_lr``, ``hr_res``, ``n_frames``, ``_get_name``)."""
+    """In-memory HR stacks (uint8 [N, C, H, W], or a sequence of stacks [C_i, H_i, W_i] of differing depths and sizes) with the attribute
+    protocol the drivers consume (``val_idx``, ``extra_hr_files``, ``crop_res``, ``lr_scale``, ``is_lr``, ``hr_res``, ``n_frames``,
+    ``_get_name``).  With ``n_frames`` every stack is cut into ``frames // max(n_frames)`` consecutive frame slices, each one item
+    (pssr/data.py:70-74, 100-110, 566-577, 649-660): item ``idx`` is slice ``k`` of file ``f``, ``(f, k) = _get_image_idx(idx, slices)``,
+    frames ``[k * m, k * m + m)`` with ``m = max(n_frames)``, named ``{name}_{k}``; the validation split is taken over files.
+    ``images`` stays the single array when every stack has one shape, else it is the list."""
 
     def __init__(self, images, hr_res=512, lr_scale=4, crappifier=Poisson(), val_split=0.1, rotation=True, split_seed=0,
                  transforms=None, names=None, n_frames=-1):
-        images = np.asarray(images)
-        if images.ndim == 3:
-            images = images[:, None]
-        if images.dtype != np.uint8:
-            raise ValueError("ArrayDataset expects uint8 images")
-        self.images = images
+        self.images = _tile_stacks(images, "ArrayDataset")
         lr_scale = None if lr_scale == -1 else lr_scale
         self.n_frames = _get_n_frames(n_frames)
-        self.slices = [1] * len(images)
-        max_size = max(images.shape[-2:])
+        shapes = _stack_shapes(self.images)
+        self.slices = _stack_slices(shapes, self.n_frames)
+        max_size = _max_extent(shapes)
         self.val_idx = _get_val_idx(self.slices, val_split, split_seed)
         self.crop_res = min(hr_res, max_size)
         self.is_lr = lr_scale is None or max_size <= hr_res // lr_scale
@@ -208,32 +245,51 @@ class ArrayDataset(Dataset):
         self.crappifier, self.rotation, self.transforms = crappifier, rotation, transforms
         self.extra_hr_files = None
         self.compact = False        # True while train_paired feeds a captured graph from this dataset: uint8 items (see _tensor_ready)
-        self.names = names if names is not None else [f"image{i}" for i in range(len(images))]
+        self.names = names if names is not None else [f"image{i}" for i in range(len(self.images))]
 
     def __len__(self):
-        return len(self.images)
+        return sum(self.slices)
+
+    def _slice(self, idx):
+        """Host stack [frames, H, W] of a dataset index: the whole file with ``n_frames=-1``, else ``max(n_frames)`` frames of it."""
+        if self.n_frames is None:
+            return self.images[idx]
+        image_idx, k = _get_image_idx(idx, self.slices)
+        m = max(self.n_frames)
+        return self.images[image_idx][k * m:k * m + m]
 
     def __getitem__(self, idx, pp=False):
         if idx >= len(self):
             raise IndexError(f"Tried to retrieve invalid image. Index {idx} is not less than {len(self)} total image frame slices.")
         is_val = idx in self.val_idx or pp        # pp: preprocess_dataset's items are never rotated (pssr/data.py:103)
         rot = [bool(random.getrandbits(1)), random.choice((1, 2, (1, 2)))] if self.rotation and not is_val else False
-        hr = self.images[idx]
+        hr = self._slice(idx)
         if self.is_lr:
             return _ready_lr(hr, self.hr_res // self.lr_scale, self.transforms, getattr(self, "compact", False))
         return _gen_pair(hr, self.hr_res, self.lr_scale, rot, self.crappifier, self.transforms, self.n_frames, getattr(self, "compact", False))
 
+    def _res_line(self):
+        return f"low-res: {self.hr_res // self.lr_scale}" if self.is_lr else f"high-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}"
+
+    def __repr__(self):
+        return f"{type(self).__name__} of {len(self.images)} images with {len(self)} total frame slices\n{self._res_line()}"
+
     def _get_name(self, idx):
-        return self.names[idx]
+        if self.n_frames is None:
+            return self.names[idx]
+        image_idx, k = _get_image_idx(idx, self.slices)
+        return f"{self.names[image_idx]}_{k}"
 
 
 class ImageDataset(ArrayDataset):
-    """Folder of pre-tiled single-frame images (anything Pillow opens), reference arguments
-    (pssr/data.py:13).  Multi-frame stacks, czi sheets and ``extra_path`` are outside this build's scope."""
+    """Folder of pre-tiled images (anything Pillow opens; every page of a multi-page tif is a frame), reference arguments
+    (pssr/data.py:13).  Files may differ in size and depth: each is cropped / padded on its own, and with ``n_frames`` each is cut into
+    its own ``frames // max(n_frames)`` frame slices (``n_frames=[5, 1]``: five LR frames in, the centre HR frame out), see
+    :class:`ArrayDataset`.  ``crop_res`` and ``is_lr`` come from the largest extent over all files.  czi sheets and ``extra_path``
+    (upstream's branch for it cannot run) are not built."""
 
     def __init__(self, path, hr_res=512, lr_scale=4, crappifier=Poisson(), n_frames=-1, extension="tif", val_split=0.1,
                  rotation=True, split_seed=0, extra_path=None, extra_scale=1, transforms=None):
-        from PIL import Image
         self.path = Path(path) if type(path) is str else path
         if not path or not self.path.exists():
             raise FileNotFoundError(f'Path "{self.path}" does not exist.')
@@ -242,20 +298,12 @@ class ImageDataset(ArrayDataset):
             raise FileNotFoundError(f'No .{extension} files exist in path "{self.path}".')
         if extra_path is not None:
             raise NotImplementedError("extra_path is not supported by pssr2_amd.ImageDataset")
-        stacks = []
-        for f in files:
-            im = Image.open(Path(self.path, f))
-            frames = []
-            for k in range(getattr(im, "n_frames", 1)):
-                im.seek(k)
-                frames.append(np.asarray(im.convert("L"), dtype=np.uint8))
-            stacks.append(np.stack(frames))
-        shapes = {s.shape for s in stacks}
-        if len(shapes) != 1:
-            raise ValueError("pssr2_amd.ImageDataset needs equally sized images")
-        super().__init__(np.stack(stacks), hr_res, lr_scale, crappifier, val_split, rotation, split_seed, transforms,
+        super().__init__(_read_sheets(self.path, files), hr_res, lr_scale, crappifier, val_split, rotation, split_seed, transforms,
                          [f.split(".")[0] for f in files], n_frames)
         self.hr_files = files
+
+    def __repr__(self):
+        return f'ImageDataset from path "{self.path}"\n{len(self.hr_files)} files with {len(self)} total frame slices\n{self._res_line()}'
 
 
 def _paired_stacks(hr_images, lr_images, who, keep_tensors=False):
@@ -778,20 +826,25 @@ class DevicePairGenerator:
         return self(ops.gen_pair_geometry_u8(stacks, rotations, hr_res), tile_offset)
 
 
-def _gather_table(images, indices, rotations):
-    """int64 [n, 3] device rows (= n ``pssr_gather_item``) that point at ``images[i]`` with the given ``False`` / ``[rot, axis]`` draws."""
+def _gather_rows(entries, device):
+    """int64 [n, 3] device rows (= n ``pssr_gather_item``) from (src address, sh, sw, ``False`` / ``[rot, axis]`` draw) entries."""
     import struct
-    c, h, w = images.shape[1:]
-    base, stride = images.data_ptr(), c * h * w
     buf = bytearray()
-    for i, rot in zip(indices, rotations):
+    for src, h, w, rot in entries:
         axis = -1
         if rot:
             axis = 3 if isinstance(rot[1], (tuple, list)) else int(rot[1])
-        buf += struct.pack("<Qiiii", base + int(i) * stride, h, w, int(bool(rot and rot[0])), axis)
+        buf += struct.pack("<Qiiii", src, h, w, int(bool(rot and rot[0])), axis)
     if not buf:                        # an empty order (val_split = 0, a rank without validation items): torch.frombuffer rejects b""
-        return torch.zeros(0, 3, dtype=torch.int64, device=images.device)
-    return torch.frombuffer(buf, dtype=torch.int64).view(-1, 3).to(images.device)
+        return torch.zeros(0, 3, dtype=torch.int64, device=device)
+    return torch.frombuffer(buf, dtype=torch.int64).view(-1, 3).to(device)
+
+
+def _gather_table(images, indices, rotations):
+    """int64 [n, 3] device rows (= n ``pssr_gather_item``) that point at ``images[i]`` with the given ``False`` / ``[rot, axis]`` draws."""
+    c, h, w = images.shape[1:]
+    base, stride = images.data_ptr(), c * h * w
+    return _gather_rows([(base + int(i) * stride, h, w, rot) for i, rot in zip(indices, rotations)], images.device)
 
 
 class DeviceTileDataset(Dataset):
@@ -802,41 +855,63 @@ class DeviceTileDataset(Dataset):
     (``draw_items`` + ``device_batch``): ``_gen_pair``'s crop / reflect pad / rot90 / flip (host-drawn in the reference's order,
     applied by one gather kernel), the Pillow-exact reduction and the crappifier (device Philox streams) as HIP launches whose
     only per-step inputs are device tensors -- which is what lets ``train_paired`` replay a whole training step as one hipGraph
-    (pssr2_amd/fastpath.py).  Noise comes from the device generator: statistically, not bitwise, the numpy stream of the host path."""
+    (pssr2_amd/fastpath.py).  Noise comes from the device generator: statistically, not bitwise, the numpy stream of the host path.
+
+    Stacks of differing depths and sizes (a sequence of [C_i, H_i, W_i]) each stay their own tensor in HBM.  With ``n_frames`` an item is
+    a frame slice of its file exactly as in ``ArrayDataset`` -- for the gather kernel that is an address (``k * m * H_i * W_i`` bytes into
+    the stack) and the file's own size, so a batch mixes slices of files of any sizes; with ``n_frames=[lr, hr]`` the centre frames of
+    each side are taken after the generator, as ``_gen_pair`` does.  ``n_frames=-1`` needs one depth over all files (a batch has one)."""
 
     def __init__(self, images, hr_res=512, lr_scale=4, crappifier=Poisson(), val_split=0.1, rotation=True, split_seed=0,
                  transforms=None, names=None, n_frames=-1, device="cuda", seed=0):
         if transforms is not None:
             raise NotImplementedError("DeviceTileDataset applies no host transforms")
-        images = torch.as_tensor(np.asarray(images) if not torch.is_tensor(images) else images)
-        if images.dim() == 3:
-            images = images[:, None]
-        if images.dtype != torch.uint8:
-            raise ValueError("DeviceTileDataset expects uint8 images")
-        self.images = images.to(device).contiguous()
+        images = _tile_stacks(images, "DeviceTileDataset", keep_tensors=True)
+        if isinstance(images, list):
+            self.images = [torch.as_tensor(s).to(device).contiguous() for s in images]
+        else:
+            self.images = torch.as_tensor(images).to(device).contiguous()
         lr_scale = None if lr_scale == -1 else lr_scale
         self.n_frames = _get_n_frames(n_frames)
-        if self.n_frames is not None and self.n_frames[0] != self.n_frames[1]:
-            raise NotImplementedError("DeviceTileDataset: 2.5-D frame slicing (n_frames=[lr, hr]) stays on the host path (ArrayDataset)")
-        n = len(self.images)
-        max_size = max(self.images.shape[-2:])
-        self.val_idx = _get_val_idx([1] * n, val_split, split_seed)
+        shapes = _stack_shapes(self.images)
+        self.slices = _stack_slices(shapes, self.n_frames)
+        self.depth = max(self.n_frames) if self.n_frames is not None else _uniform_frames(shapes, "DeviceTileDataset", "stacks")
+        max_size = _max_extent(shapes)
+        self.val_idx = _get_val_idx(self.slices, val_split, split_seed)
         self.crop_res = min(hr_res, max_size)
         self.is_lr = lr_scale is None or max_size <= hr_res // lr_scale
         self.hr_res, self.lr_scale = hr_res, lr_scale if lr_scale is not None else 1
         self.crappifier, self.rotation, self.transforms = crappifier, rotation, None
         self.extra_hr_files = None
-        self.names = names if names is not None else [f"image{i}" for i in range(n)]
+        self.names = names if names is not None else [f"image{i}" for i in range(len(self.images))]
         self._val_set, self._val_key = set(self.val_idx), None
-        self.tile_counter = torch.zeros(1, dtype=torch.int64, device=self.images.device)
+        self.device = self.images[0].device if isinstance(self.images, list) else self.images.device
+        self.tile_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.gen = DevicePairGenerator(self.lr_scale, crappifier, seed=seed, tile_counter=self.tile_counter)
         self._item_bytes = 24             # struct pssr_gather_item {src, sh, sw, rot, flip_axis}
+        # per dataset index (file, slice k, address of the slice's first frame, the file's H, W), in _get_image_idx's order: every read of
+        # the gather kernel, depth frames of H x W bytes from that address, lies inside the file's stack since (k + 1) * depth <= frames
+        if isinstance(self.images, list):
+            bases = [s.data_ptr() for s in self.images]
+        else:
+            bases = [self.images.data_ptr() + f * self.images[0].numel() for f in range(len(self.images))]
+        self._where = [(f, k, base + k * self.depth * h * w, h, w)
+                       for f, (base, (_, h, w), n) in enumerate(zip(bases, shapes, self.slices)) for k in range(n)]
 
     def __len__(self):
-        return len(self.images)
+        return len(self._where)
 
     def _get_name(self, idx):
-        return self.names[idx]
+        if self.n_frames is None:
+            return self.names[idx]
+        f, k = self._where[idx][:2]
+        return f"{self.names[f]}_{k}"
+
+    def _res_line(self):
+        return f"low-res: {self.hr_res // self.lr_scale}" if self.is_lr else f"high-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}"
+
+    def __repr__(self):
+        return f"{type(self).__name__} of {len(self.images)} images with {len(self)} total frame slices\n{self._res_line()}"
 
     def _draw_rotation(self, idx, pp=False):
         # ``idx in self.val_idx`` as upstream (pssr/data.py:103), with the list hashed once per assignment / length change: users enlarge
@@ -850,21 +925,32 @@ class DeviceTileDataset(Dataset):
 
     def draw_items(self, indices, pp=False):
         """Gather table (int64 [n, 3] on the device = n ``pssr_gather_item``) for these dataset indices, drawing the training
-        rotations exactly as ``__getitem__`` would for the same sequence of indices (none with ``pp``)."""
-        return _gather_table(self.images, indices, [self._draw_rotation(int(i), pp) for i in indices])
+        rotations exactly as ``__getitem__`` would for the same sequence of indices (none with ``pp``).  An index outside the dataset
+        raises ``IndexError`` before anything is drawn: a row is an address the kernel reads from."""
+        indices = [int(i) for i in indices]
+        for i in indices:
+            if not 0 <= i < len(self):
+                raise IndexError(f"Tried to retrieve invalid image. Index {i} is not less than {len(self)} total image frame slices.")
+        return _gather_rows([self._where[i][2:] + (self._draw_rotation(i, pp),) for i in indices], self.device)
 
     def device_batch(self, items):
         """items: int64 [b, 3] device rows of ``draw_items``.  Returns float32 (hr, lr) on the device, or lr alone in LR mode.  No
         host synchronisation, no host-side data: capturable in a hipGraph (the Philox tile counter advances on the device)."""
         from . import _lib as L, ops
-        b, c = items.shape[0], self.images.shape[1]
+        b, c = items.shape[0], self.depth
         res = self.hr_res // self.lr_scale if self.is_lr else self.hr_res
-        out = torch.empty(b, c, res, res, dtype=torch.uint8, device=self.images.device)
+        out = torch.empty(b, c, res, res, dtype=torch.uint8, device=self.device)
         L.check(L.lib().pssr_gen_pair_geometry_u8(L.ptr(items), b, L.ptr(out), c, res, L.stream_ptr()), "pssr_gen_pair_geometry_u8")
         if self.is_lr:
             return ops.u8_to_f32(out)
         hr, lr = self.gen(out)
         ops.counter_add(self.tile_counter, b)
+        nf = self.n_frames
+        if nf is not None and nf[0] != nf[1]:           # centre frames of each side, as _gen_pair
+            if not nf[1] > hr.shape[-3]:
+                hr = _slice_center(hr, nf[1]).contiguous()
+            if not nf[0] > lr.shape[-3]:
+                lr = _slice_center(lr, nf[0]).contiguous()
         return hr, lr
 
     def __getitem__(self, idx, pp=False):
@@ -963,10 +1049,10 @@ class _SheetBank:
         return ops.gather_windows_u8(self.table, len(self.sheets), items, c, res)
 
 
-def _uniform_frames(sheets, who):
-    frames = {s.shape[0] for s in sheets}
+def _uniform_frames(sheets, who, what="sheets"):
+    frames = {int(getattr(s, "shape", s)[0]) for s in sheets}          # sheets, or their shapes
     if len(frames) != 1:
-        raise ValueError(f"{who}: n_frames=-1 needs sheets with the same number of frames (a batch has one depth); found {sorted(frames)}")
+        raise ValueError(f"{who}: n_frames=-1 needs {what} with the same number of frames (a batch has one depth); found {sorted(frames)}")
     return frames.pop()
 
 

@@ -110,6 +110,13 @@ def train_paired(model: nn.Module, dataset: Dataset, batch_size: int, loss_fn: n
         from .optim import LossScaler
         scaler = LossScaler()
 
+    # one optimizer arithmetic however the steps are issued: the replay keeps FusedAdamW's step count and rate on the device (the bias
+    # correction then comes from the device's powf, which differs from the host's in the last place for some step counts); the loop
+    # below does the same, so that PSSR_GRAPH=0 gives the replay's bits
+    from .optim import FusedAdamW
+    if isinstance(optim, FusedAdamW) and torch.device(device).type == "cuda":
+        optim.device_state = True
+
     stepper = evaler = None
     if fast:
         stepper = fastpath.TrainStepper(model, dataset, batch_size, loss_fn, optim, clamp, image_range, scaler, len(train_sampler), device)
