@@ -14,6 +14,14 @@ File decoding (tif/czi) is out of scope: ``ImageDataset`` rea
 Image sheets (the reference's ``SlidingDataset`` / ``PairedSlidingDataset``) follow the same three steps: ``SlidingSheetDataset`` /
 ``PairedSlidingArrayDataset`` over sheets in memory, the file classes on top of them (Pillow, multi-page tifs included), and
 ``DeviceSlidingDataset`` / ``DevicePairedSlidingDataset`` with the sheets in HBM and the windows cut by ``pssr_gather_windows_u8``.
+
+Layout: four families (tile, paired tile, sheet, paired sheet), each an in-memory class, a folder class on top of it and an HBM-resident
+class that derives from it.  What they share is written once: ``_ItemProtocol`` (index check, rotation draw, ``val_idx`` membership through
+``_in_val``, ``compact``, ``__repr__``), ``_center_frames``, ``_u8_stack`` (input normalisation), ``_find_files`` / ``_find_paired_files`` /
+``_read_sheets`` (folders), ``_pack_rows`` (kernel tables), and for the device classes ``_DeviceItems`` with ``_DeviceSynthesis`` (pairs
+synthesised from HR: everything after the uint8 gather) and ``_DevicePairs`` (real pairs).  ``SlidingArrayDataset`` is
+``SlidingSheetDataset`` in LR mode under a short signature: unlike its earlier stand-alone form it prints upstream's LR-mode line and
+refuses sheets that are not uint8.
 """
 from __future__ import annotations
 
@@ -54,6 +62,14 @@ def _slice_center(image, n_frames):
     return image[..., center - half:center + half + 1, :, :]
 
 
+def _center_frames(sides, n_frames):
+    """``n_frames=[lr, hr]`` of different lengths (pssr/data.py:488-492): the centre ``hr`` / ``lr`` frames of the (HR, LR) arrays or tensors
+    [..., C, H, W]; a side that has fewer frames stays whole.  Views: the device callers make them contiguous."""
+    if n_frames is None or n_frames[0] == n_frames[1]:
+        return tuple(sides)
+    return tuple(side if n > side.shape[-3] else _slice_center(side, n) for side, n in zip(sides, n_frames[::-1]))
+
+
 def _tensor_ready(image, transforms, compact=False):
     """float32 tensor of an image (pssr/data.py:497-505).  ``compact``: uint8 instead -- what the drivers of this package ask their own
     datasets for while they feed a captured graph from a DataLoader (every value here is an integer in [0, 255]: uint8 pixels, or the
@@ -86,11 +102,7 @@ def _gen_pair(hr, hr_res, lr_scale, rotation, crappifier, transforms, n_frames, 
     if crappifier is not None:
         lr = crappifier.crappify(lr) if issubclass(type(crappifier), Crappifier) else crappifier(lr)
         lr = np.clip(lr.round(), 0, 255)
-    if n_frames is not None and n_frames[0] != n_frames[1]:
-        if not n_frames[1] > hr.shape[-3]:
-            hr = _slice_center(hr, n_frames[1])
-        if not n_frames[0] > lr.shape[-3]:
-            lr = _slice_center(lr, n_frames[0])
+    hr, lr = _center_frames((hr, lr), n_frames)
     return _tensor_ready(hr, transforms, compact), _tensor_ready(lr, transforms, compact)
 
 
@@ -104,11 +116,7 @@ def _transform_pair(hr, lr, hr_res, lr_res, rotation, transforms, n_frames, comp
             image = np.flip(np.rot90(image, axes=(1, 2)) if rotation[0] else image, axis=rotation[1])
         sides.append(image)
     hr, lr = sides
-    if n_frames is not None and n_frames[0] != n_frames[1]:
-        if not n_frames[1] > hr.shape[-3]:
-            hr = _slice_center(hr, n_frames[1])
-        if not n_frames[0] > lr.shape[-3]:
-            lr = _slice_center(lr, n_frames[0])
+    hr, lr = _center_frames((hr, lr), n_frames)
     return _tensor_ready(hr, transforms, compact), _tensor_ready(lr, transforms, compact)
 
 
@@ -184,28 +192,46 @@ class _RandomIterIdx:
         return n // self.world if self.world > 1 and n >= self.world else n
 
 
-# --------------------------------------------------------------------------------------- datasets
+# --------------------------------------------------------------------------------------- dataset inputs
+def _u8_stack(x, ndim, message, keep_tensors=False):
+    """One input of a dataset as the classes hold it: a numpy array (a tensor as it is with ``keep_tensors``: the device classes) of
+    ``ndim`` axes [..., frames, H, W], an input without the frame axis taken as one frame each.  Anything else, and anything but uint8,
+    raises ``ValueError(message)``."""
+    if not torch.is_tensor(x):
+        x = np.asarray(x)
+    elif not keep_tensors:
+        x = x.cpu().numpy()
+    if x.ndim == ndim - 1:
+        x = x[..., None, :, :]
+    if x.ndim != ndim or str(x.dtype).split(".")[-1] != "uint8":          # numpy's and torch's spelling of the dtype
+        raise ValueError(message)
+    return x
+
+
 def _tile_stacks(images, who, keep_tensors=False):
     """The stacks of a tile dataset: one uint8 array / tensor [N, C, H, W] (``[N, H, W]``: one frame each) as it came, or a sequence of uint8
     stacks [C_i, H_i, W_i] (2-D: one frame) of any depths and sizes -- stacked into one array when every shape agrees, else a list."""
-    if torch.is_tensor(images):
-        single = images if keep_tensors else images.cpu().numpy()
-    elif isinstance(images, np.ndarray) and images.dtype != object:
-        single = images
-    else:
-        stacks = [s if torch.is_tensor(s) and keep_tensors else (s.cpu().numpy() if torch.is_tensor(s) else np.asarray(s)) for s in images]
-        if len(stacks) and len({tuple(s.shape) for s in stacks}) == 1:
-            single = torch.stack(stacks) if torch.is_tensor(stacks[0]) else np.stack(stacks)
-        else:
-            stacks = [s[None] if s.ndim == 2 else s for s in stacks]
-            if any(s.ndim != 3 or str(s.dtype).split(".")[-1] != "uint8" for s in stacks):
-                raise ValueError(f"{who} expects uint8 images")
-            return stacks
-    if single.ndim == 3:
-        single = single[:, None]
-    if str(single.dtype).split(".")[-1] != "uint8":
-        raise ValueError(f"{who} expects uint8 images")
-    return single
+    message = f"{who} expects uint8 images"
+    if torch.is_tensor(images) or (isinstance(images, np.ndarray) and images.dtype != object):
+        return _u8_stack(images, 4, message, keep_tensors)
+    stacks = [_u8_stack(s, 3, message, keep_tensors) for s in images]
+    if len(stacks) and len({tuple(s.shape) for s in stacks}) == 1:
+        return torch.stack(stacks) if torch.is_tensor(stacks[0]) else np.stack(stacks)
+    return stacks
+
+
+def _check_paired(hr, lr, error=ValueError):
+    if len(hr) != len(lr):
+        raise error(f"Mismatch between amounts of high-low-resolution images. Found {len(hr)} high-resolution and {len(lr)} low-resolution images.")
+    return hr, lr
+
+
+def _paired_stacks(hr_images, lr_images, who, keep_tensors=False):
+    return _check_paired(*(_u8_stack(images, 4, f"{who} expects uint8 images [N, C, H, W]", keep_tensors) for images in (hr_images, lr_images)))
+
+
+def _sheet_list(sheets, who, keep_tensors=False):
+    return [_u8_stack(s, 3, f"{who} expects uint8 sheets [F, H, W]", keep_tensors) for s in sheets]
 
 
 def _stack_shapes(images):
@@ -222,7 +248,132 @@ def _max_extent(shapes):
     return max((max(s[-2:]) for s in shapes), default=0)
 
 
-class ArrayDataset(Dataset):
+def _tiles_slices(sheets, size, stride, n_frames, slide):
+    """Windows per sheet and frame slices per window (pssr/data.py:205-210)."""
+    tiles, slices = [], []
+    for s in sheets:
+        tx, ty = _n_tiles(s, size, stride)
+        tiles.append(tx * ty)
+        slices.append(1 if n_frames is None else ((s.shape[0] - max(n_frames) + 1) if slide else (s.shape[0] // max(n_frames))))
+    return tiles, slices
+
+
+def _check_stride(hr_res, overlap):
+    overlap = 0 if overlap is None else overlap
+    if not hr_res > overlap:
+        raise ValueError(f"hr_res must be greater than overlap. Given values are {hr_res} and {overlap} respectively.")
+    return hr_res - overlap
+
+
+# --------------------------------------------------------------------------------------- folders
+def _existing_path(path):
+    given, path = path, Path(path) if type(path) is str else path
+    if not given or not path.exists():
+        raise FileNotFoundError(f'Path "{path}" does not exist.')
+    return path
+
+
+def _find_files(path, extension, sheets=False):
+    """(folder, its ``.extension`` files at any depth, relative and sorted), with the reference's errors in its order; ``sheets``: the sheet
+    classes, which upstream reads czi files for and this package does not."""
+    path = _existing_path(path)
+    if sheets and extension.lower() == "czi":
+        raise NotImplementedError("czi sheets are not supported by pssr2_amd (czifile is not a dependency): export them to tif")
+    files = sorted(f.split(str(path), maxsplit=1)[-1].strip("/") for f in glob.glob(f"{path}/**/*.{extension}", recursive=True))
+    if not files:
+        raise FileNotFoundError(f'No .{extension} files exist in path "{path}".')
+    return path, files
+
+
+def _find_paired_files(hr_path, lr_path, extension, instead, sheets=False):
+    """((HR folder, files), (LR folder, files)) of a two-folder dataset (pssr/data.py:294-306, 384-396): both folders exist, the warning
+    for one folder given twice (raised for the caller of the dataset's constructor), the files of each side, as many on both."""
+    hr_path, lr_path = _existing_path(hr_path), _existing_path(lr_path)
+    if hr_path == lr_path:
+        warnings.warn(f"hr_path is equal to lr_path! Consider using {instead} instead.", stacklevel=3)
+    hr, lr = _find_files(hr_path, extension, sheets), _find_files(lr_path, extension, sheets)
+    _check_paired(hr[1], lr[1], FileNotFoundError)
+    return hr, lr
+
+
+def _read_sheets(path, files):
+    """Every file as a uint8 stack [F, H, W] through Pillow (multi-page tifs: one frame per page), sizes free."""
+    from PIL import Image
+    sheets = []
+    for f in files:
+        with Image.open(Path(path, f)) as im:
+            frames = []
+            for k in range(getattr(im, "n_frames", 1)):
+                im.seek(k)
+                frames.append(np.asarray(im.convert("L"), dtype=np.uint8))
+        sheets.append(np.stack(frames))
+    return sheets
+
+
+def _file_names(files):
+    return [f.split(".")[0] for f in files]
+
+
+# --------------------------------------------------------------------------------------- item protocol
+def _get_image_idx(idx, slices, tiles=None):
+    """(sheet, index inside the sheet) of a dataset index (pssr/data.py:697-706)."""
+    tiles = [1] * len(slices) if tiles is None else tiles
+    for image_idx, (s, t) in enumerate(zip(slices, tiles)):
+        if idx < s * t:
+            return image_idx, idx
+        idx -= s * t
+    return None
+
+
+def _in_val(dataset, idx):
+    # ``idx in dataset.val_idx`` as upstream (pssr/data.py:103), with the list hashed once per assignment / length change: users enlarge
+    # val_idx after training to predict every image
+    key = (id(dataset.val_idx), len(dataset.val_idx))
+    if key != getattr(dataset, "_val_key", None):
+        dataset._val_set, dataset._val_key = set(dataset.val_idx), key
+    return idx in dataset._val_set
+
+
+class _ItemProtocol(Dataset):
+    """What every dataset family shares of the reference's item protocol: the index check, the rotation draw, ``extra_hr_files`` and
+    ``compact``, ``__repr__``.  A family sets ``hr_res``, ``lr_scale``, ``is_lr``, ``rotation``, ``transforms``, ``val_idx`` and ``names``
+    (``_set_protocol``) and writes ``__len__``, ``_get_name``, ``_summary`` and ``_item``."""
+    _keep_tensors = False           # True in the device classes: inputs already in HBM stay there
+    _host_items = True              # False in the device classes: their items are float32 device tensors, so the host feed has nothing to
+                                    # compact and they have no ``compact`` attribute at all (the drivers ask ``getattr(dataset, "compact", None)``)
+
+    def _set_protocol(self, hr_res, lr_scale, rotation, transforms, names, stem, count):
+        self.hr_res, self.lr_scale, self.rotation, self.transforms = hr_res, lr_scale, rotation, transforms
+        self.extra_hr_files = None
+        if self._host_items:
+            self.compact = False        # True while a driver feeds a captured graph from this dataset: uint8 items (see _tensor_ready)
+        self.names = list(names) if names is not None else [f"{stem}{i}" for i in range(count)]
+
+    def _check_idx(self, idx, row=False):
+        """``row``: the index becomes a row that a kernel reads addresses from, so nothing before the first item either."""
+        if idx >= len(self) or (row and idx < 0):
+            raise IndexError(f"Tried to retrieve invalid image. Index {idx} is not less than {len(self)} total image frame slices.")
+
+    def _draw_rotation(self, idx, pp=False):
+        """``False`` for a validation item and for ``pp`` (preprocess_dataset's items are never rotated, pssr/data.py:103), else the
+        reference's two draws in its order -- also in LR mode, where they go unused."""
+        if self.rotation and not (_in_val(self, idx) or pp):
+            return [bool(random.getrandbits(1)), random.choice((1, 2, (1, 2)))]
+        return False
+
+    def __getitem__(self, idx, pp=False):
+        self._check_idx(idx)
+        return self._item(idx, self._draw_rotation(idx, pp))
+
+    def _res_line(self):
+        return f"low-res: {self.hr_res // self.lr_scale}" if self.is_lr else f"high-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}"
+
+    def __repr__(self):
+        return f"{self._summary()} with {len(self)} total frame slices\n{self._res_line()}"
+
+
+# --------------------------------------------------------------------------------------- tiles
+class ArrayDataset(_ItemProtocol):
     """In-memory HR stacks (uint8 [N, C, H, W], or a sequence of stacks [C_i, H_i, W_i] of differing depths and sizes) with the attribute
     protocol the drivers consume (``val_idx``, ``extra_hr_files``, ``crop_res``, ``lr_scale``, ``is_lr``, ``hr_res``, ``n_frames``,
     ``_get_name``).  With ``n_frames`` every stack is cut into ``frames // max(n_frames)`` consecutive frame slices, each one item
@@ -232,7 +383,7 @@ class ArrayDataset(Dataset):
 
     def __init__(self, images, hr_res=512, lr_scale=4, crappifier=Poisson(), val_split=0.1, rotation=True, split_seed=0,
                  transforms=None, names=None, n_frames=-1):
-        self.images = _tile_stacks(images, "ArrayDataset")
+        self.images = _tile_stacks(images, type(self).__name__, self._keep_tensors)
         lr_scale = None if lr_scale == -1 else lr_scale
         self.n_frames = _get_n_frames(n_frames)
         shapes = _stack_shapes(self.images)
@@ -241,11 +392,8 @@ class ArrayDataset(Dataset):
         self.val_idx = _get_val_idx(self.slices, val_split, split_seed)
         self.crop_res = min(hr_res, max_size)
         self.is_lr = lr_scale is None or max_size <= hr_res // lr_scale
-        self.hr_res, self.lr_scale = hr_res, lr_scale if lr_scale is not None else 1
-        self.crappifier, self.rotation, self.transforms = crappifier, rotation, transforms
-        self.extra_hr_files = None
-        self.compact = False        # True while train_paired feeds a captured graph from this dataset: uint8 items (see _tensor_ready)
-        self.names = names if names is not None else [f"image{i}" for i in range(len(self.images))]
+        self.crappifier = crappifier
+        self._set_protocol(hr_res, lr_scale if lr_scale is not None else 1, rotation, transforms, names, "image", len(self.images))
 
     def __len__(self):
         return sum(self.slices)
@@ -258,21 +406,14 @@ class ArrayDataset(Dataset):
         m = max(self.n_frames)
         return self.images[image_idx][k * m:k * m + m]
 
-    def __getitem__(self, idx, pp=False):
-        if idx >= len(self):
-            raise IndexError(f"Tried to retrieve invalid image. Index {idx} is not less than {len(self)} total image frame slices.")
-        is_val = idx in self.val_idx or pp        # pp: preprocess_dataset's items are never rotated (pssr/data.py:103)
-        rot = [bool(random.getrandbits(1)), random.choice((1, 2, (1, 2)))] if self.rotation and not is_val else False
+    def _item(self, idx, rot):
         hr = self._slice(idx)
         if self.is_lr:
-            return _ready_lr(hr, self.hr_res // self.lr_scale, self.transforms, getattr(self, "compact", False))
-        return _gen_pair(hr, self.hr_res, self.lr_scale, rot, self.crappifier, self.transforms, self.n_frames, getattr(self, "compact", False))
+            return _ready_lr(hr, self.hr_res // self.lr_scale, self.transforms, self.compact)
+        return _gen_pair(hr, self.hr_res, self.lr_scale, rot, self.crappifier, self.transforms, self.n_frames, self.compact)
 
-    def _res_line(self):
-        return f"low-res: {self.hr_res // self.lr_scale}" if self.is_lr else f"high-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}"
-
-    def __repr__(self):
-        return f"{type(self).__name__} of {len(self.images)} images with {len(self)} total frame slices\n{self._res_line()}"
+    def _summary(self):
+        return f"{type(self).__name__} of {len(self.images)} images"
 
     def _get_name(self, idx):
         if self.n_frames is None:
@@ -290,47 +431,22 @@ class ImageDataset(ArrayDataset):
 
     def __init__(self, path, hr_res=512, lr_scale=4, crappifier=Poisson(), n_frames=-1, extension="tif", val_split=0.1,
                  rotation=True, split_seed=0, extra_path=None, extra_scale=1, transforms=None):
-        self.path = Path(path) if type(path) is str else path
-        if not path or not self.path.exists():
-            raise FileNotFoundError(f'Path "{self.path}" does not exist.')
-        files = sorted(f.split(str(self.path), maxsplit=1)[-1].strip("/") for f in glob.glob(f"{self.path}/**/*.{extension}", recursive=True))
-        if not files:
-            raise FileNotFoundError(f'No .{extension} files exist in path "{self.path}".')
+        self.path, self.hr_files = _find_files(path, extension)
         if extra_path is not None:
             raise NotImplementedError("extra_path is not supported by pssr2_amd.ImageDataset")
-        super().__init__(_read_sheets(self.path, files), hr_res, lr_scale, crappifier, val_split, rotation, split_seed, transforms,
-                         [f.split(".")[0] for f in files], n_frames)
-        self.hr_files = files
+        super().__init__(_read_sheets(self.path, self.hr_files), hr_res, lr_scale, crappifier, val_split, rotation, split_seed, transforms,
+                         _file_names(self.hr_files), n_frames)
 
-    def __repr__(self):
-        return f'ImageDataset from path "{self.path}"\n{len(self.hr_files)} files with {len(self)} total frame slices\n{self._res_line()}'
-
-
-def _paired_stacks(hr_images, lr_images, who, keep_tensors=False):
-    out = []
-    for images in (hr_images, lr_images):
-        if not torch.is_tensor(images):
-            images = np.asarray(images)
-        elif not keep_tensors:
-            images = images.cpu().numpy()
-        if images.ndim == 3:
-            images = images[:, None]
-        if images.ndim != 4 or str(images.dtype).split(".")[-1] != "uint8":
-            raise ValueError(f"{who} expects uint8 images [N, C, H, W]")
-        out.append(images)
-    if len(out[0]) != len(out[1]):
-        raise ValueError(f"Mismatch between amounts of high-low-resolution images. Found {len(out[0])} high-resolution and "
-                         f"{len(out[1])} low-resolution images.")
-    return out
+    def _summary(self):
+        return f'ImageDataset from path "{self.path}"\n{len(self.hr_files)} files'
 
 
-class PairedArrayDataset(Dataset):
+class PairedArrayDataset(_ItemProtocol):
     """Real (HR, LR) pairs in memory, uint8 [N, C, H, W] and [N, c, h, w]: the reference's ``PairedImageDataset`` (pssr/data.py:268-346)
     without the files -- its defaults (``val_split=1``: every item is a validation item; ``split_seed=None``: the last images), its
     attribute protocol and its item geometry (``_transform_pair``), for ``train_crappifier``, ``approximate_crappifier``,
     ``test_metrics`` and ``predict_images(norm=True)``.  Every pair is one item: with ``n_frames=[lr, hr]`` of different lengths the
     centre frames of the two stacks are taken, as ``_transform_pair`` does."""
-    _keep_tensors = False
 
     def __init__(self, hr_images, lr_images, hr_res=512, lr_scale=4, n_frames=-1, val_split=1, rotation=True, split_seed=None,
                  transforms=None, names=None):
@@ -340,46 +456,19 @@ class PairedArrayDataset(Dataset):
         self.val_idx = _get_val_idx(self.slices, val_split, split_seed)
         self.is_lr = False
         self.crop_res = min(hr_res, max(self.hr_images.shape[-2:]))
-        self.extra_hr_files = None
-        self.hr_res, self.lr_scale, self.rotation, self.transforms = hr_res, lr_scale, rotation, transforms
-        self.compact = False        # see ArrayDataset.compact
-        self.names = list(names) if names is not None else [f"image{i}" for i in range(len(self.hr_images))]
+        self._set_protocol(hr_res, lr_scale, rotation, transforms, names, "image", len(self.hr_images))
 
-    def __len__(self):
-        return sum(self.slices)
+    __len__ = ArrayDataset.__len__
 
-    def _draw_rotation(self, idx, pp=False):
-        if self.rotation and not (idx in self.val_idx or pp):
-            return [bool(random.getrandbits(1)), random.choice((1, 2, (1, 2)))]      # the reference's draws, in its order
-        return False
+    def _item(self, idx, rot):
+        return _transform_pair(self.hr_images[idx], self.lr_images[idx], self.hr_res, self.hr_res // self.lr_scale, rot, self.transforms,
+                               self.n_frames, self.compact)
 
-    def __getitem__(self, idx, pp=False):
-        if idx >= len(self):
-            raise IndexError(f"Tried to retrieve invalid image. Index {idx} is not less than {len(self)} total image frame slices.")
-        return _transform_pair(self.hr_images[idx], self.lr_images[idx], self.hr_res, self.hr_res // self.lr_scale,
-                               self._draw_rotation(idx, pp), self.transforms, self.n_frames, getattr(self, "compact", False))
-
-    def __repr__(self):
-        return (f"{type(self).__name__} of {len(self.hr_images)} paired images with {len(self)} total frame slices\n"
-                f"high-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}")
+    def _summary(self):
+        return f"{type(self).__name__} of {len(self.hr_images)} paired images"
 
     def _get_name(self, idx):
         return self.names[idx] + ("_0" if self.n_frames is not None else "")
-
-
-def _read_folder(path, files):
-    from PIL import Image
-    stacks = []
-    for f in files:
-        im = Image.open(Path(path, f))
-        frames = []
-        for k in range(getattr(im, "n_frames", 1)):
-            im.seek(k)
-            frames.append(np.asarray(im.convert("L"), dtype=np.uint8))
-        stacks.append(np.stack(frames))
-    if len({st.shape for st in stacks}) != 1:
-        raise ValueError(f'pssr2_amd.PairedImageDataset needs equally sized images in "{path}"')
-    return np.stack(stacks)
 
 
 class PairedImageDataset(PairedArrayDataset):
@@ -389,76 +478,21 @@ class PairedImageDataset(PairedArrayDataset):
 
     def __init__(self, hr_path, lr_path, hr_res=512, lr_scale=4, n_frames=-1, extension="tif", val_split=1, rotation=True,
                  split_seed=None, transforms=None):
-        self.hr_path = Path(hr_path) if type(hr_path) is str else hr_path
-        self.lr_path = Path(lr_path) if type(lr_path) is str else lr_path
-        for path in (self.hr_path, self.lr_path):
-            if not path or not path.exists():
-                raise FileNotFoundError(f'Path "{path}" does not exist.')
-        if self.hr_path == self.lr_path:
-            warnings.warn("hr_path is equal to lr_path! Consider using ImageDataset instead.", stacklevel=2)
-        found = []
-        for path in (self.hr_path, self.lr_path):
-            files = sorted(f.split(str(path), maxsplit=1)[-1].strip("/") for f in glob.glob(f"{path}/**/*.{extension}", recursive=True))
-            if not files:
-                raise FileNotFoundError(f'No .{extension} files exist in path "{path}".')
-            found.append(files)
-        self.hr_files, self.lr_files = found
-        if len(self.hr_files) != len(self.lr_files):
-            raise FileNotFoundError(f"Mismatch between amounts of high-low-resolution images. Found {len(self.hr_files)} high-resolution "
-                                    f"and {len(self.lr_files)} low-resolution images.")
-        super().__init__(_read_folder(self.hr_path, self.hr_files), _read_folder(self.lr_path, self.lr_files), hr_res, lr_scale, n_frames,
-                         val_split, rotation, split_seed, transforms, [f.split(".")[0] for f in self.lr_files])
+        (self.hr_path, self.hr_files), (self.lr_path, self.lr_files) = _find_paired_files(hr_path, lr_path, extension, "ImageDataset")
+        sides = []
+        for path, files in ((self.hr_path, self.hr_files), (self.lr_path, self.lr_files)):
+            stacks = _read_sheets(path, files)
+            if len({st.shape for st in stacks}) != 1:
+                raise ValueError(f'pssr2_amd.PairedImageDataset needs equally sized images in "{path}"')
+            sides.append(np.stack(stacks))
+        super().__init__(*sides, hr_res, lr_scale, n_frames, val_split, rotation, split_seed, transforms, _file_names(self.lr_files))
         self.mode = "L"
 
-    def __repr__(self):
-        return (f'PairedImageDataset from paths "{self.hr_path}" and "{self.lr_path}"\n{len(self.hr_files)} paired files with {len(self)} '
-                f"total frame slices\nhigh-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}")
-
-
-class SlidingArrayDataset(Dataset):
-    """LR-mode sliding window over in-memory sheets (pssr/data.py:132-266 with ``lr_scale=-1``): tiles are
-    row-major, ``stride = hr_res - overlap``, trailing remainders are dropped."""
-
-    def __init__(self, sheets, hr_res=128, overlap=32, names=None, transforms=None):
-        self.sheets = [np.asarray(s if np.asarray(s).ndim == 3 else np.asarray(s)[None]) for s in sheets]
-        self.hr_res, self.lr_scale, self.stride = hr_res, 1, hr_res - overlap
-        self.tiles = [int(np.prod(_n_tiles(s, hr_res, self.stride))) for s in self.sheets]
-        self.val_idx = list(range(sum(self.tiles)))
-        self.crop_res, self.is_lr, self.extra_hr_files, self.n_frames = hr_res, True, None, None
-        self.names = names if names is not None else [f"sheet{i}" for i in range(len(self.sheets))]
-        self.transforms = transforms
-        self.compact = False        # see ArrayDataset.compact
-
-    def __len__(self):
-        return sum(self.tiles)
-
-    def _locate(self, idx):
-        for s, t in enumerate(self.tiles):
-            if idx < t:
-                return s, idx
-            idx -= t
-        raise IndexError(idx)
-
-    def __getitem__(self, idx):
-        s, t = self._locate(idx)
-        return _tensor_ready(_sliding_tile(self.sheets[s], self.hr_res, self.stride, t), self.transforms, getattr(self, "compact", False))
-
-    def _get_name(self, idx):
-        s, t = self._locate(idx)
-        return f"{self.names[s]}_{t}_0"
+    def _summary(self):
+        return f'PairedImageDataset from paths "{self.hr_path}" and "{self.lr_path}"\n{len(self.hr_files)} paired files'
 
 
 # --------------------------------------------------------------------------------------- sheets
-def _get_image_idx(idx, slices, tiles=None):
-    """(sheet, index inside the sheet) of a dataset index (pssr/data.py:697-706)."""
-    tiles = [1] * len(slices) if tiles is None else tiles
-    for image_idx, (s, t) in enumerate(zip(slices, tiles)):
-        if idx < s * t:
-            return image_idx, idx
-        idx -= s * t
-    return None
-
-
 def _window_origin(sheet, size, stride, n_frames, n_slices, idx, slide):
     """(frame0, y0, x0) of the window ``_sliding_window`` cuts for the in-sheet index ``idx`` (pssr/data.py:629-660): tiles row-major,
     ``tile = idx // n_slices``; frame slice ``idx % n_slices``, times ``n_frames`` unless the stack is slid over."""
@@ -474,47 +508,18 @@ def _sliding_window(sheet, size, stride, n_frames, n_slices, idx, slide):
     return window if n_frames is None else window[frame0:frame0 + n_frames]
 
 
-def _sheet_list(sheets, who, keep_tensors=False):
-    out = []
-    for s in sheets:
-        if not torch.is_tensor(s):
-            s = np.asarray(s)
-        elif not keep_tensors:
-            s = s.cpu().numpy()
-        if s.ndim == 2:
-            s = s[None]
-        if s.ndim != 3 or str(s.dtype).split(".")[-1] != "uint8":
-            raise ValueError(f"{who} expects uint8 sheets [F, H, W]")
-        out.append(s)
-    return out
+class _SheetIndex(_ItemProtocol):
+    """Windows times frame slices per sheet (``tiles``, ``slices``): what the two sheet families count and name their items by."""
+
+    def __len__(self):
+        return sum(t * s for t, s in zip(self.tiles, self.slices))
+
+    def _get_name(self, idx):
+        image_idx, local = _get_image_idx(idx, self.slices, self.tiles)
+        return f"{self.names[image_idx]}_{local // self.slices[image_idx]}_{local % self.slices[image_idx]}"
 
 
-def _tiles_slices(sheets, size, stride, n_frames, slide):
-    """Windows per sheet and frame slices per window (pssr/data.py:205-210)."""
-    tiles, slices = [], []
-    for s in sheets:
-        tx, ty = _n_tiles(s, size, stride)
-        tiles.append(tx * ty)
-        slices.append(1 if n_frames is None else ((s.shape[0] - max(n_frames) + 1) if slide else (s.shape[0] // max(n_frames))))
-    return tiles, slices
-
-
-def _in_val(dataset, idx):
-    # ``idx in dataset.val_idx`` as upstream, with the list hashed once per assignment / length change (see DeviceTileDataset._draw_rotation)
-    key = (id(dataset.val_idx), len(dataset.val_idx))
-    if key != getattr(dataset, "_val_key", None):
-        dataset._val_set, dataset._val_key = set(dataset.val_idx), key
-    return idx in dataset._val_set
-
-
-def _check_stride(hr_res, overlap):
-    overlap = 0 if overlap is None else overlap
-    if not hr_res > overlap:
-        raise ValueError(f"hr_res must be greater than overlap. Given values are {hr_res} and {overlap} respectively.")
-    return hr_res - overlap
-
-
-class SlidingSheetDataset(Dataset):
+class SlidingSheetDataset(_SheetIndex):
     """Training dataset over in-memory image sheets (uint8 [F, H, W] each, 2-D accepted, of any sizes): the reference's
     ``SlidingDataset`` (pssr/data.py:132-266) without the files.  Same arithmetic -- ``stride = hr_res - overlap``, whole windows only,
     row-major; per sheet ``tiles`` windows times ``slices`` frame slices (``frames - max(n_frames) + 1`` with ``slide``, else
@@ -524,35 +529,19 @@ class SlidingSheetDataset(Dataset):
 
     def __init__(self, sheets, hr_res=512, lr_scale=4, crappifier=Poisson(), overlap=128, n_frames=-1, slide=False, val_split=0.1,
                  rotation=True, split_seed=0, transforms=None, names=None):
-        self.sheets = _sheet_list(sheets, type(self).__name__, getattr(self, "_keep_tensors", False))
+        self.sheets = _sheet_list(sheets, type(self).__name__, self._keep_tensors)
         self.stride = _check_stride(hr_res, overlap)
-        lr_scale = None if lr_scale == -1 else lr_scale
         self.n_frames, self.slide = _get_n_frames(n_frames), slide
         self.tiles, self.slices = _tiles_slices(self.sheets, hr_res, self.stride, self.n_frames, slide)
         self.val_idx = _get_val_idx(self.slices, val_split, split_seed, self.tiles)
         self.crop_res = hr_res
-        self.is_lr = lr_scale is None
+        self.is_lr = lr_scale in (-1, None)
         if self.is_lr:
             print("LR mode is enabled, dataset will load only unmodified low-resolution images.")
             if val_split < 1:
                 warnings.warn("val_split is less than 1, not all low-resolution images will be used in prediciton.", stacklevel=2)
-        self.hr_res, self.lr_scale = hr_res, lr_scale if lr_scale is not None else 1
-        self.crappifier, self.rotation, self.transforms = crappifier, rotation, transforms
-        self.extra_hr_files = None
-        self.compact = False        # see ArrayDataset.compact
-        self.names = list(names) if names is not None else [f"sheet{i}" for i in range(len(self.sheets))]
-
-    def __len__(self):
-        return sum(t * s for t, s in zip(self.tiles, self.slices))
-
-    def _check_idx(self, idx):
-        if idx >= len(self):
-            raise IndexError(f"Tried to retrieve invalid image. Index {idx} is not less than {len(self)} total image frame slices.")
-
-    def _draw_rotation(self, idx, pp=False):
-        if self.rotation and not (_in_val(self, idx) or pp):
-            return [bool(random.getrandbits(1)), random.choice((1, 2, (1, 2)))]      # the reference's draws, in its order
-        return False
+        self.crappifier = crappifier
+        self._set_protocol(hr_res, 1 if self.is_lr else lr_scale, rotation, transforms, names, "sheet", len(self.sheets))
 
     def _window(self, idx):
         """Host window [frames, hr_res, hr_res] of a dataset index, ``max(n_frames)`` frames deep."""
@@ -560,48 +549,23 @@ class SlidingSheetDataset(Dataset):
         return _sliding_window(self.sheets[image_idx], self.hr_res, self.stride, max(self.n_frames) if self.n_frames is not None else None,
                                self.slices[image_idx], local, self.slide)
 
-    def __getitem__(self, idx, pp=False):
-        self._check_idx(idx)
-        hr, rot, compact = self._window(idx), self._draw_rotation(idx, pp), getattr(self, "compact", False)
+    def _item(self, idx, rot):
+        hr = self._window(idx)
         if self.is_lr:
-            return _ready_lr(hr, self.hr_res, self.transforms, compact)
-        return _gen_pair(hr, self.hr_res, self.lr_scale, rot, self.crappifier, self.transforms, self.n_frames, compact)
+            return _ready_lr(hr, self.hr_res, self.transforms, self.compact)
+        return _gen_pair(hr, self.hr_res, self.lr_scale, rot, self.crappifier, self.transforms, self.n_frames, self.compact)
 
-    def _res_line(self):
-        return f"low-res: {self.hr_res}" if self.is_lr else f"high-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}"
-
-    def __repr__(self):
-        return f"{type(self).__name__} of {len(self.sheets)} sheets with {len(self)} total frame slices\n{self._res_line()}"
-
-    def _get_name(self, idx):
-        image_idx, local = _get_image_idx(idx, self.slices, self.tiles)
-        return f"{self.names[image_idx]}_{local // self.slices[image_idx]}_{local % self.slices[image_idx]}"
+    def _summary(self):
+        return f"{type(self).__name__} of {len(self.sheets)} sheets"
 
 
-def _sheet_files(path, extension):
-    path = Path(path) if type(path) is str else path
-    if not path or not path.exists():
-        raise FileNotFoundError(f'Path "{path}" does not exist.')
-    if extension.lower() == "czi":
-        raise NotImplementedError("czi sheets are not supported by pssr2_amd (czifile is not a dependency): export them to tif")
-    files = sorted(f.split(str(path), maxsplit=1)[-1].strip("/") for f in glob.glob(f"{path}/**/*.{extension}", recursive=True))
-    if not files:
-        raise FileNotFoundError(f'No .{extension} files exist in path "{path}".')
-    return path, files
+class SlidingArrayDataset(SlidingSheetDataset):
+    """LR-mode sliding window over in-memory sheets, every tile a validation item: ``SlidingSheetDataset(lr_scale=-1, val_split=1)`` under
+    the short signature ``predict_images`` is given sheets with (tiles row-major, ``stride = hr_res - overlap``, trailing remainders
+    dropped, names ``{name}_{tile}_0``)."""
 
-
-def _read_sheets(path, files):
-    """Every file as a uint8 stack [F, H, W] through Pillow (multi-page tifs: one frame per page), sizes free."""
-    from PIL import Image
-    sheets = []
-    for f in files:
-        with Image.open(Path(path, f)) as im:
-            frames = []
-            for k in range(getattr(im, "n_frames", 1)):
-                im.seek(k)
-                frames.append(np.asarray(im.convert("L"), dtype=np.uint8))
-        sheets.append(np.stack(frames))
-    return sheets
+    def __init__(self, sheets, hr_res=128, overlap=32, names=None, transforms=None):
+        super().__init__(sheets, hr_res, -1, None, overlap, val_split=1, transforms=transforms, names=names)
 
 
 class SlidingDataset(SlidingSheetDataset):
@@ -612,19 +576,19 @@ class SlidingDataset(SlidingSheetDataset):
     def __init__(self, path, hr_res=512, lr_scale=4, crappifier=Poisson(), overlap=128, n_frames=-1, slide=False, stack="TZ",
                  extension="tif", preload=True, val_split=0.1, rotation=True, split_seed=0, extra_path=None, extra_scale=1,
                  transforms=None):
-        self.path, self.hr_files = _sheet_files(path, extension)
+        self.path, self.hr_files = _find_files(path, extension, sheets=True)
         if extra_path is not None:
             raise NotImplementedError("extra_path is not supported by pssr2_amd.SlidingDataset")
         self.stack, self.mode, self.preload, self.extra_path, self.extra_scale = stack.upper(), "L", preload, None, extra_scale
         _check_stride(hr_res, overlap)          # before any file is read, as upstream
         super().__init__(_read_sheets(self.path, self.hr_files), hr_res, lr_scale, crappifier, overlap, n_frames, slide, val_split, rotation,
-                         split_seed, transforms, [f.split(".")[0] for f in self.hr_files])
+                         split_seed, transforms, _file_names(self.hr_files))
 
-    def __repr__(self):
-        return f'SlidingDataset from path "{self.path}"\n{len(self.hr_files)} files with {len(self)} total frame slices\n{self._res_line()}'
+    def _summary(self):
+        return f'SlidingDataset from path "{self.path}"\n{len(self.hr_files)} files'
 
 
-class PairedSlidingArrayDataset(Dataset):
+class PairedSlidingArrayDataset(_SheetIndex):
     """Real (HR, LR) sheet pairs in memory (uint8 [F, H, W] / [f, h, w] each): the reference's ``PairedSlidingDataset``
     (pssr/data.py:348-444) without the files -- its defaults (``val_split=1``, ``split_seed=None``), attribute protocol and item geometry
     (``_transform_pair``), for ``train_crappifier``, ``approximate_crappifier`` and ``test_metrics``.  Windows, slices and the split are
@@ -634,24 +598,14 @@ class PairedSlidingArrayDataset(Dataset):
 
     def __init__(self, hr_sheets, lr_sheets, hr_res=512, lr_scale=4, overlap=128, n_frames=-1, slide=False, val_split=1, rotation=True,
                  split_seed=None, transforms=None, names=None):
-        keep = getattr(self, "_keep_tensors", False)
-        self.hr_sheets, self.lr_sheets = _sheet_list(hr_sheets, type(self).__name__, keep), _sheet_list(lr_sheets, type(self).__name__, keep)
-        if len(self.hr_sheets) != len(self.lr_sheets):
-            raise ValueError(f"Mismatch between amounts of high-low-resolution images. Found {len(self.hr_sheets)} high-resolution and "
-                             f"{len(self.lr_sheets)} low-resolution images.")
+        who = type(self).__name__
+        self.hr_sheets, self.lr_sheets = _check_paired(_sheet_list(hr_sheets, who, self._keep_tensors), _sheet_list(lr_sheets, who, self._keep_tensors))
         self.stride = _check_stride(hr_res, overlap)
         self.n_frames, self.slide = _get_n_frames(n_frames), slide
         self.tiles, self.slices = _tiles_slices(self.hr_sheets, hr_res, self.stride, self.n_frames, slide)
         self.val_idx = _get_val_idx(self.slices, val_split, split_seed, self.tiles)
-        self.is_lr, self.crop_res, self.extra_hr_files = False, hr_res, None
-        self.hr_res, self.lr_scale, self.rotation, self.transforms = hr_res, lr_scale, rotation, transforms
-        self.compact = False        # see ArrayDataset.compact
-        self.names = list(names) if names is not None else [f"sheet{i}" for i in range(len(self.hr_sheets))]
-
-    __len__ = SlidingSheetDataset.__len__
-    _check_idx = SlidingSheetDataset._check_idx
-    _draw_rotation = SlidingSheetDataset._draw_rotation
-    _get_name = SlidingSheetDataset._get_name
+        self.is_lr, self.crop_res = False, hr_res
+        self._set_protocol(hr_res, lr_scale, rotation, transforms, names, "sheet", len(self.hr_sheets))
 
     def _side_args(self, idx):
         """Per side (HR, LR): (sheet, size, stride, frames, slices of the sheet, in-sheet index, slide) as ``_sliding_window`` takes them."""
@@ -661,15 +615,13 @@ class PairedSlidingArrayDataset(Dataset):
                 (self.lr_sheets[image_idx], self.hr_res // self.lr_scale, self.stride // self.lr_scale, nf[0] if nf is not None else None,
                  self.slices[image_idx], local, self.slide))
 
-    def __getitem__(self, idx, pp=False):
-        self._check_idx(idx)
+    def _item(self, idx, rot):
         hr_args, lr_args = self._side_args(idx)
-        return _transform_pair(_sliding_window(*hr_args), _sliding_window(*lr_args), self.hr_res, self.hr_res // self.lr_scale,
-                               self._draw_rotation(idx, pp), self.transforms, self.n_frames, getattr(self, "compact", False))
+        return _transform_pair(_sliding_window(*hr_args), _sliding_window(*lr_args), self.hr_res, self.hr_res // self.lr_scale, rot,
+                               self.transforms, self.n_frames, self.compact)
 
-    def __repr__(self):
-        return (f"{type(self).__name__} of {len(self.hr_sheets)} paired sheets with {len(self)} total frame slices\n"
-                f"high-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}")
+    def _summary(self):
+        return f"{type(self).__name__} of {len(self.hr_sheets)} paired sheets"
 
 
 class PairedSlidingDataset(PairedSlidingArrayDataset):
@@ -679,24 +631,14 @@ class PairedSlidingDataset(PairedSlidingArrayDataset):
 
     def __init__(self, hr_path, lr_path, hr_res=512, lr_scale=4, overlap=128, n_frames=-1, slide=False, stack="TZ", extension="tif",
                  preload=True, val_split=1, rotation=True, split_seed=None, transforms=None):
-        for path in (hr_path, lr_path):
-            path = Path(path) if type(path) is str else path
-            if not path or not path.exists():
-                raise FileNotFoundError(f'Path "{path}" does not exist.')
-        if (Path(hr_path) if type(hr_path) is str else hr_path) == (Path(lr_path) if type(lr_path) is str else lr_path):
-            warnings.warn("hr_path is equal to lr_path! Consider using SlidingDataset instead.", stacklevel=2)
-        (self.hr_path, self.hr_files), (self.lr_path, self.lr_files) = _sheet_files(hr_path, extension), _sheet_files(lr_path, extension)
-        if len(self.hr_files) != len(self.lr_files):
-            raise FileNotFoundError(f"Mismatch between amounts of high-low-resolution images. Found {len(self.hr_files)} high-resolution "
-                                    f"and {len(self.lr_files)} low-resolution images.")
+        (self.hr_path, self.hr_files), (self.lr_path, self.lr_files) = _find_paired_files(hr_path, lr_path, extension, "SlidingDataset", sheets=True)
         self.stack, self.mode, self.preload = stack.upper(), "L", preload
         _check_stride(hr_res, overlap)
         super().__init__(_read_sheets(self.hr_path, self.hr_files), _read_sheets(self.lr_path, self.lr_files), hr_res, lr_scale, overlap,
-                         n_frames, slide, val_split, rotation, split_seed, transforms, [f.split(".")[0] for f in self.lr_files])
+                         n_frames, slide, val_split, rotation, split_seed, transforms, _file_names(self.lr_files))
 
-    def __repr__(self):
-        return (f'PairedSlidingDataset from paths "{self.hr_path}" and "{self.lr_path}"\n{len(self.hr_files)} paired files with {len(self)} '
-                f"total frame slices\nhigh-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}")
+    def _summary(self):
+        return f'PairedSlidingDataset from paths "{self.hr_path}" and "{self.lr_path}"\n{len(self.hr_files)} paired files'
 
 
 def _save_stack(path, stack):
@@ -826,18 +768,30 @@ class DevicePairGenerator:
         return self(ops.gen_pair_geometry_u8(stacks, rotations, hr_res), tile_offset)
 
 
-def _gather_rows(entries, device):
-    """int64 [n, 3] device rows (= n ``pssr_gather_item``) from (src address, sh, sw, ``False`` / ``[rot, axis]`` draw) entries."""
+def _pack_rows(head, entries):
+    """int64 [n, 3] host rows, one 24-byte kernel item per entry: its leading fields as the struct format ``head`` says, then the rot90 flag
+    and the flip axis (-1: none, 3: both) of its ``False`` / ``[rot, axis]`` draw.  One ``struct.pack`` over all entries."""
     import struct
-    buf = bytearray()
-    for src, h, w, rot in entries:
-        axis = -1
-        if rot:
-            axis = 3 if isinstance(rot[1], (tuple, list)) else int(rot[1])
-        buf += struct.pack("<Qiiii", src, h, w, int(bool(rot and rot[0])), axis)
-    if not buf:                        # an empty order (val_split = 0, a rank without validation items): torch.frombuffer rejects b""
-        return torch.zeros(0, 3, dtype=torch.int64, device=device)
-    return torch.frombuffer(buf, dtype=torch.int64).view(-1, 3).to(device)
+    flat = []
+    for entry in entries:
+        rot = entry[-1]
+        flat += entry[:-1]
+        flat += (1 if rot[0] else 0, 3 if isinstance(rot[1], (tuple, list)) else int(rot[1])) if rot else (0, -1)
+    if not flat:                       # an empty order (val_split = 0, a rank without validation items): torch.frombuffer rejects b""
+        return torch.zeros(0, 3, dtype=torch.int64)
+    buf = bytearray(24 * len(entries))
+    struct.pack_into("<" + (head + "ii") * len(entries), buf, 0, *flat)
+    return torch.frombuffer(buf, dtype=torch.int64).view(-1, 3)
+
+
+def _gather_rows(entries, device):
+    """int64 [n, 3] device rows (= n ``pssr_gather_item`` {src, sh, sw, rot, flip_axis}) from (src address, sh, sw, draw) entries."""
+    return _pack_rows("Qii", entries).to(device)
+
+
+def _window_rows(entries):
+    """int64 [n, 3] rows (= n ``pssr_window_item`` {sheet, frame0, y0, x0, rot, flip_axis}) from (sheet, frame0, y0, x0, draw) entries; host tensor."""
+    return _pack_rows("iiii", entries)
 
 
 def _gather_table(images, indices, rotations):
@@ -847,180 +801,12 @@ def _gather_table(images, indices, rotations):
     return _gather_rows([(base + int(i) * stride, h, w, rot) for i, rot in zip(indices, rotations)], images.device)
 
 
-class DeviceTileDataset(Dataset):
-    """``ArrayDataset`` whose uint8 HR stacks live in HBM: same constructor arguments, same attribute protocol
-    (``val_idx``, ``extra_hr_files``, ``crop_res``, ``lr_scale``, ``is_lr``, ``hr_res``, ``n_frames``, ``_get_name``) and the same
-    ``__getitem__`` contract (float32 CHW tensors, here already on the device), so ``train_paired`` / ``predict_images`` /
-    ``test_metrics`` take it like any dataset.  In addition it can produce whole batches without touching the host
-    (``draw_items`` + ``device_batch``): ``_gen_pair``'s crop / reflect pad / rot90 / flip (host-drawn in the reference's order,
-    applied by one gather kernel), the Pillow-exact reduction and the crappifier (device Philox streams) as HIP launches whose
-    only per-step inputs are device tensors -- which is what lets ``train_paired`` replay a whole training step as one hipGraph
-    (pssr2_amd/fastpath.py).  Noise comes from the device generator: statistically, not bitwise, the numpy stream of the host path.
-
-    Stacks of differing depths and sizes (a sequence of [C_i, H_i, W_i]) each stay their own tensor in HBM.  With ``n_frames`` an item is
-    a frame slice of its file exactly as in ``ArrayDataset`` -- for the gather kernel that is an address (``k * m * H_i * W_i`` bytes into
-    the stack) and the file's own size, so a batch mixes slices of files of any sizes; with ``n_frames=[lr, hr]`` the centre frames of
-    each side are taken after the generator, as ``_gen_pair`` does.  ``n_frames=-1`` needs one depth over all files (a batch has one)."""
-
-    def __init__(self, images, hr_res=512, lr_scale=4, crappifier=Poisson(), val_split=0.1, rotation=True, split_seed=0,
-                 transforms=None, names=None, n_frames=-1, device="cuda", seed=0):
-        if transforms is not None:
-            raise NotImplementedError("DeviceTileDataset applies no host transforms")
-        images = _tile_stacks(images, "DeviceTileDataset", keep_tensors=True)
-        if isinstance(images, list):
-            self.images = [torch.as_tensor(s).to(device).contiguous() for s in images]
-        else:
-            self.images = torch.as_tensor(images).to(device).contiguous()
-        lr_scale = None if lr_scale == -1 else lr_scale
-        self.n_frames = _get_n_frames(n_frames)
-        shapes = _stack_shapes(self.images)
-        self.slices = _stack_slices(shapes, self.n_frames)
-        self.depth = max(self.n_frames) if self.n_frames is not None else _uniform_frames(shapes, "DeviceTileDataset", "stacks")
-        max_size = _max_extent(shapes)
-        self.val_idx = _get_val_idx(self.slices, val_split, split_seed)
-        self.crop_res = min(hr_res, max_size)
-        self.is_lr = lr_scale is None or max_size <= hr_res // lr_scale
-        self.hr_res, self.lr_scale = hr_res, lr_scale if lr_scale is not None else 1
-        self.crappifier, self.rotation, self.transforms = crappifier, rotation, None
-        self.extra_hr_files = None
-        self.names = names if names is not None else [f"image{i}" for i in range(len(self.images))]
-        self._val_set, self._val_key = set(self.val_idx), None
-        self.device = self.images[0].device if isinstance(self.images, list) else self.images.device
-        self.tile_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.gen = DevicePairGenerator(self.lr_scale, crappifier, seed=seed, tile_counter=self.tile_counter)
-        self._item_bytes = 24             # struct pssr_gather_item {src, sh, sw, rot, flip_axis}
-        # per dataset index (file, slice k, address of the slice's first frame, the file's H, W), in _get_image_idx's order: every read of
-        # the gather kernel, depth frames of H x W bytes from that address, lies inside the file's stack since (k + 1) * depth <= frames
-        if isinstance(self.images, list):
-            bases = [s.data_ptr() for s in self.images]
-        else:
-            bases = [self.images.data_ptr() + f * self.images[0].numel() for f in range(len(self.images))]
-        self._where = [(f, k, base + k * self.depth * h * w, h, w)
-                       for f, (base, (_, h, w), n) in enumerate(zip(bases, shapes, self.slices)) for k in range(n)]
-
-    def __len__(self):
-        return len(self._where)
-
-    def _get_name(self, idx):
-        if self.n_frames is None:
-            return self.names[idx]
-        f, k = self._where[idx][:2]
-        return f"{self.names[f]}_{k}"
-
-    def _res_line(self):
-        return f"low-res: {self.hr_res // self.lr_scale}" if self.is_lr else f"high-res: {self.hr_res}, low-res: {self.hr_res // self.lr_scale}"
-
-    def __repr__(self):
-        return f"{type(self).__name__} of {len(self.images)} images with {len(self)} total frame slices\n{self._res_line()}"
-
-    def _draw_rotation(self, idx, pp=False):
-        # ``idx in self.val_idx`` as upstream (pssr/data.py:103), with the list hashed once per assignment / length change: users enlarge
-        # val_idx after training to predict every image
-        key = (id(self.val_idx), len(self.val_idx))
-        if key != self._val_key:
-            self._val_set, self._val_key = set(self.val_idx), key
-        if self.rotation and not (idx in self._val_set or pp):
-            return [bool(random.getrandbits(1)), random.choice((1, 2, (1, 2)))]      # the reference's draws, in its order
-        return False
-
-    def draw_items(self, indices, pp=False):
-        """Gather table (int64 [n, 3] on the device = n ``pssr_gather_item``) for these dataset indices, drawing the training
-        rotations exactly as ``__getitem__`` would for the same sequence of indices (none with ``pp``).  An index outside the dataset
-        raises ``IndexError`` before anything is drawn: a row is an address the kernel reads from."""
-        indices = [int(i) for i in indices]
-        for i in indices:
-            if not 0 <= i < len(self):
-                raise IndexError(f"Tried to retrieve invalid image. Index {i} is not less than {len(self)} total image frame slices.")
-        return _gather_rows([self._where[i][2:] + (self._draw_rotation(i, pp),) for i in indices], self.device)
-
-    def device_batch(self, items):
-        """items: int64 [b, 3] device rows of ``draw_items``.  Returns float32 (hr, lr) on the device, or lr alone in LR mode.  No
-        host synchronisation, no host-side data: capturable in a hipGraph (the Philox tile counter advances on the device)."""
-        from . import _lib as L, ops
-        b, c = items.shape[0], self.depth
-        res = self.hr_res // self.lr_scale if self.is_lr else self.hr_res
-        out = torch.empty(b, c, res, res, dtype=torch.uint8, device=self.device)
-        L.check(L.lib().pssr_gen_pair_geometry_u8(L.ptr(items), b, L.ptr(out), c, res, L.stream_ptr()), "pssr_gen_pair_geometry_u8")
-        if self.is_lr:
-            return ops.u8_to_f32(out)
-        hr, lr = self.gen(out)
-        ops.counter_add(self.tile_counter, b)
-        nf = self.n_frames
-        if nf is not None and nf[0] != nf[1]:           # centre frames of each side, as _gen_pair
-            if not nf[1] > hr.shape[-3]:
-                hr = _slice_center(hr, nf[1]).contiguous()
-            if not nf[0] > lr.shape[-3]:
-                lr = _slice_center(lr, nf[0]).contiguous()
-        return hr, lr
-
-    def __getitem__(self, idx, pp=False):
-        if idx >= len(self):
-            raise IndexError(f"Tried to retrieve invalid image. Index {idx} is not less than {len(self)} total image frame slices.")
-        out = self.device_batch(self.draw_items([idx], pp))
-        return out[0] if self.is_lr else (out[0][0], out[1][0])
-
-
-class DevicePairedTileDataset(PairedArrayDataset):
-    """``PairedArrayDataset`` whose two uint8 stacks live in HBM: same arguments, attributes and item values (float32 CHW tensors, here on
-    the device), so the drivers take it like any dataset whose items need no host-to-device copy.  Whole batches come from one host
-    draw (``draw_pair_items``: the reference's rotation draws, index by index) and two launches of the ``_gen_pair`` gather kernel
-    (``device_pair_batch``: one table per side, the same (rot, flip) per item).  These are deliberately not DeviceTileDataset's
-    ``draw_items`` / ``device_batch``: the hipGraph replay of ``train_paired`` (pssr2_amd/fastpath.py) does not cover real pairs."""
-    _keep_tensors = True        # stacks already in HBM stay there
-
-    def __init__(self, hr_images, lr_images, hr_res=512, lr_scale=4, n_frames=-1, val_split=1, rotation=True, split_seed=None,
-                 transforms=None, names=None, device="cuda"):
-        if transforms is not None:
-            raise NotImplementedError("DevicePairedTileDataset applies no host transforms")
-        super().__init__(hr_images, lr_images, hr_res, lr_scale, n_frames, val_split, rotation, split_seed, None, names)
-        self.hr_images = torch.as_tensor(self.hr_images).to(device).contiguous()
-        self.lr_images = torch.as_tensor(self.lr_images).to(device).contiguous()
-        if not self.hr_images.is_cuda:
-            raise RuntimeError("DevicePairedTileDataset keeps its images on an MI355X (HIP) device; there is no CPU fallback")
-        del self.compact            # items are float32 device tensors: the host feed has nothing to compact
-
-    def draw_pair_items(self, indices, pp=False):
-        """(HR table, LR table) for these dataset indices: the training rotations are drawn exactly as ``__getitem__`` would draw them
-        for the same sequence of indices, and each draw is written to both tables."""
-        indices = [int(i) for i in indices]
-        for i in indices:
-            if i >= len(self):
-                raise IndexError(f"Tried to retrieve invalid image. Index {i} is not less than {len(self)} total image frame slices.")
-        rots = [self._draw_rotation(i, pp) for i in indices]
-        return _gather_table(self.hr_images, indices, rots), _gather_table(self.lr_images, indices, rots)
-
-    def device_pair_batch(self, tables, u8=False):
-        """tables: ``draw_pair_items``' result.  float32 (uint8 with ``u8``) (hr [b, C, R, R], lr [b, c, r, r]) on the device, no host
-        synchronisation."""
-        from . import _lib as L, ops
-        out = []
-        for table, images, res, keep in zip(tables, (self.hr_images, self.lr_images), (self.hr_res, self.hr_res // self.lr_scale), (1, 0)):
-            b, c = table.shape[0], images.shape[1]
-            side = torch.empty(b, c, res, res, dtype=torch.uint8, device=images.device)
-            if b:
-                L.check(L.lib().pssr_gen_pair_geometry_u8(L.ptr(table), b, L.ptr(side), c, res, L.stream_ptr()), "pssr_gen_pair_geometry_u8")
-            if self.n_frames is not None and self.n_frames[0] != self.n_frames[1] and not self.n_frames[keep] > c:
-                side = _slice_center(side, self.n_frames[keep]).contiguous()
-            out.append(side if u8 or not b else ops.u8_to_f32(side))
-        return tuple(out)
-
-    def __getitem__(self, idx, pp=False):
-        hr, lr = self.device_pair_batch(self.draw_pair_items([idx], pp))
-        return hr[0], lr[0]
-
-
-def _window_rows(entries):
-    """int64 [n, 3] rows (= n ``pssr_window_item``) from (sheet, frame0, y0, x0, rotation draw) entries; host tensor."""
-    import struct
-    buf = bytearray()
-    for sheet, frame0, y0, x0, rot in entries:
-        axis = -1
-        if rot:
-            axis = 3 if isinstance(rot[1], (tuple, list)) else int(rot[1])
-        buf += struct.pack("<iiiiii", sheet, frame0, y0, x0, int(bool(rot and rot[0])), axis)
-    if not buf:                        # an empty order: torch.frombuffer rejects b""
-        return torch.zeros(0, 3, dtype=torch.int64)
-    return torch.frombuffer(buf, dtype=torch.int64).view(-1, 3)
+def _gen_pair_geometry_u8(items, depth, res, device):
+    """uint8 [b, depth, res, res]: one launch of the ``_gen_pair`` gather kernel over the int64 [b, 3] device rows ``items``."""
+    from . import _lib as L
+    out = torch.empty(items.shape[0], depth, res, res, dtype=torch.uint8, device=device)
+    L.check(L.lib().pssr_gen_pair_geometry_u8(L.ptr(items), items.shape[0], L.ptr(out), depth, res, L.stream_ptr()), "pssr_gen_pair_geometry_u8")
+    return out
 
 
 class _SheetBank:
@@ -1056,35 +842,169 @@ def _uniform_frames(sheets, who, what="sheets"):
     return frames.pop()
 
 
-class DeviceSlidingDataset(SlidingSheetDataset):
+class _DeviceItems:
+    """What the four HBM-resident classes put in front of their host class: inputs stay tensors, items are float32 device tensors (no
+    ``compact``), no host transforms, and every index is checked before it becomes a row of a kernel's table."""
+    _keep_tensors, _host_items = True, False
+
+    def _no_transforms(self, transforms):
+        if transforms is not None:
+            raise NotImplementedError(f"{type(self).__name__} applies no host transforms")
+
+    def _row_indices(self, indices):
+        """The indices as ints; one outside the dataset raises ``IndexError`` before anything is drawn: a row is an address the kernel reads from."""
+        indices, n = [int(i) for i in indices], len(self)
+        for i in indices:
+            if not 0 <= i < n:
+                self._check_idx(i, row=True)
+        return indices
+
+
+class _DeviceSynthesis(_DeviceItems):
+    """The half that ``DeviceTileDataset`` and ``DeviceSlidingDataset`` share: everything after their uint8 HR batch [b, depth, R, R] is
+    gathered (``_gather_u8`` over the rows of their ``draw_items``)."""
+
+    def _set_generator(self, device, seed):
+        self.tile_counter = torch.zeros(1, dtype=torch.int64, device=device)
+        self.gen = DevicePairGenerator(self.lr_scale, self.crappifier, seed=seed, tile_counter=self.tile_counter)
+
+    def device_batch(self, items):
+        """items: int64 [b, 3] device rows of ``draw_items``.  Returns float32 (hr, lr) on the device, or lr alone in LR mode.  No
+        host synchronisation, no host-side data: capturable in a hipGraph (the Philox tile counter advances on the device)."""
+        from . import ops
+        out = self._gather_u8(items)
+        if self.is_lr:
+            return ops.u8_to_f32(out)
+        pair = self.gen(out)
+        ops.counter_add(self.tile_counter, items.shape[0])
+        hr, lr = _center_frames(pair, self.n_frames)           # centre frames of each side, as _gen_pair
+        return hr.contiguous(), lr.contiguous()
+
+    def __getitem__(self, idx, pp=False):
+        out = self.device_batch(self.draw_items([idx], pp))
+        return out[0] if self.is_lr else (out[0][0], out[1][0])
+
+
+class _DevicePairs(_DeviceItems):
+    """The half that the two paired device classes share: ``device_pair_batch`` around their ``_gather_u8(side, table, depth, res)``;
+    ``depths``: frames per side (HR, LR) of what that gathers."""
+
+    def device_pair_batch(self, tables, u8=False):
+        """tables: ``draw_pair_items``' result.  float32 (uint8 with ``u8``, and for an empty table) (hr [b, C, R, R], lr [b, c, r, r]) on
+        the device, no host synchronisation; with ``n_frames=[lr, hr]`` the centre frames of each side, as ``_transform_pair``."""
+        from . import ops
+        sides = []
+        for side, (table, depth, res) in enumerate(zip(tables, self.depths, (self.hr_res, self.hr_res // self.lr_scale))):
+            if table.shape[0]:
+                sides.append(self._gather_u8(side, table, depth, res))
+            else:
+                sides.append(torch.empty(0, depth, res, res, dtype=torch.uint8, device=table.device))
+        sides = [s.contiguous() for s in _center_frames(sides, self.n_frames)]
+        return tuple(s if u8 or not s.shape[0] else ops.u8_to_f32(s) for s in sides)
+
+    def __getitem__(self, idx, pp=False):
+        hr, lr = self.device_pair_batch(self.draw_pair_items([idx], pp))
+        return hr[0], lr[0]
+
+
+class DeviceTileDataset(_DeviceSynthesis, ArrayDataset):
+    """``ArrayDataset`` whose uint8 HR stacks live in HBM: same constructor arguments, same attribute protocol
+    (``val_idx``, ``extra_hr_files``, ``crop_res``, ``lr_scale``, ``is_lr``, ``hr_res``, ``n_frames``, ``_get_name``) and the same
+    ``__getitem__`` contract (float32 CHW tensors, here already on the device), so ``train_paired`` / ``predict_images`` /
+    ``test_metrics`` take it like any dataset.  In addition it can produce whole batches without touching the host
+    (``draw_items`` + ``device_batch``): ``_gen_pair``'s crop / reflect pad / rot90 / flip (host-drawn in the reference's order,
+    applied by one gather kernel), the Pillow-exact reduction and the crappifier (device Philox streams) as HIP launches whose
+    only per-step inputs are device tensors -- which is what lets ``train_paired`` replay a whole training step as one hipGraph
+    (pssr2_amd/fastpath.py).  Noise comes from the device generator: statistically, not bitwise, the numpy stream of the host path.
+
+    Stacks of differing depths and sizes (a sequence of [C_i, H_i, W_i]) each stay their own tensor in HBM.  With ``n_frames`` an item is
+    a frame slice of its file exactly as in ``ArrayDataset`` -- for the gather kernel that is an address (``k * m * H_i * W_i`` bytes into
+    the stack) and the file's own size, so a batch mixes slices of files of any sizes; with ``n_frames=[lr, hr]`` the centre frames of
+    each side are taken after the generator, as ``_gen_pair`` does.  ``n_frames=-1`` needs one depth over all files (a batch has one)."""
+
+    def __init__(self, images, hr_res=512, lr_scale=4, crappifier=Poisson(), val_split=0.1, rotation=True, split_seed=0,
+                 transforms=None, names=None, n_frames=-1, device="cuda", seed=0):
+        self._no_transforms(transforms)
+        super().__init__(images, hr_res, lr_scale, crappifier, val_split, rotation, split_seed, None, names, n_frames)
+        if isinstance(self.images, list):
+            self.images = [torch.as_tensor(s).to(device).contiguous() for s in self.images]
+        else:
+            self.images = torch.as_tensor(self.images).to(device).contiguous()
+        shapes = _stack_shapes(self.images)
+        self.depth = max(self.n_frames) if self.n_frames is not None else _uniform_frames(shapes, type(self).__name__, "stacks")
+        self.device = self.images[0].device if isinstance(self.images, list) else self.images.device
+        self._set_generator(self.device, seed)
+        # per dataset index (file, slice k, address of the slice's first frame, the file's H, W), in _get_image_idx's order: every read of
+        # the gather kernel, depth frames of H x W bytes from that address, lies inside the file's stack since (k + 1) * depth <= frames
+        if isinstance(self.images, list):
+            bases = [s.data_ptr() for s in self.images]
+        else:
+            bases = [self.images.data_ptr() + f * self.images[0].numel() for f in range(len(self.images))]
+        self._where = [(f, k, base + k * self.depth * h * w, h, w)
+                       for f, (base, (_, h, w), n) in enumerate(zip(bases, shapes, self.slices)) for k in range(n)]
+
+    def __len__(self):
+        return len(self._where)
+
+    def draw_items(self, indices, pp=False):
+        """Gather table (int64 [n, 3] on the device = n ``pssr_gather_item``) for these dataset indices, drawing the training
+        rotations exactly as ``__getitem__`` would for the same sequence of indices (none with ``pp``)."""
+        return _gather_rows([self._where[i][2:] + (self._draw_rotation(i, pp),) for i in self._row_indices(indices)], self.device)
+
+    def _gather_u8(self, items):
+        return _gen_pair_geometry_u8(items, self.depth, self.hr_res // self.lr_scale if self.is_lr else self.hr_res, self.device)
+
+
+class DevicePairedTileDataset(_DevicePairs, PairedArrayDataset):
+    """``PairedArrayDataset`` whose two uint8 stacks live in HBM: same arguments, attributes and item values (float32 CHW tensors, here on
+    the device), so the drivers take it like any dataset whose items need no host-to-device copy.  Whole batches come from one host
+    draw (``draw_pair_items``: the reference's rotation draws, index by index) and two launches of the ``_gen_pair`` gather kernel
+    (``device_pair_batch``: one table per side, the same (rot, flip) per item).  These are deliberately not DeviceTileDataset's
+    ``draw_items`` / ``device_batch``: the hipGraph replay of ``train_paired`` (pssr2_amd/fastpath.py) does not cover real pairs."""
+
+    def __init__(self, hr_images, lr_images, hr_res=512, lr_scale=4, n_frames=-1, val_split=1, rotation=True, split_seed=None,
+                 transforms=None, names=None, device="cuda"):
+        self._no_transforms(transforms)
+        super().__init__(hr_images, lr_images, hr_res, lr_scale, n_frames, val_split, rotation, split_seed, None, names)
+        self.hr_images = torch.as_tensor(self.hr_images).to(device).contiguous()
+        self.lr_images = torch.as_tensor(self.lr_images).to(device).contiguous()
+        if not self.hr_images.is_cuda:
+            raise RuntimeError("DevicePairedTileDataset keeps its images on an MI355X (HIP) device; there is no CPU fallback")
+        self.depths = (self.hr_images.shape[1], self.lr_images.shape[1])
+
+    def draw_pair_items(self, indices, pp=False):
+        """(HR table, LR table) for these dataset indices: the training rotations are drawn exactly as ``__getitem__`` would draw them
+        for the same sequence of indices, and each draw is written to both tables."""
+        indices = self._row_indices(indices)
+        rots = [self._draw_rotation(i, pp) for i in indices]
+        return _gather_table(self.hr_images, indices, rots), _gather_table(self.lr_images, indices, rots)
+
+    def _gather_u8(self, side, table, depth, res):
+        return _gen_pair_geometry_u8(table, depth, res, table.device)
+
+
+class DeviceSlidingDataset(_DeviceSynthesis, SlidingSheetDataset):
     """``SlidingSheetDataset`` whose sheets live in HBM: same arguments, attributes and item values (float32 CHW tensors, here on the
     device).  Like ``DeviceTileDataset`` it makes whole batches without touching the host -- ``draw_items`` (the reference's rotation
     draws, index by index, and each window's origin: one ``pssr_window_item`` per index) and ``device_batch`` (one window gather out of
     the sheets, then the Pillow-exact reduction and the crappifier on device Philox streams) -- so ``train_paired`` replays a whole
     training step over sheets as one hipGraph (pssr2_amd/fastpath.py).  With ``n_frames=-1`` every sheet must have the same number of
     frames (a batch has one depth); host transforms are not applied."""
-    _keep_tensors = True        # sheets already in HBM stay there
 
     def __init__(self, sheets, hr_res=512, lr_scale=4, crappifier=Poisson(), overlap=128, n_frames=-1, slide=False, val_split=0.1,
                  rotation=True, split_seed=0, transforms=None, names=None, device="cuda", seed=0):
-        if transforms is not None:
-            raise NotImplementedError("DeviceSlidingDataset applies no host transforms")
+        self._no_transforms(transforms)
         super().__init__(sheets, hr_res, lr_scale, crappifier, overlap, n_frames, slide, val_split, rotation, split_seed, None, names)
         self.depth = max(self.n_frames) if self.n_frames is not None else _uniform_frames(self.sheets, type(self).__name__)
         self.bank = _SheetBank(self.sheets, device, type(self).__name__)
         self.sheets = self.bank.sheets
-        del self.compact            # items are float32 device tensors: the host feed has nothing to compact
-        self.tile_counter = torch.zeros(1, dtype=torch.int64, device=self.bank.device)
-        self.gen = DevicePairGenerator(self.lr_scale, crappifier, seed=seed, tile_counter=self.tile_counter)
-        self._item_bytes = 24             # struct pssr_window_item {sheet, frame0, y0, x0, rot, flip_axis}
+        self._set_generator(self.bank.device, seed)
 
     def draw_items(self, indices, pp=False):
         """Window table (int64 [n, 3] on the device = n ``pssr_window_item``) for these dataset indices, drawing the training rotations
         exactly as ``__getitem__`` would for the same sequence of indices.  Every window is checked against its sheet here."""
         entries = []
-        for idx in indices:
-            idx = int(idx)
-            self._check_idx(idx)
+        for idx in self._row_indices(indices):
             image_idx, local = _get_image_idx(idx, self.slices, self.tiles)
             origin = _window_origin(self.sheets[image_idx], self.hr_res, self.stride, None if self.n_frames is None else self.depth,
                                     self.slices[image_idx], local, self.slide)
@@ -1092,52 +1012,30 @@ class DeviceSlidingDataset(SlidingSheetDataset):
             entries.append((image_idx, *origin, self._draw_rotation(idx, pp)))
         return _window_rows(entries).to(self.bank.device)
 
-    def device_batch(self, items):
-        """items: int64 [b, 3] device rows of ``draw_items``.  Returns float32 (hr, lr) on the device, or lr alone in LR mode.  No host
-        synchronisation, no host-side data: capturable in a hipGraph (the Philox tile counter advances on the device)."""
-        from . import ops
-        out = self.bank.gather(items, self.depth, self.hr_res)
-        if self.is_lr:
-            return ops.u8_to_f32(out)
-        hr, lr = self.gen(out)
-        ops.counter_add(self.tile_counter, items.shape[0])
-        nf = self.n_frames
-        if nf is not None and nf[0] != nf[1]:           # centre frames of each side, as _gen_pair
-            if not nf[1] > hr.shape[-3]:
-                hr = _slice_center(hr, nf[1]).contiguous()
-            if not nf[0] > lr.shape[-3]:
-                lr = _slice_center(lr, nf[0]).contiguous()
-        return hr, lr
-
-    def __getitem__(self, idx, pp=False):
-        out = self.device_batch(self.draw_items([idx], pp))
-        return out[0] if self.is_lr else (out[0][0], out[1][0])
+    def _gather_u8(self, items):
+        return self.bank.gather(items, self.depth, self.hr_res)
 
 
-class DevicePairedSlidingDataset(PairedSlidingArrayDataset):
+class DevicePairedSlidingDataset(_DevicePairs, PairedSlidingArrayDataset):
     """``PairedSlidingArrayDataset`` whose sheets live in HBM: same arguments, attributes and item values (float32 CHW tensors, here on
     the device).  Whole batches come from one host draw (``draw_pair_items``) and two window gathers (``device_pair_batch``: one sheet
-    table and one item table per side, the same (rot, flip) per item), as ``DevicePairedTileDataset`` does for pre-cut pairs."""
-    _keep_tensors = True
+    table and one item table per side, the same (rot, flip) per item), as ``DevicePairedTileDataset`` does for pre-cut pairs.  Each side
+    is gathered at its own depth (``n_frames[1]`` / ``n_frames[0]``), which the centre-frame slicing leaves as it is."""
 
     def __init__(self, hr_sheets, lr_sheets, hr_res=512, lr_scale=4, overlap=128, n_frames=-1, slide=False, val_split=1, rotation=True,
                  split_seed=None, transforms=None, names=None, device="cuda"):
-        if transforms is not None:
-            raise NotImplementedError("DevicePairedSlidingDataset applies no host transforms")
+        self._no_transforms(transforms)
         super().__init__(hr_sheets, lr_sheets, hr_res, lr_scale, overlap, n_frames, slide, val_split, rotation, split_seed, None, names)
         who, nf = type(self).__name__, self.n_frames
         self.depths = (nf[1], nf[0]) if nf is not None else (_uniform_frames(self.hr_sheets, who), _uniform_frames(self.lr_sheets, who))
         self.banks = (_SheetBank(self.hr_sheets, device, who), _SheetBank(self.lr_sheets, device, who))
         self.hr_sheets, self.lr_sheets = self.banks[0].sheets, self.banks[1].sheets
-        del self.compact
 
     def draw_pair_items(self, indices, pp=False):
         """(HR table, LR table) for these dataset indices: the training rotations are drawn exactly as ``__getitem__`` would draw them for
         the same sequence of indices, and each draw is written to both tables.  Every window is checked against its sheet here."""
         entries = ([], [])
-        for idx in indices:
-            idx = int(idx)
-            self._check_idx(idx)
+        for idx in self._row_indices(indices):
             image_idx, _ = _get_image_idx(idx, self.slices, self.tiles)
             rot = self._draw_rotation(idx, pp)
             for side, bank, depth, (sheet, size, stride, frames, n_slices, local, slide) in zip(entries, self.banks, self.depths, self._side_args(idx)):
@@ -1146,20 +1044,5 @@ class DevicePairedSlidingDataset(PairedSlidingArrayDataset):
                 side.append((image_idx, *origin, rot))
         return tuple(_window_rows(side).to(bank.device) for side, bank in zip(entries, self.banks))
 
-    def device_pair_batch(self, tables, u8=False):
-        """tables: ``draw_pair_items``' result.  float32 (uint8 with ``u8``) (hr [b, C, R, R], lr [b, c, r, r]) on the device, no host
-        synchronisation.  Each side is gathered at its own depth (``n_frames[1]`` / ``n_frames[0]``), which ``_transform_pair``'s
-        centre-frame slicing leaves as it is."""
-        from . import ops
-        out = []
-        for table, bank, depth, res in zip(tables, self.banks, self.depths, (self.hr_res, self.hr_res // self.lr_scale)):
-            if table.shape[0]:
-                side = bank.gather(table, depth, res)
-            else:
-                side = torch.empty(0, depth, res, res, dtype=torch.uint8, device=bank.device)
-            out.append(side if u8 or not table.shape[0] else ops.u8_to_f32(side))
-        return tuple(out)
-
-    def __getitem__(self, idx, pp=False):
-        hr, lr = self.device_pair_batch(self.draw_pair_items([idx], pp))
-        return hr[0], lr[0]
+    def _gather_u8(self, side, table, depth, res):
+        return self.banks[side].gather(table, depth, res)
