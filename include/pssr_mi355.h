@@ -639,6 +639,22 @@ int pssr_head_conv_bwd_rows(const float* g_nchw, float g_scale, const float* w_o
                             int cin, int cout, int dtype, pssr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Backward of the flat-K (im2col) source of a wide convolution in ONE pass over its output gradient (csrc/pre_xcol_bwd.hip;
+ * Reconstruction.pre's input-image source, pssr/models/_blocks.py:10,16): for dy [npix][cout], x [npix][kx] and dx [npix][kx] in 16-bit
+ * storage (channel strides / offsets in elements) and the f32 weight window W1[k][j] = w[n_perm[k] * w_row + w_off + j]
+ * (j < nk <= kx, zero beyond; n_perm NULL: identity), rounded to storage as the packed weights are,
+ *   dx[p][j] = sum_k dy[p][k] W1[k][j]   (rounded to storage)      dw[k][j] = sum_p dy[p][k] x[p][j]   (f32 [cout][kx]; feed it to
+ *   pssr_unpack_conv_wgrad_parts as one part with k_pad = kx, which applies n_perm and the channel window of the OIHW gradient).
+ * Every workgroup stores one partial slab of dw into `slabs` (f32 [parts][cout][kx], parts = pssr_flatk_bwd_pair_parts(npix)) and a
+ * second launch sums the slabs in a fixed order: no floating-point atomics, the result is bit-reproducible.
+ * pssr_flatk_bwd_pair_supported: bf16 / f16, cout a multiple of 64 up to 1024, kx = 16. */
+int pssr_flatk_bwd_pair_supported(int dtype, int cout, int kx);
+int pssr_flatk_bwd_pair_parts(int64_t npix);
+int pssr_flatk_bwd_pair(const void* dy, int dy_cs, int dy_co, int cout, const void* x, int x_cs, int x_co, void* dx, int dx_cs,
+                        int dx_co, int kx, const float* w, int w_row, int w_off, int nk, const int32_t* n_perm, float* slabs,
+                        int parts, float* dw, int64_t npix, int dtype, pssr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Whole-sheet prediction on the device (BASELINE config 5).
  * pssr_sliding_tiles_u8: tiles [ntile][c][size][size] f32 = the row-major sliding windows tile0 .. tile0+ntile-1 of a uint8 sheet
  *   [c][h][w] (pssr/data.py:629-638 `_sliding_window` + `_tensor_ready`; stride = size - overlap; remainders dropped).

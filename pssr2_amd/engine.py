@@ -40,6 +40,7 @@ def _blocked_order(r: int):
 _NO_MATERIALISE = os.environ.get("PSSR_MATERIALISE", "0") != "1"
 _XCOL_SIDE = os.environ.get("PSSR_XCOL_SIDE", "0") == "1"
 _FUSE_DOUT = os.environ.get("PSSR_FUSE_DOUT", "1") != "0"
+_XCOL_FUSE = os.environ.get("PSSR_XCOL_FUSE", "1") != "0"
 _OVERWRITE_GRADS = os.environ.get("PSSR_OVERWRITE_GRADS", "1") != "0"
 _EVAL_SHUF = os.environ.get("PSSR_EVAL_SHUF", "1") != "0"         # eval mode: F.pixel_shuffle(x, 2) done by the producing conv's stores (FLAG_SHUF2)
 _EVAL_AFFINE = os.environ.get("PSSR_EVAL_AFFINE", "1") != "0"     # eval mode: BatchNorm + ReLU in the producing conv's epilogue (FLAG_AFFINE)
@@ -970,10 +971,26 @@ class Engine:
         gb_pre[self.pre_perm_long] = gpb
         grads[id(rec.pre.bias)] = gb_pre
         self._wgrad(p, grads, rec.pre, bw.dpre, cpre_n, feat, h0, 9, mode=0, ci_begin=0, ci_count=h0, n_perm=self.pre_perm, hh=h, ww=w)
-        self._wgrad(p, grads, rec.pre, bw.dpre, cpre_n, p.xcol, self.xc, 1, mode=2, ci_begin=h0, ci_count=self.cin, n_perm=self.pre_perm, hh=h, ww=w)
+        # the input-image source: its weight gradient and its data gradient are both 16-wide products with d(pre), the largest tensor of
+        # the step -- one launch reads it once for both (ops.flatk_bwd_pair; PSSR_XCOL_FUSE=0: the two separate launches, for A/B runs and
+        # the equivalence test)
+        fuse_x = _XCOL_FUSE and not self.atrous and not self.explicit_shuffle and ops.flatk_bwd_pair_supported(code, cpre_n, self.xc)
+        if fuse_x:
+            slot = grads[id(rec.pre.weight)]
+
+            def pair_x():
+                dw1 = ops.flatk_bwd_pair(bw.dpre, cpre_n, p.xcol, bw.dxcol_b, rec.pre.weight, code, ci_begin=h0, ci_count=self.cin, n_perm=self.pre_perm)
+                ops.unpack_conv_wgrad(dw1, slot, mode=2, ci_begin=h0, ci_count=self.cin, n_perm=self.pre_perm, k_pad=self.xc,
+                                      accumulate=not self._overwrite_grads)
+            if self._side_on:
+                self._on_side([bw.dpre, p.xcol, bw.dxcol_b], pair_x)       # _finish_input_norm waits for bw.dxcol_b (_before_write)
+            else:
+                pair_x()
+        else:
+            self._wgrad(p, grads, rec.pre, bw.dpre, cpre_n, p.xcol, self.xc, 1, mode=2, ci_begin=h0, ci_count=self.cin, n_perm=self.pre_perm, hh=h, ww=w)
         self._ready(grads, list(rec.parameters()))
         ops.conv2d(bw.dpre, cpre_n, self._pw_pre("dgrad0", code), dfeat, h0, n=n, h=h, w=w)
-        if not self.atrous:
+        if not self.atrous and not fuse_x:
             # the 16-channel data gradient of the input source only feeds the input BatchNorm's parameter gradients at the very end of the
             # pass: on the second stream it is off the dependent chain (the two queues of the backward phase end within 0.1 ms of each
             # other, so this pays only together with something that lightens the weight-gradient queue: PSSR_XCOL_SIDE)

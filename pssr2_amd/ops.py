@@ -564,6 +564,31 @@ def head_conv_bwd_rows(g, g_scale, weight, act, dact, blk, dw_rows, bias_rows, n
                                             blk, L.ptr(dw_rows), L.ptr(bias_rows), n, h, w, cin, cout, dtype, L.stream_ptr()), "pssr_head_conv_bwd_rows")
 
 
+def flatk_bwd_pair_supported(dtype, cout, kx):
+    """One pass over dy for both gradients of a flat-K source (flatk_bwd_pair): 16-bit storage, cout a multiple of 64 up to 1024, kx = 16."""
+    return bool(L.lib().pssr_flatk_bwd_pair_supported(dtype, cout, kx))
+
+
+def flatk_bwd_pair(dy, cout, x, dx, weight, dtype, *, ci_begin, ci_count, n_perm=None, dy_coff=0):
+    """dx = dy . W1 (rounded to storage) and dW1 = dy^T . x from ONE read of dy, for the flat-K window W1[k][j] = weight[n_perm[k], ci_begin
+    + j // ks^2, j % ks^2] (j < ci_count * ks^2) of an OIHW f32 weight.  dy / x / dx: [..., cstride] tensors of equal pixel count.  Returns dW1 as
+    f32 [1, cout, 1, kx]: one part for ``unpack_conv_wgrad(..., mode=2, k_pad=kx, ci_begin=, ci_count=, n_perm=)``."""
+    kx = x.shape[-1]
+    npix = dy.numel() // dy.shape[-1]
+    assert x.numel() // kx == npix and dx.numel() // dx.shape[-1] == npix and dx.shape[-1] == kx
+    assert weight.dtype == torch.float32 and weight.is_contiguous() and weight.dim() == 4
+    kk = weight.shape[2] * weight.shape[3]
+    parts = L.lib().pssr_flatk_bwd_pair_parts(npix)
+    if parts <= 0:
+        L.check(parts if parts < 0 else -1, "pssr_flatk_bwd_pair_parts")
+    slabs = torch.empty(parts, cout, kx, dtype=torch.float32, device=dy.device)
+    dw = torch.empty(1, cout, 1, kx, dtype=torch.float32, device=dy.device)
+    L.check(L.lib().pssr_flatk_bwd_pair(L.ptr(dy), dy.shape[-1], dy_coff, cout, L.ptr(x), kx, 0, L.ptr(dx), kx, 0, kx, L.ptr(weight),
+                                        weight.shape[1] * kk, ci_begin * kk, ci_count * kk, L.ptr(n_perm), L.ptr(slabs), parts, L.ptr(dw), npix, dtype,
+                                        L.stream_ptr()), "pssr_flatk_bwd_pair")
+    return dw
+
+
 def crappify_saltpepper(x, amount, gain, spread, seed, tile_offset, flags, out=None, tile_counter=None):
     out = torch.empty_like(x) if out is None else out
     tiles = x.shape[0]
