@@ -666,6 +666,23 @@ int pssr_sliding_tiles_u8(const uint8_t* sheet, float* tiles, int c, int h, int 
                           pssr_stream_t stream);
 int pssr_patch_tiles_u8(const uint8_t* tiles, uint8_t* sheet, int c, int n_rows, int n_cols, int size, int overlap, int margin,
                         pssr_stream_t stream);
+/* The same two steps for a frame stack and for sheets that do not fit the tile grid (predict_sheet's n_frames / slide / cover).
+ * pssr_stack_tiles_u8: tiles [ntile][m][size][size] f32 cut from a uint8 stack [frames][h][w].  Tiles are numbered slice-major over
+ *   a grid of tiles_y x tiles_x windows per frame slice: for g = tile0 + i, k = g / (tiles_y*tiles_x), t = g % (tiles_y*tiles_x),
+ *   ty = t / tiles_x, tx = t % tiles_x and
+ *     tiles[i][f][y][x] = (float) stack[k*frame_step + f][fold(ty*stride + y, h)][fold(tx*stride + x, w)],
+ *   where fold(i, n) = (j = i mod 2(n-1)) < n ? j : 2(n-1) - j is the source index of np.pad(mode="reflect"): a grid that reaches past
+ *   the bottom or the right edge reads the sheet extended by reflection, and no extended copy exists.  Every slice touched must lie
+ *   inside the stack (k*frame_step + m <= frames), and an axis the grid leaves needs at least 2 pixels.  With m = frames,
+ *   frame_step anything, one slice and a grid inside the sheet this is pssr_sliding_tiles_u8.
+ * pssr_patch_stack_u8: out [n_slices][c][out_h][out_w] u8 = the top-left out_h x out_w pixels of pssr_patch_tiles_u8's sheet for each of
+ *   n_slices tile sets [n_slices*n_rows*n_cols][c][size][size] (slice-major, as above), in one launch;
+ *   1 <= out_h <= n_rows*step+overlap and 1 <= out_w <= n_cols*step+overlap.  Pixels outside the crop are not computed.
+ */
+int pssr_stack_tiles_u8(const uint8_t* stack, float* tiles, int frames, int h, int w, int m, int frame_step, int size, int stride,
+                        int tiles_y, int tiles_x, int tile0, int ntile, pssr_stream_t stream);
+int pssr_patch_stack_u8(const uint8_t* tiles, uint8_t* out, int n_slices, int c, int n_rows, int n_cols, int size, int overlap,
+                        int margin, int out_h, int out_w, pssr_stream_t stream);
 
 
 /* ---------------------------------------------------------------------------------------------

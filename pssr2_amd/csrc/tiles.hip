@@ -4,6 +4,8 @@
 //   * overlap-averaged stitching of the predicted uint8 tiles (pssr/util.py:116-137 `_patch_images` followed by the uint8
 //     cast of `reassemble_sheets`, pssr/util.py:101): out = floor(sum / count) with `margin` pixels trimmed on inner edges.
 // Both are pure index arithmetic + one integer divide per pixel, bit-exact.
+// The stack forms (predict_sheet's n_frames / slide / cover) number the tiles slice-major over all frame slices of a stack, read a grid
+// that leaves the sheet at the bottom / right through np.pad(mode="reflect")'s source index, and stitch every slice, cropped, in one launch.
 #include "common.h"
 
 namespace {
@@ -56,6 +58,87 @@ __global__ void patch_tiles_kernel(const uint8_t* __restrict__ tiles, uint8_t* _
     }
 }
 
+// np.pad(mode="reflect") source index of extended coordinate i >= 0 on an axis of n >= 2 pixels (the edge pixel is not repeated)
+__device__ __forceinline__ int fold_reflect(int i, int n) {
+    const int p = 2 * (n - 1), j = i % p;
+    return j < n ? j : p - j;
+}
+
+// One tile per blockIdx.y step, its m*size rows spread over blockIdx.x and the thread rows of a block; a thread keeps its V-pixel column
+// group and walks rows: one 32-bit divide and one y fold per row, x folded only in tiles that cross the right edge (uniform per tile).
+// V = 4: one 16-byte store per thread and row (size % 4 == 0, tiles 16-byte aligned); the sheet side is byte loads, w being arbitrary.
+template <int V>
+__global__ void __launch_bounds__(256) stack_tiles_kernel(const uint8_t* __restrict__ stack, float* __restrict__ out, int h, int w, int m,
+                                                          int frame_step, int size, int stride, int per_slice, int tiles_x, int tile0, int ntile) {
+    const int groups = size / V;                                  // column groups per row
+    const int gx = groups < 256 ? groups : 256;                   // of which a block covers gx at a time,
+    const int rows_per_pass = 256 / gx;                           // on rows_per_pass rows
+    const int lx = threadIdx.x % gx, ly = threadIdx.x / gx;
+    if (ly >= rows_per_pass) return;
+    const int rows = m * size;
+    for (int i = blockIdx.y; i < ntile; i += gridDim.y) {
+        const int g = tile0 + i, k = g / per_slice, t = g % per_slice;
+        const int y0 = (t / tiles_x) * stride, x0 = (t % tiles_x) * stride;
+        const bool fold_x = x0 + size > w;
+        const uint8_t* slice = stack + (long)k * frame_step * h * w;
+        float* tile = out + (long)i * rows * size;
+        for (int row = blockIdx.x * rows_per_pass + ly; row < rows; row += gridDim.x * rows_per_pass) {
+            const int f = row / size;
+            int sy = y0 + (row - f * size);
+            if (sy >= h) sy = fold_reflect(sy, h);
+            const uint8_t* src = slice + ((long)f * h + sy) * w;
+            float* dst = tile + (long)row * size;
+            for (int q = lx; q < groups; q += gx) {
+                const int sx = x0 + q * V;
+                float v[V];
+                if (fold_x) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) v[j] = (float)src[sx + j < w ? sx + j : fold_reflect(sx + j, w)];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) v[j] = (float)src[sx + j];
+                }
+                if constexpr (V == 4) *reinterpret_cast<float4*>(dst + q * 4) = make_float4(v[0], v[1], v[2], v[3]);
+                else dst[q] = v[0];
+            }
+        }
+    }
+}
+
+// patch_tiles_kernel's value for the top-left out_h x out_w pixels of every slice: one output row per blockIdx.y step (the tile rows
+// that cover it and their margins found once), threads along x
+__global__ void __launch_bounds__(256) patch_stack_kernel(const uint8_t* __restrict__ tiles, uint8_t* __restrict__ out, long n_out_rows, int c,
+                                                          int n_rows, int n_cols, int size, int overlap, int margin, int out_h, int out_w) {
+    const int step = size - overlap;
+    const int per_slice = n_rows * n_cols;
+    for (long orow = blockIdx.y; orow < n_out_rows; orow += gridDim.y) {
+        const int y = (int)(orow % out_h);
+        const long sc = orow / out_h;                              // slice * c + channel
+        const int ch = (int)(sc % c);
+        const long first_tile = (sc / c) * per_slice;
+        const int r_lo = y >= size ? (y - size) / step + 1 : 0;
+        int r_hi = y / step; if (r_hi > n_rows - 1) r_hi = n_rows - 1;
+        for (int x = blockIdx.x * 256 + threadIdx.x; x < out_w; x += gridDim.x * 256) {
+            const int c_lo = x >= size ? (x - size) / step + 1 : 0;
+            int c_hi = x / step; if (c_hi > n_cols - 1) c_hi = n_cols - 1;
+            unsigned sum = 0, cnt = 0;
+            for (int r = r_lo; r <= r_hi; ++r) {
+                const int ly = y - r * step;
+                const int top = r != 0 ? margin : 0, bot = r != n_rows - 1 ? margin : 0;
+                if (ly < top || ly >= size - bot) continue;
+                for (int q = c_lo; q <= c_hi; ++q) {
+                    const int lx = x - q * step;
+                    const int lef = q != 0 ? margin : 0, rig = q != n_cols - 1 ? margin : 0;
+                    if (lx < lef || lx >= size - rig) continue;
+                    sum += tiles[(((first_tile + r * n_cols + q) * c + ch) * size + ly) * size + lx];
+                    ++cnt;
+                }
+            }
+            out[orow * out_w + x] = cnt ? (uint8_t)(sum / cnt) : 0;
+        }
+    }
+}
+
 static inline int grid1d(long total) { long b = (total + 255) / 256; return (int)(b < 16384 ? (b > 0 ? b : 1) : 16384); }
 
 }  // namespace
@@ -79,6 +162,55 @@ int pssr_patch_tiles_u8(const uint8_t* tiles, uint8_t* sheet, int c, int n_rows,
     const int step = size - overlap;
     const long total = (long)c * (n_rows * step + overlap) * (n_cols * step + overlap);
     hipLaunchKernelGGL(patch_tiles_kernel, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)s, tiles, sheet, c, n_rows, n_cols, size, overlap, margin);
+    PSSR_LAUNCH_CHECK();
+    return PSSR_OK;
+}
+
+int pssr_stack_tiles_u8(const uint8_t* stack, float* tiles, int frames, int h, int w, int m, int frame_step, int size, int stride, int tiles_y,
+                        int tiles_x, int tile0, int ntile, pssr_stream_t s) {
+    PSSR_CHECK(stack && tiles, PSSR_ERR_ARG, "stack_tiles: null pointer");
+    PSSR_CHECK(frames > 0 && h > 0 && w > 0 && m > 0 && frame_step > 0 && size > 0 && stride > 0 && tiles_y > 0 && tiles_x > 0 && ntile > 0 && tile0 >= 0,
+               PSSR_ERR_ARG, "stack_tiles: sizes must be positive and tile0 >= 0 (frames=%d h=%d w=%d m=%d frame_step=%d size=%d stride=%d grid=%dx%d tile0=%d ntile=%d)",
+               frames, h, w, m, frame_step, size, stride, tiles_y, tiles_x, tile0, ntile);
+    const long per_slice = (long)tiles_y * tiles_x, last = (long)tile0 + ntile - 1;
+    const long ext_h = (long)(tiles_y - 1) * stride + size, ext_w = (long)(tiles_x - 1) * stride + size;
+    PSSR_CHECK(per_slice <= INT_MAX && last < INT_MAX && ext_h <= INT_MAX / 2 && ext_w <= INT_MAX / 2 && (long)m * size <= INT_MAX / 2,
+               PSSR_ERR_ARG, "stack_tiles: tile grid %dx%d, tile range %d+%d or extents exceed 32-bit indexing", tiles_y, tiles_x, tile0, ntile);
+    const long k_last = last / per_slice;
+    PSSR_CHECK(k_last * frame_step + m <= frames, PSSR_ERR_ARG, "stack_tiles: slice %ld (frames %ld..%ld) leaves the stack of %d frames", k_last,
+               k_last * frame_step, k_last * frame_step + m - 1, frames);
+    PSSR_CHECK(ext_h <= h || h >= 2, PSSR_ERR_ARG, "stack_tiles: the grid is %ld rows high but an axis of length %d cannot be reflected", ext_h, h);
+    PSSR_CHECK(ext_w <= w || w >= 2, PSSR_ERR_ARG, "stack_tiles: the grid is %ld columns wide but an axis of length %d cannot be reflected", ext_w, w);
+    const bool vec = size % 4 == 0 && (uintptr_t)tiles % 16 == 0;
+    const int groups = vec ? size / 4 : size, gx = groups < 256 ? groups : 256, rows_per_pass = 256 / gx;
+    const int bx = cdiv(m * size, rows_per_pass);
+    const dim3 grid(bx < 1024 ? bx : 1024, ntile < 65535 ? ntile : 65535);
+    if (vec)
+        hipLaunchKernelGGL(stack_tiles_kernel<4>, grid, dim3(256), 0, (hipStream_t)s, stack, tiles, h, w, m, frame_step, size, stride, (int)per_slice,
+                           tiles_x, tile0, ntile);
+    else
+        hipLaunchKernelGGL(stack_tiles_kernel<1>, grid, dim3(256), 0, (hipStream_t)s, stack, tiles, h, w, m, frame_step, size, stride, (int)per_slice,
+                           tiles_x, tile0, ntile);
+    PSSR_LAUNCH_CHECK();
+    return PSSR_OK;
+}
+
+int pssr_patch_stack_u8(const uint8_t* tiles, uint8_t* out, int n_slices, int c, int n_rows, int n_cols, int size, int overlap, int margin, int out_h,
+                        int out_w, pssr_stream_t s) {
+    PSSR_CHECK(tiles && out, PSSR_ERR_ARG, "patch_stack: null pointer");
+    PSSR_CHECK(n_slices > 0 && c > 0 && n_rows > 0 && n_cols > 0 && size > 0, PSSR_ERR_ARG, "patch_stack: bad args");
+    PSSR_CHECK(overlap >= 0 && overlap < size && margin >= 0 && margin <= overlap && 2 * margin < size, PSSR_ERR_ARG,
+               "patch_stack: need 0 <= margin <= overlap < size (margin=%d overlap=%d size=%d)", margin, overlap, size);
+    const int step = size - overlap;
+    const long full_h = (long)n_rows * step + overlap, full_w = (long)n_cols * step + overlap;
+    PSSR_CHECK((long)n_rows * n_cols <= INT_MAX && full_h <= INT_MAX && full_w <= INT_MAX, PSSR_ERR_ARG, "patch_stack: tile grid %dx%d exceeds 32-bit indexing",
+               n_rows, n_cols);
+    PSSR_CHECK(out_h >= 1 && out_h <= full_h && out_w >= 1 && out_w <= full_w, PSSR_ERR_ARG,
+               "patch_stack: crop %dx%d must lie within the stitched sheet of %ldx%ld", out_h, out_w, full_h, full_w);
+    const long n_out_rows = (long)n_slices * c * out_h;
+    const int bx = cdiv(out_w, 256);
+    hipLaunchKernelGGL(patch_stack_kernel, dim3(bx < 1024 ? bx : 1024, (unsigned)(n_out_rows < 65535 ? n_out_rows : 65535)), dim3(256), 0, (hipStream_t)s, tiles,
+                       out, n_out_rows, c, n_rows, n_cols, size, overlap, margin, out_h, out_w);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }

@@ -541,6 +541,28 @@ def patch_tiles_u8(tiles, n_rows, n_cols, overlap, margin):
     return out
 
 
+def stack_tiles_u8(stack, m, frame_step, size, stride, tiles_y, tiles_x, tile0, ntile):
+    """uint8 stack [F,H,W] on the device -> float32 tiles [ntile, m, size, size]: tiles ``tile0 ..`` of the slice-major order over frame
+    slices (``m`` frames every ``frame_step``) times a ``tiles_y`` x ``tiles_x`` grid, the sheet reflected where the grid leaves it."""
+    assert stack.dtype == torch.uint8 and stack.is_contiguous()
+    frames, h, w = stack.shape
+    out = torch.empty(ntile, m, size, size, dtype=torch.float32, device=stack.device)
+    L.check(L.lib().pssr_stack_tiles_u8(L.ptr(stack), L.ptr(out), frames, h, w, m, frame_step, size, stride, tiles_y, tiles_x, tile0, ntile,
+                                        L.stream_ptr()), "pssr_stack_tiles_u8")
+    return out
+
+
+def patch_stack_u8(tiles, n_slices, n_rows, n_cols, overlap, margin, out_h, out_w):
+    """uint8 tiles [n_slices*n_rows*n_cols, C, S, S] (slice-major) -> uint8 [n_slices, C, out_h, out_w]: every slice stitched as
+    ``patch_tiles_u8`` and cut to its top-left ``out_h`` x ``out_w`` pixels, in one launch."""
+    t, c, size, _ = tiles.shape
+    assert t == n_slices * n_rows * n_cols and tiles.dtype == torch.uint8 and tiles.is_contiguous()
+    out = torch.empty(n_slices, c, max(out_h, 0), max(out_w, 0), dtype=torch.uint8, device=tiles.device)
+    L.check(L.lib().pssr_patch_stack_u8(L.ptr(tiles), L.ptr(out), n_slices, c, n_rows, n_cols, size, overlap, margin, out_h, out_w, L.stream_ptr()),
+            "pssr_patch_stack_u8")
+    return out
+
+
 def head_conv_bwd(g, g_scale, weight, act, dact, blk, dw, bias_sum, n, h, w, cin, cout, dtype, *, act_coff=0, dact_coff=0):
     """dgrad + wgrad (+ the bias sums of the pixel-shuffle conv in front) in one pass over the activation."""
     L.check(L.lib().pssr_head_conv_bwd(L.ptr(g), C.c_float(g_scale), L.ptr(weight), L.ptr(act), act.shape[-1], act_coff, L.ptr(dact), dact.shape[-1], dact_coff,

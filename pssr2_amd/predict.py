@@ -12,7 +12,7 @@ from torch.utils.data import DataLoader, Dataset
 
 from . import distributed as D
 from . import ops
-from .data import _slice_center
+from .data import _get_n_frames, _slice_center
 from .util import _get_callbacks
 
 try:
@@ -223,14 +223,49 @@ def predict_collage(model: nn.Module, dataset: Dataset, device: str = "cpu", nor
     Image.fromarray(collage.cpu().numpy()).save(f"{out_dir}/{prefix + '_' if prefix else ''}collage_{n_images}.png")
 
 
+def _sheet_grid(h: int, w: int, tile: int, stride: int, cover: bool):
+    """``(n_rows, n_cols)`` of the windows ``predict_sheet`` cuts: whole windows only (pssr/data.py:629-638), or with ``cover`` the
+    smallest grid whose windows reach the bottom and the right edge of the sheet (extended by reflection, so no axis may be 1 long)."""
+    if cover:
+        if h < 2 or w < 2:
+            raise ValueError(f"cover=True extends the sheet by reflection, which an axis of length 1 does not have (sheet {h}x{w})")
+        return tuple(-(-max(n - tile, 0) // stride) + 1 for n in (h, w))
+    if h < tile or w < tile:
+        raise ValueError(f"sheet {h}x{w} is smaller than one tile ({tile})")
+    return (h - tile) // stride + 1, (w - tile) // stride + 1
+
+
+def _slice_plan(frames: int, n_frames, slide: bool):
+    """``(m, step, n_slices)``: frame slice ``k`` of a stack of ``frames`` is frames ``[k * step, k * step + m)`` with
+    ``m = max(n_frames)`` as in the sheet datasets' LR mode (``frames - m + 1`` slices with ``slide``, else ``frames // m``);
+    ``n_frames=-1``: one slice of all frames."""
+    n_frames = _get_n_frames(n_frames)
+    if n_frames is None:
+        return frames, frames, 1
+    m = max(n_frames)
+    n_slices = frames - m + 1 if slide else frames // m
+    if m < 1 or n_slices < 1:
+        raise ValueError(f"A stack of {frames} frames holds no slice of n_frames = {m} frames.")
+    return m, 1 if slide else m, n_slices
+
+
 def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 32, margin: int = 0, batch_size: int = 128,
-                  device: str = "cuda", to_numpy: bool = True):
+                  device: str = "cuda", to_numpy: bool = True, *, n_frames=-1, slide: bool = False, cover: bool = False):
     r"""Whole-sheet prediction entirely on the device: what ``predict_images`` on a ``SlidingDataset`` in LR mode
     (pssr/data.py:132-266, pssr/predict.py:11-83) followed by ``reassemble_sheets`` (pssr/util.py:54-137) computes, without
     the per-tile host round trips.  ``sheet``: uint8 array or tensor [C, H, W] (or [H, W]) of the low-resolution image.
     Tiles of ``tile_res`` LR pixels with ``overlap`` are cut on the device, predicted in batches, truncated to uint8
     (``_pred_array``), and stitched with overlap averaging and ``margin`` trimming (in LR pixels times the model's scale,
-    as upstream).  Returns uint8 [C_out, H', W'] with H' = (n_rows*(tile_res-overlap)+overlap)*scale."""
+    as upstream).  Returns uint8 [C_out, H', W'] with H' = (n_rows*(tile_res-overlap)+overlap)*scale.
+
+    ``cover=True`` predicts the whole sheet whatever its size: the tile grid is the smallest that reaches the bottom and the right edge,
+    the tiles beyond them read the sheet reflected there (``np.pad(mode="reflect")``, by address arithmetic: no padded copy is made),
+    and the result is cut to ``H * scale`` x ``W * scale``.  It equals ``predict_sheet`` of the sheet padded that way on the host, cut;
+    ``margin`` trims the inner edges of that extended grid.  A sheet smaller than a tile is fine, an axis of length 1 is not.
+
+    ``n_frames=m`` or ``[lr, hr]`` (with ``slide`` as in the sheet datasets) reads ``sheet`` as a stack [F, H, W] and runs the model on
+    every frame slice ``[k * step, k * step + max(n_frames))``: returns uint8 [S, C_out, H', W'], slice ``k`` first.  The tiles of all
+    slices form one slice-major sequence cut into batches of ``batch_size`` (a batch may span slices), and one launch stitches them."""
     if margin > overlap:
         raise ValueError(f"The value of margin cannot be greater than overlap. Given {margin} and {overlap} respectively.")
     sheet = torch.as_tensor(np.asarray(sheet) if not torch.is_tensor(sheet) else sheet)
@@ -240,25 +275,36 @@ def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 3
         raise ValueError("predict_sheet expects a uint8 sheet (the reference's uint8 tif path)")
     sheet = sheet.to(device).contiguous()
     c, h, w = sheet.shape
-    if h < tile_res or w < tile_res:
-        raise ValueError(f"sheet {h}x{w} is smaller than one tile ({tile_res})")
     stride = tile_res - overlap
-    n_rows, n_cols = (h - tile_res) // stride + 1, (w - tile_res) // stride + 1
-    n_tiles = n_rows * n_cols
+    n_rows, n_cols = _sheet_grid(h, w, tile_res, stride, cover)
+    m, step, n_slices = _slice_plan(c, n_frames, slide)
+    # the plain call keeps the kernels it has always used (pssr_sliding_tiles_u8 / pssr_patch_tiles_u8); stacks and covered sheets take
+    # the slice-major, reflecting pair (pssr_stack_tiles_u8 / pssr_patch_stack_u8)
+    stacked = _get_n_frames(n_frames) is not None
+    plain = not cover and not stacked
+    n_tiles = n_slices * n_rows * n_cols
     model.to(device)
     model.eval()
     preds = None
     with torch.no_grad():
         for t0 in range(0, n_tiles, batch_size):
             nt = min(batch_size, n_tiles - t0)
-            lr = ops.sliding_tiles_u8(sheet, tile_res, stride, t0, nt)
+            if plain:
+                lr = ops.sliding_tiles_u8(sheet, tile_res, stride, t0, nt)
+            else:
+                lr = ops.stack_tiles_u8(sheet, m, step, tile_res, stride, n_rows, n_cols, t0, nt)
             y = model(lr).contiguous().float()
             if preds is None:
                 preds = torch.empty(n_tiles, *y.shape[1:], dtype=torch.uint8, device=y.device)
             ops.clip_u8(y, preds[t0:t0 + nt])
     scale = preds.shape[-1] // tile_res
     # upstream passes overlap*lr_scale and the raw margin to _patch_images (pssr/util.py:99)
-    out = ops.patch_tiles_u8(preds, n_rows, n_cols, overlap * scale, margin)
+    if plain:
+        out = ops.patch_tiles_u8(preds, n_rows, n_cols, overlap * scale, margin)
+    else:
+        out_h, out_w = ((h, w) if cover else (n_rows * stride + overlap, n_cols * stride + overlap))
+        out = ops.patch_stack_u8(preds, n_slices, n_rows, n_cols, overlap * scale, margin, out_h * scale, out_w * scale)
+        out = out if stacked else out[0]
     return out.cpu().numpy() if to_numpy else out
 
 
