@@ -11,7 +11,9 @@ from __future__ import annotations
 
 import contextlib
 import functools
+import math
 import re
+import zlib
 from pathlib import Path
 from typing import NamedTuple
 
@@ -118,6 +120,38 @@ def expected(ref: torch.Tensor, dt) -> torch.Tensor:
     r32 = ref.float()
     assert torch.equal(r32.double(), ref), "reference is not exact in f32: the operands break the exactness premise"
     return r32.to(dt)
+
+
+def stable_seed(*key):
+    """a generator seed that depends on the key alone (hash() of a string changes from process to process)"""
+    return zlib.crc32(repr(key).encode()) & 0x7fffffff
+
+
+MEAN_GRID = Grid(2, 0.5)
+
+
+def per_channel(key, c):
+    """BatchNorm-like per-channel constants on the exact grids: scale, shift (both signs), mean, invstd"""
+    g = torch.Generator().manual_seed(stable_seed(key, c))
+    return pick(g, (c,), SCALES), dyadic(g, (c,), SHIFT_GRID), dyadic(g, (c,), MEAN_GRID), pick(g, (c,), (0.5, 1.0, 2.0))
+
+
+def nchw(t):
+    return t.view(1, -1, 1, 1)
+
+
+def dev(t):
+    return t.float().contiguous().cuda()
+
+
+def assert_equal(got, want, what=""):
+    got = got.cpu()
+    assert got.dtype == want.dtype and got.shape == want.shape, (got.dtype, want.dtype, got.shape, want.shape)
+    if not torch.equal(got, want):
+        bad = (got != want).nonzero()
+        i = tuple(bad[0].tolist())
+        raise AssertionError(f"{what}: {len(bad)} of {want.numel()} values differ; first at {i}: got {got[i].item()!r}, "
+                             f"want {want[i].item()!r}")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -388,6 +422,71 @@ def mask_edge_values(dt):
     bits = {torch.bfloat16: [0x0000, 0x8000, 0x0001, 0x8001, 0x0080, 0x8080, 0xBF80, 0x3F80, 0x7F7F],
             torch.float16: [0x0000, 0x8000, 0x0001, 0x8001, 0x0400, 0x8400, 0xBC00, 0x3C00, 0x7BFF]}[dt]
     return torch.tensor([b - 65536 if b >= 32768 else b for b in bits], dtype=torch.int16).view(dt)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the weight gradient (csrc/conv_wgrad.hip) and its unpack pass (csrc/pack.hip)
+def tiles_per_workgroup(n_tiles, split):
+    """pixel tiles each of the `split` workgroups of one slab walks: workgroup b takes tiles b, b + split, ..."""
+    return [len(range(b, n_tiles, split)) for b in range(split)]
+
+
+def unpack_map(mode, cout, cin, ks, k_pad, *, ci_begin=0, ci_count=None, n_perm=None):
+    """Where pssr_unpack_conv_wgrad_parts puts element [n][tap][k] of a packed gradient f32 [rows][taps][k_pad] (taps = ks * ks in mode
+    0, else 1): int64 [cout, taps, k_pad] of flat indices into the OIHW gradient [cout, cin, ks, ks], -1 where the element is
+    discarded.  Written from the layouts in include/pssr_mi355.h:
+      mode 0  K = input channel - ci_begin, one slice per tap; row n is output channel n_perm[n]
+      mode 2  K = (input channel - ci_begin) * ks * ks + tap; row n is output channel n_perm[n]
+      mode 4  K = tap * cpad + input channel, cpad = cin rounded up to 16 (no channel window, no permutation)"""
+    kk = ks * ks
+    taps = kk if mode == 0 else 1
+    ci_count = cin - ci_begin if ci_count is None else ci_count
+    n = torch.arange(cout).view(cout, 1, 1)
+    tap = torch.arange(taps).view(1, taps, 1)
+    k = torch.arange(k_pad).view(1, 1, k_pad)
+    co = n if n_perm is None else n_perm.long().view(cout, 1, 1)
+    if mode == 0:
+        ci, tp, ok = ci_begin + k, tap, k < ci_count
+    elif mode == 2:
+        ci, tp, ok = ci_begin + k // kk, k % kk, k < ci_count * kk
+    elif mode == 4:
+        assert ci_begin == 0 and ci_count == cin and n_perm is None
+        cpad = (cin + 15) // 16 * 16
+        ci, tp = k % cpad, k // cpad
+        ok = (tp < kk) & (ci < cin)
+    else:
+        raise ValueError(mode)
+    idx = (co * cin + ci) * kk + tp
+    return torch.where(ok.expand_as(idx), idx, torch.full_like(idx, -1))
+
+
+def unpack_reference(parts, dest, umap, accumulate):
+    """float64 result of the unpack pass: parts [parts, rows, taps, k_pad] summed over the parts and scattered by `umap` into a copy of
+    the OIHW tensor `dest` (added to it when `accumulate`); what the map does not address keeps its value"""
+    cout = umap.shape[0]
+    sel = umap >= 0
+    idx = umap[sel]
+    assert idx.unique().numel() == idx.numel(), "the map addresses a destination element twice"
+    s = parts[:, :cout].sum(0)[sel]
+    out = dest.clone().reshape(-1)
+    out[idx] = (out[idx] + s) if accumulate else s
+    return out.view_as(dest)
+
+
+def gelu64(z):
+    return 0.5 * z * (1.0 + torch.special.erf(z / math.sqrt(2.0)))
+
+
+GELU16_ERR = 7e-6       # the error bound csrc/common.h states for the polynomial GELU of the 16-bit builds
+
+
+def gelu_exact_inputs(dt):
+    """The z = k / 8, |k| <= 32, for which the 16-bit GELU prologue stages a known value: gelu(z) +- 2 * GELU16_ERR (the factor 2 for
+    the f32 evaluation) rounds to one number of the storage type.  z = 0 is kept too: the kernel maps it to exactly 0."""
+    z = torch.arange(-32, 33, dtype=torch.float64) / 8
+    g = gelu64(z)
+    keep = ((g - 2 * GELU16_ERR).float().to(dt) == (g + 2 * GELU16_ERR).float().to(dt)) | (z == 0)
+    return z[keep]
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -6,10 +6,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _conv_exact import (B_GRID, PRODUCTION_TUNABLES, SCALE_GRID, SHIFT_GRID, STAT_ROWS, W_GRID, X_GRID, Grid, assert_exact_premise,
-                         assert_head_premise, assert_headq_premise, dyadic, expected, fold_stat_rows, from_blocked, head_refs, head_tiles,
-                         head_weight_grid, is_conv_kernel, is_head_kernel, kernel_name_table, later_trip_mask, mask_edge_values, needs_rounding,
-                         parse_kernel_name, pix_index, scaled, shuf2_perm, storage_ulp, stored_grid, sum_fits, to_blocked)
+from _conv_exact import (B_GRID, GELU16_ERR, PRODUCTION_TUNABLES, SCALE_GRID, SHIFT_GRID, STAT_ROWS, W_GRID, X_GRID, Grid,
+                         assert_exact_premise, assert_head_premise, assert_headq_premise, dyadic, expected, fold_stat_rows, from_blocked,
+                         gelu64, gelu_exact_inputs, head_refs, head_tiles, head_weight_grid, is_conv_kernel, is_head_kernel,
+                         kernel_name_table, later_trip_mask, mask_edge_values, needs_rounding, parse_kernel_name, pix_index, scaled,
+                         shuf2_perm, storage_ulp, stored_grid, sum_fits, tiles_per_workgroup, to_blocked, unpack_map, unpack_reference)
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -249,3 +250,92 @@ def test_kernel_name_table_survives_a_demangler_that_garbles_names():
     # two kernels under one reported name: marked, so that launched_kernels fails instead of guessing
     assert kernel_name_table([a, b], lambda s: "head_fwd_kernel<E>")["head_fwd_kernel<E>"] is None
     assert kernel_name_table([b, c], lambda s: "head_fwd_kernel<2, 1>")["head_fwd_kernel<2, 1>"] == ("head_fwd_kernel", (2, 1))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the helpers of tests/test_gpu_wgrad_exact.py and tests/test_gpu_unpack_exact.py
+def test_tiles_per_workgroup():
+    assert tiles_per_workgroup(12, 1) == [12] and tiles_per_workgroup(12, 12) == [1] * 12
+    assert tiles_per_workgroup(12, 5) == [3, 3, 2, 2, 2] and tiles_per_workgroup(12, 7) == [2, 2, 2, 2, 2, 1, 1]
+
+
+def _unpack_operands(seed, cout, cin, h, w):
+    g = torch.Generator().manual_seed(seed)
+    return dyadic(g, (2, cin, h, w), X_GRID), dyadic(g, (2, cout, h, w), X_GRID)
+
+
+def _padded(packed, k_pad):
+    """[cout, taps, K] -> [1, cout + 3, taps, k_pad]: NaN in the padding rows and columns"""
+    cout, taps, k = packed.shape
+    out = torch.full((1, cout + 3, taps, k_pad), float("nan"), dtype=torch.float64)
+    out[0, :cout, :, :k] = packed
+    return out
+
+
+@pytest.mark.parametrize("ks", [3, 1])
+def test_unpack_map_mode0_against_conv2d_weight(ks):
+    """the packed gradient of a convolution over the channel window, its rows in n_perm order, built tap by tap with unfold"""
+    cout, cin, h, w, b, c, k_pad = 8, 7, 6, 5, 2, 4, 16
+    x, dy = _unpack_operands(5, cout, cin, h, w)
+    perm = shuf2_perm(cout)
+    cols = F.unfold(x, ks, padding=ks // 2).view(2, cin, ks * ks, h * w)            # [N, ci, tap, pixel]
+    packed = torch.einsum("bnl,bktl->ntk", dy[:, perm].reshape(2, cout, h * w), cols[:, b:b + c])
+    umap = unpack_map(0, cout, cin, ks, k_pad, ci_begin=b, ci_count=c, n_perm=perm)
+    assert umap.shape == (cout, ks * ks, k_pad) and int((umap >= 0).sum()) == cout * c * ks * ks
+    old = torch.full((cout, cin, ks, ks), 3.0, dtype=torch.float64)
+    want = torch.nn.grad.conv2d_weight(x, (cout, cin, ks, ks), dy, padding=ks // 2)
+    for acc in (False, True):
+        got = unpack_reference(_padded(packed, k_pad), old, umap, acc)
+        assert torch.equal(got[:, b:b + c], want[:, b:b + c] + (3.0 if acc else 0.0))
+        assert torch.equal(got[:, :b], old[:, :b]) and torch.equal(got[:, b + c:], old[:, b + c:])
+    # no window, no permutation, k_pad == cin: the packed order [n][tap][ci] itself
+    umap = unpack_map(0, cout, cin, ks, cin)
+    full = torch.einsum("bnl,bktl->ntk", dy.reshape(2, cout, h * w), cols)
+    assert torch.equal(unpack_reference(full[None], old, umap, False), want)
+
+
+@pytest.mark.parametrize("ks", [3, 1])
+def test_unpack_map_mode2_against_conv2d_weight(ks):
+    """flat K: a 1x1 convolution over the im2col'ed channel window, K = (ci - ci_begin) * ks * ks + tap"""
+    cout, cin, h, w, b, c, k_pad = 8, 6, 5, 7, 3, 2, 32
+    x, dy = _unpack_operands(6, cout, cin, h, w)
+    perm = shuf2_perm(cout)
+    xcol = F.unfold(x[:, b:b + c], ks, padding=ks // 2)                             # [N, c * ks * ks, pixel]
+    packed = torch.einsum("bnl,bkl->nk", dy[:, perm].reshape(2, cout, h * w), xcol)[:, None]
+    umap = unpack_map(2, cout, cin, ks, k_pad, ci_begin=b, ci_count=c, n_perm=perm)
+    old = torch.zeros(cout, cin, ks, ks, dtype=torch.float64)
+    got = unpack_reference(_padded(packed, k_pad), old, umap, False)
+    want = torch.nn.grad.conv2d_weight(x, (cout, cin, ks, ks), dy, padding=ks // 2)
+    assert torch.equal(got[:, b:b + c], want[:, b:b + c]) and not bool(got[:, :b].any()) and not bool(got[:, b + c:].any())
+
+
+@pytest.mark.parametrize("ks,cin", [(2, 5), (3, 18)])
+def test_unpack_map_mode4_against_conv2d_weight(ks, cin):
+    """space to depth: a ks x ks stride-ks convolution as 1x1 over K = tap * cpad + ci, cpad = cin rounded up to 16"""
+    cout, oh, ow = 8, 3, 2
+    cpad = (cin + 15) // 16 * 16
+    x, _ = _unpack_operands(7, cout, cin, oh * ks, ow * ks)
+    dy = dyadic(torch.Generator().manual_seed(8), (2, cout, oh, ow), X_GRID)
+    s2d = torch.full((2, ks * ks, cpad, oh, ow), float("nan"), dtype=torch.float64)
+    s2d[:, :, :cin] = x.view(2, cin, oh, ks, ow, ks).permute(0, 3, 5, 1, 2, 4).reshape(2, ks * ks, cin, oh, ow)
+    s2d = s2d.reshape(2, ks * ks * cpad, oh * ow)
+    packed = torch.einsum("bnl,bkl->nk", dy.reshape(2, cout, oh * ow), s2d)[:, None]
+    umap = unpack_map(4, cout, cin, ks, ks * ks * cpad)
+    got = unpack_reference(packed[None], torch.zeros(cout, cin, ks, ks, dtype=torch.float64), umap, False)
+    assert torch.equal(got, torch.nn.grad.conv2d_weight(x, (cout, cin, ks, ks), dy, stride=ks))
+
+
+def test_unpack_reference_rejects_a_map_that_collides():
+    umap = torch.zeros(2, 1, 4, dtype=torch.int64)
+    with pytest.raises(AssertionError, match="twice"):
+        unpack_reference(torch.zeros(1, 2, 1, 4, dtype=torch.float64), torch.zeros(2, 4, 1, 1, dtype=torch.float64), umap, False)
+
+
+@pytest.mark.parametrize("dt,survivors", [(torch.bfloat16, 50), (torch.float16, 40)])
+def test_gelu_screening_keeps_enough_inputs(dt, survivors):
+    z = gelu_exact_inputs(dt)
+    assert int((z != 0).sum()) == survivors and 0.0 in z.tolist() and len(z) >= 32
+    g = gelu64(z)
+    torch.testing.assert_close(g, F.gelu(z), rtol=0, atol=1e-15)
+    lo, hi = (g - 2 * GELU16_ERR).float().to(dt), (g + 2 * GELU16_ERR).float().to(dt)
+    assert torch.equal(lo[z != 0], hi[z != 0]) and torch.equal(lo[z != 0], g.float().to(dt)[z != 0])

@@ -200,7 +200,7 @@ WG_CASES = [
 ]
 
 
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("case", WG_CASES)
 def test_conv_wgrad(case, dt):
     from pssr2_amd import ops
@@ -216,7 +216,7 @@ def test_conv_wgrad(case, dt):
     copad = ops.pad_to(cout, 16)
     sc = torch.zeros(cpad); sc[:cin] = scale
     sh = torch.zeros(cpad); sh[:cin] = shift
-    co_eff = cout if (cout * (2 if dt == torch.bfloat16 else 4)) % 16 == 0 else copad
+    co_eff = cout if (cout * (4 if dt == torch.float32 else 2)) % 16 == 0 else copad
     dwp = torch.zeros(co_eff, ks * ks, cpad, device="cuda")
     ops.conv2d_wgrad(_nhwc(dy, copad, dt), co_eff, _nhwc(yprev, cpad, dt), cpad, ks * ks, dwp, n=n, h=h, w=w, dtype=code,
                      pro_scale=sc.cuda(), pro_shift=sh.cuda())

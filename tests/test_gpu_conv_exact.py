@@ -10,8 +10,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _conv_exact import (B_GRID, SCALE_GRID, SCALES, SHIFT_GRID, X_GRID, W_GRID, Grid, assert_exact_premise, assert_guards, dyadic,
-                         expected, from_blocked, launched_kernels, nhwc, pick, production_tunables, shuf2_perm, tunables)
+from _conv_exact import (B_GRID, SCALE_GRID, SHIFT_GRID, X_GRID, W_GRID, Grid, assert_equal, assert_exact_premise, assert_guards, dev,
+                         dyadic, expected, from_blocked, launched_kernels, nchw, nhwc, per_channel, production_tunables, shuf2_perm,
+                         tunables)
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("production_tunables")]
 _ = production_tunables      # (the fixture is used through the mark above)
@@ -19,7 +20,6 @@ _ = production_tunables      # (the fixture is used through the mark above)
 BF16, F16, F32 = torch.bfloat16, torch.float16, torch.float32
 DT16 = (BF16, F16)
 RELU, STATS, AFFINE, SHUF2, SOLO = 1, 2, 4, 16, 32     # PSSR_FLAG_*
-MEAN_GRID = Grid(2, 0.5)
 
 IG, V3, FLAT, FIN = "conv_igemm_kernel", "conv_v3_kernel", "conv_flat_kernel", "conv_splitk_finish_kernel"
 
@@ -60,30 +60,6 @@ def operands(shape):
     wt = dyadic(g, (cout, cin, ks, ks), W_GRID)
     b = dyadic(g, (cout,), B_GRID)
     return x, wt, b, F.conv2d(x, wt, padding=ks // 2)
-
-
-def per_channel(key, c):
-    """BatchNorm-like per-channel constants on the exact grids: scale, shift, mean, invstd"""
-    g = torch.Generator().manual_seed(_seed(key, c))
-    return pick(g, (c,), SCALES), dyadic(g, (c,), SHIFT_GRID), dyadic(g, (c,), MEAN_GRID), pick(g, (c,), (0.5, 1.0, 2.0))
-
-
-def nchw(t):
-    return t.view(1, -1, 1, 1)
-
-
-def dev(t):
-    return t.float().contiguous().cuda()
-
-
-def assert_equal(got, want, what=""):
-    got = got.cpu()
-    assert got.dtype == want.dtype and got.shape == want.shape, (got.dtype, want.dtype, got.shape, want.shape)
-    if not torch.equal(got, want):
-        bad = (got != want).nonzero()
-        i = tuple(bad[0].tolist())
-        raise AssertionError(f"{what}: {len(bad)} of {want.numel()} values differ; first at {i}: got {got[i].item()!r}, "
-                             f"want {want[i].item()!r}")
 
 
 def conv(dt, x, wt, *, bias=None, flags=0, out_coff=8, blk=0, pro=None, x1=None, w1=None, tail=None, affine=None, stats=False,
@@ -333,7 +309,10 @@ def test_tilings_agree(row, dt):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# e. weight gradient
+# e. weight gradient: four production-sized rows, each in atomic and in partial-slab mode on four layouts.  The table with one row per
+# (family, template integers) of csrc/conv_wgrad.hip, the walk of the tile loop and the GELU prologue are in
+# tests/test_gpu_wgrad_exact.py; the unpack pass on its own (windows, permuted and padded rows, part lanes, modes 2 and 4) is in
+# tests/test_gpu_unpack_exact.py
 WG = "conv_wgrad_kernel"
 WG_ROWS = {
     # id: ((n, cin, cout, h, w, ks), prologue, 16-bit kernels, f32 kernels)
@@ -360,7 +339,8 @@ def wgrad_case(row):
 @pytest.mark.parametrize("row,dt", [pytest.param(r, dt, id=f"{r}-{str(dt)[6:]}") for r in WG_ROWS for dt in (BF16, F16, F32)])
 def test_wgrad_exact(row, dt, parts):
     """dw in f32 equals the float64 reference exactly, in atomic and in partial-slab mode, with channel offsets and in the blocked
-    pixel orders; the BatchNorm + ReLU prologue where the row has one"""
+    pixel orders (blk 1 and 2); the BatchNorm + ReLU prologue where the row has one.  At these shapes every workgroup takes one pixel
+    tile and the unpack pass runs its contiguous path only: see tests/test_gpu_wgrad_exact.py and tests/test_gpu_unpack_exact.py"""
     from pssr2_amd import ops
     shape, pro, k16, k32 = WG_ROWS[row]
     n, cin, cout, h, w, ks = shape
