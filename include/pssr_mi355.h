@@ -42,6 +42,10 @@ const char* pssr_last_error(void);
  * Weight packing.  torch keeps Conv2d weights OIHW f32 (pssr/models/_blocks.py:10-11,28,35); the
  * conv kernels consume a K-chunked, LDS-image-ordered copy in the compute dtype:
  *   packed[chunk][tap][n (padded to 128)][32 bytes = 2 swizzled 16-byte slots of K]
+ * A chunk is KCH consecutive K indices and a slot holds EPS = KCH / 2 of them in order: EPS = 4, KCH = 8 for PSSR_F32, EPS = 8,
+ * KCH = 16 for PSSR_BF16 and PSSR_F16.  K elements [0, EPS) of a chunk are in slot (n >> 3) & 1 of column n and elements
+ * [EPS, KCH) in the other one, i.e. the slot at byte offset 16 s holds the half h = s ^ ((n >> 3) & 1) (the conv kernels read
+ * half h of column n at n * 32 + ((h ^ ((n >> 3) & 1)) << 4): conflict-free LDS reads).
  * mode 0 (forward):  GEMM-K = input channels  [ci_begin, ci_begin+ci_count) of the OIHW tensor,
  *                    GEMM-N = output channels (optionally permuted by `n_perm`: n_src = n_perm[n]).
  * mode 1 (dgrad):    GEMM-K = output channels, GEMM-N = input channels of the range, taps flipped.
@@ -360,7 +364,8 @@ int pssr_avgpool2_planes_div(const float* in, float in_div, float* out, int plan
 int pssr_avgpool2_pair_div(const float* x, const float* y, float in_div, float* xo, float* yo, int planes, int h, int w,
                            pssr_stream_t stream);
 
-/* torch.optim.AdamW step (decoupled weight decay) over flat f32 buffers; `step` is 1-based. */
+/* torch.optim.AdamW step (decoupled weight decay) over flat f32 buffers; `step` is 1-based.  p, g, m and v must be 16-byte
+ * aligned when n >= 4 (all three entry points; pssr_amp_check asks it of g for every n): PSSR_ERR_ARG otherwise, nothing is launched. */
 int pssr_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
                     pssr_stream_t stream);

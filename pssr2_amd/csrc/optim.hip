@@ -97,6 +97,8 @@ extern "C" int pssr_adamw_step(float* p, const float* g, float* m, float* v, int
 extern "C" int pssr_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, int64_t* state, float beta1, float beta2,
                                    float eps, float weight_decay, float grad_scale, pssr_stream_t s) {
     PSSR_CHECK(p && g && m && v && state && n > 0, PSSR_ERR_ARG, "adamw_step_dev: bad args");
+    PSSR_CHECK(((uintptr_t)p % 16 == 0 && (uintptr_t)g % 16 == 0 && (uintptr_t)m % 16 == 0 && (uintptr_t)v % 16 == 0) || n < 4, PSSR_ERR_ARG,
+               "adamw_step_dev: buffers must be 16-byte aligned");
     long blocks = (n / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
@@ -121,6 +123,8 @@ extern "C" int pssr_adamw_step_amp(float* p, const float* g, float* m, float* v,
                                    float eps, float weight_decay, float grad_scale, int32_t* amp, float growth, float backoff,
                                    int interval, pssr_stream_t s) {
     PSSR_CHECK(p && g && m && v && state && amp && n > 0 && interval > 0 && growth > 0.f && backoff > 0.f, PSSR_ERR_ARG, "adamw_step_amp: bad args");
+    PSSR_CHECK(((uintptr_t)p % 16 == 0 && (uintptr_t)g % 16 == 0 && (uintptr_t)m % 16 == 0 && (uintptr_t)v % 16 == 0) || n < 4, PSSR_ERR_ARG,
+               "adamw_step_amp: buffers must be 16-byte aligned");
     long blocks = (n / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;

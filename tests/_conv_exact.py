@@ -473,6 +473,151 @@ def unpack_reference(parts, dest, umap, accumulate):
     return out.view_as(dest)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the weight pack (csrc/pack.hip: pssr_pack_conv_weight, pssr_pack_conv_weight_batch)
+def pack_eps(dtype):
+    """(EPS, KCH) of a storage type (include/pssr_mi355.h): elements per 16-byte slot, K indices per chunk"""
+    eps = 16 // torch.empty(0, dtype=dtype).element_size()
+    return eps, 2 * eps
+
+
+def pack_dims(mode, cout, cin, ks, ci_count):
+    """(taps, GEMM-K, GEMM-N) of a packing mode"""
+    kk = ks * ks
+    s2d = kk * ((cin + 15) // 16 * 16)
+    gk = {0: ci_count, 1: cout, 2: ci_count * kk, 3: cout, 4: s2d, 5: cout}[mode]
+    gn = {0: cout, 1: ci_count, 2: cout, 3: ci_count * kk, 4: cout, 5: s2d}[mode]
+    return (kk if mode < 2 else 1), gk, gn
+
+
+def pack_map(mode, cout, cin, ks, k_pad, n_pad, dtype, *, ci_begin=0, ci_count=None, n_perm=None, center=False):
+    """Which source element every element of a packed weight holds: int64 [taps * k_pad * n_pad] in packed order
+    packed[chunk][tap][n][slot][e] of flat indices into the OIHW tensor [cout, cin, ks, ks]; -1 is padding (stored as +0).  Written
+    from the layouts in include/pssr_mi355.h:
+      position -> (k, tap, n): the slot at byte offset 16 s of column n holds half h = s ^ ((n >> 3) & 1) of the chunk, so
+                  k = chunk * KCH + h * EPS + e
+      mode 0  K = input channel - ci_begin, N = output channel n_perm[n], one slice per tap
+      mode 1  K = output channel n_perm[k], N = input channel - ci_begin, slice `tap` holds kernel tap ks * ks - 1 - tap
+      mode 2  one slice; K = (input channel - ci_begin) * ks * ks + tap, N = output channel n_perm[n]
+      mode 3  its transpose: K = output channel n_perm[k], N = the flat index
+      mode 4  one slice; K = tap * cpad + input channel, cpad = cin rounded up to 16, N = output channel (no window, no permutation)
+      mode 5  its transpose
+    center (modes 2 / 3, ks = 3): the source is a 1x1 weight [cout, cin, 1, 1] standing for the centre tap of a 3x3 kernel."""
+    eps, kch = pack_eps(dtype)
+    kk = ks * ks
+    ci_count = cin - ci_begin if ci_count is None else ci_count
+    taps = kk if mode < 2 else 1
+    assert k_pad % kch == 0 and n_pad % 128 == 0
+    assert not center or (mode in (2, 3) and ks == 3)
+    chunk = torch.arange(k_pad // kch).view(-1, 1, 1, 1, 1)
+    tap = torch.arange(taps).view(1, -1, 1, 1, 1)
+    n = torch.arange(n_pad).view(1, 1, -1, 1, 1)
+    s = torch.arange(2).view(1, 1, 1, 2, 1)
+    e = torch.arange(eps).view(1, 1, 1, 1, -1)
+    k = chunk * kch + (s ^ ((n >> 3) & 1)) * eps + e
+    k, tap, n = torch.broadcast_tensors(k, tap, n)
+    if mode in (1, 3, 5):       # the transposed forms: the output channel runs along K
+        o, i = k, n
+    else:
+        o, i = n, k
+    if mode in (0, 1):
+        ci, tp, ok = ci_begin + i, (tap if mode == 0 else kk - 1 - tap), i < ci_count
+    elif mode in (2, 3):
+        ci, tp, ok = ci_begin + i // kk, i % kk, i < ci_count * kk
+    elif mode in (4, 5):
+        assert ci_begin == 0 and ci_count == cin and n_perm is None
+        cpad = (cin + 15) // 16 * 16
+        ci, tp = i % cpad, i // cpad
+        ok = (tp < kk) & (ci < cin)
+    else:
+        raise ValueError(mode)
+    ok = ok & (o < cout)
+    co = o if n_perm is None else n_perm.long()[o.clamp(max=cout - 1)]
+    if center:
+        idx, ok = co * cin + ci, ok & (tp == 4)
+    else:
+        idx = (co * cin + ci) * kk + tp
+    return torch.where(ok, idx, torch.full_like(idx, -1)).reshape(-1)
+
+
+def pack_reference(w, pmap, dtype):
+    """what the pack must store: the source elements gathered by `pmap` and converted with torch (round to nearest even), +0 where
+    the map says padding"""
+    out = torch.zeros(pmap.numel(), dtype=dtype)
+    sel = pmap >= 0
+    out[sel] = w.reshape(-1)[pmap[sel]].to(dtype)
+    return out
+
+
+def packed_matrices(packed, taps, k_pad, n_pad, dtype):
+    """de-swizzle a packed weight (flat, packed order) to the per-tap GEMM matrices B[tap][k][n]; `dtype` gives EPS and KCH (the
+    tensor itself may hold anything, float64 values or indices)"""
+    eps, kch = pack_eps(dtype)
+    p = packed.view(k_pad // kch, taps, n_pad, 2, eps)
+    flip = ((torch.arange(n_pad) >> 3) & 1).bool()
+    halves = torch.where(flip.view(1, 1, -1, 1, 1), p.flip(3), p)          # [chunk][tap][n][half][e]
+    return halves.permute(1, 0, 3, 4, 2).reshape(taps, k_pad, n_pad)
+
+
+def pack_position(i, taps, n_pad, dtype):
+    """flat packed index -> (chunk, tap, n, slot, e)"""
+    eps, _ = pack_eps(dtype)
+    i, e = divmod(int(i), eps)
+    i, s = divmod(i, 2)
+    i, n = divmod(i, n_pad)
+    chunk, tap = divmod(i, taps)
+    return chunk, tap, n, s, e
+
+
+def assert_packed_equal(got_bytes, want, taps, n_pad, what=""):
+    """got_bytes: the uint8 buffer of a packed weight; want: pack_reference's tensor.  Bytewise: padding must be +0, not -0, and every
+    byte of the buffer must have been written."""
+    got = got_bytes.cpu().view(want.dtype)
+    assert got.numel() == want.numel(), f"{what}: {got.numel()} packed elements, want {want.numel()}"
+    ibits = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[want.element_size()]
+    gb, wb = got.view(ibits), want.view(ibits)
+    if not torch.equal(gb, wb):
+        bad = (gb != wb).nonzero().view(-1)
+        i = int(bad[0])
+        mask = (1 << (8 * want.element_size())) - 1
+        raise AssertionError(f"{what}: {len(bad)} of {want.numel()} packed elements differ; first at (chunk, tap, n, slot, e) = "
+                             f"{pack_position(i, taps, n_pad, want.dtype)}: got {got[i].item()!r} (bits {int(gb[i]) & mask:#x}), "
+                             f"want {want[i].item()!r} (bits {int(wb[i]) & mask:#x})")
+
+
+# f32 bit patterns the pack has to convert or carry right, for every storage type
+PACK_EDGE_BITS = (
+    0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000,     # bf16 ties: +-(1 + 2^-8) -> 1 (even), +-(1 + 3 2^-8) -> 1 + 2^-6
+    0x3F801000, 0x3F803000, 0xBF801000, 0xBF803000,     # f16 ties: +-(1 + 2^-11) -> 1, +-(1 + 3 2^-11) -> 1 + 2^-9
+    0x3F808001, 0x3F807FFF, 0x3F801001, 0x3F800FFF,     # one f32 ulp above / below a tie
+    0x80000000, 0x00000000,                             # -0.0, +0.0
+    0x00010000, 0x80010000, 0x7F7F0000, 0xFF7F0000,     # bf16: smallest subnormal 2^-133, largest finite
+    0x00008000, 0x00018000, 0x0000C000,                 # bf16 subnormal ties (-> 0, -> 2 steps) and 3/4 of a step (-> 1 step)
+    0x33800000, 0xB3800000, 0x477FE000, 0xC77FE000,     # f16: smallest subnormal 2^-24, largest finite 65504
+    0x33000000, 0x33C00000, 0x33000001,                 # f16 subnormal ties 2^-25 (-> 0), 3 2^-25 (-> 2^-23), just above the first
+    0x477FF000, 0x477FEFFF, 0xC77FF000,                 # 65520 -> f16 inf, 65519.996 -> 65504, -65520 -> -inf
+    0x00000001, 0x80000001, 0x00400000, 0x007FFFFF,     # f32 subnormals
+    0x7F7FFFFF, 0xFF7FFFFF, 0x00800000,                 # f32 largest finite, smallest normal
+)
+
+
+def pack_source(key, shape, pmap, *, nan_outside=False):
+    """f32 OIHW source of a pack test: seeded normal values, PACK_EDGE_BITS at evenly spread elements that `pmap` addresses, and
+    (nan_outside) NaN in every element it does not address"""
+    g = torch.Generator().manual_seed(stable_seed("pack", key))
+    w = torch.randn(shape, generator=g, dtype=torch.float32)
+    flat = w.view(-1)
+    addressed = pmap[pmap >= 0].unique()
+    edge = torch.tensor([b - (1 << 32) if b >= 1 << 31 else b for b in PACK_EDGE_BITS], dtype=torch.int64).to(torch.int32).view(torch.float32)
+    assert addressed.numel() >= edge.numel()
+    flat[addressed[torch.arange(edge.numel()) * (addressed.numel() // edge.numel())]] = edge
+    if nan_outside:
+        outside = torch.ones(flat.numel(), dtype=torch.bool)
+        outside[addressed] = False
+        flat[outside] = float("nan")
+    return w
+
+
 def gelu64(z):
     return 0.5 * z * (1.0 + torch.special.erf(z / math.sqrt(2.0)))
 

@@ -10,7 +10,8 @@ from _conv_exact import (B_GRID, GELU16_ERR, PRODUCTION_TUNABLES, SCALE_GRID, SH
                          assert_exact_premise, assert_head_premise, assert_headq_premise, dyadic, expected, fold_stat_rows, from_blocked,
                          gelu64, gelu_exact_inputs, head_refs, head_tiles, head_weight_grid, is_conv_kernel, is_head_kernel,
                          kernel_name_table, later_trip_mask, mask_edge_values, needs_rounding, parse_kernel_name, pix_index, scaled,
-                         shuf2_perm, storage_ulp, stored_grid, sum_fits, tiles_per_workgroup, to_blocked, unpack_map, unpack_reference)
+                         shuf2_perm, storage_ulp, stored_grid, sum_fits, tiles_per_workgroup, to_blocked, unpack_map, unpack_reference,
+                         assert_packed_equal, pack_eps, pack_map, pack_reference, packed_matrices)
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -339,3 +340,193 @@ def test_gelu_screening_keeps_enough_inputs(dt, survivors):
     torch.testing.assert_close(g, F.gelu(z), rtol=0, atol=1e-15)
     lo, hi = (g - 2 * GELU16_ERR).float().to(dt), (g + 2 * GELU16_ERR).float().to(dt)
     assert torch.equal(lo[z != 0], hi[z != 0]) and torch.equal(lo[z != 0], g.float().to(dt)[z != 0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the helpers of tests/test_gpu_pack_exact.py: pack_map, pack_reference, packed_matrices, assert_packed_equal
+def _small_pack_cases():
+    import _pack_cases as P
+    return [(n, dt) for n in list(P.CASES) + list(P.CENTER) for dt in P.EVERY[n]["dtypes"]]
+
+
+def _pack_id(v):
+    import _pack_cases as P
+    return P.DT_NAME.get(v, v)
+
+
+@pytest.mark.parametrize("name,dt", _small_pack_cases(), ids=_pack_id)
+def test_pack_map_is_injective_and_covers_exactly_the_window(name, dt):
+    import _pack_cases as P
+    c = P.EVERY[name]
+    taps, k_pad, n_pad = P.geometry(name)
+    pmap = P.case_map(name, dt)
+    assert pmap.shape == (taps * k_pad * n_pad,) and pmap.dtype == torch.int64
+    idx = pmap[pmap >= 0]
+    assert idx.unique().numel() == idx.numel(), "two packed elements hold the same source element"
+    cout, cin, ks, _ = P.source_shape(name)
+    window = torch.zeros(cout, cin, ks, ks, dtype=torch.bool)
+    window[:, c["ci_begin"]:c["ci_begin"] + c["ci_count"]] = True
+    got = torch.zeros(window.numel(), dtype=torch.bool)
+    got[idx] = True
+    assert torch.equal(got.view_as(window), window)
+    assert int(pmap.min()) == -1                        # every case has padding (n_pad >= 128 > GEMM-N or k_pad > GEMM-K)
+
+
+@pytest.mark.parametrize("name,dt", [(n, dt) for n, dt in _small_pack_cases() if n.split("_")[1] in ("m0", "m2", "m4") and "center" not in n],
+                         ids=_pack_id)
+def test_pack_map_forward_modes_against_unpack_map(name, dt):
+    """de-swizzled to B[tap][k][n], the forward forms hold what the (validated) unpack map of the weight gradient puts at [n][tap][k]"""
+    import _pack_cases as P
+    c = P.EVERY[name]
+    taps, k_pad, n_pad = P.geometry(name)
+    B = packed_matrices(P.case_map(name, dt), taps, k_pad, n_pad, dt)
+    umap = unpack_map(c["mode"], c["cout"], c["cin"], c["ks"], k_pad, ci_begin=c["ci_begin"], ci_count=c["ci_count"], n_perm=P.perm_of(name))
+    assert torch.equal(B[:, :, :c["cout"]], umap.permute(1, 2, 0))
+    assert bool((B[:, :, c["cout"]:] == -1).all())
+
+
+def _packed64(mode, w, k_pad, n_pad, dt, **kw):
+    """B[tap][k][n] of a float64 weight, through pack_map / pack_reference / packed_matrices with the slot geometry of dt"""
+    cout, cin, ks, _ = w.shape
+    pmap = pack_map(mode, cout, cin, ks, k_pad, n_pad, dt, **kw)
+    taps = ks * ks if mode < 2 else 1
+    return packed_matrices(pack_reference(w, pmap, torch.float64), taps, k_pad, n_pad, dt)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("ks", [1, 3])
+def test_pack_map_mode1_against_conv2d_input(ks, dt):
+    """dgrad as the conv kernel computes it: a forward convolution of dy (rows in n_perm order) with the per-tap matrices"""
+    cout, cin, h, w, b, c = 8, 7, 6, 5, 2, 4
+    g = torch.Generator().manual_seed(21)
+    wt, dy = dyadic(g, (cout, cin, ks, ks), W_GRID), dyadic(g, (2, cout, h, w), X_GRID)
+    perm = shuf2_perm(cout)
+    B = _packed64(1, wt, 16, 128, dt, ci_begin=b, ci_count=c, n_perm=perm)
+    assert not bool(B[:, cout:].any()) and not bool(B[:, :, c:].any())
+    cols = F.unfold(dy[:, perm], ks, padding=ks // 2).view(2, cout, ks * ks, h * w)
+    dx = torch.einsum("bktl,tkn->bnl", cols, B[:, :cout, :c]).view(2, c, h, w)
+    want = torch.nn.grad.conv2d_input((2, cin, h, w), wt, dy, padding=ks // 2)
+    assert torch.equal(dx, want[:, b:b + c])
+    if ks == 3:     # the perturbation the GPU test must catch: taps not flipped
+        Bn = _packed64(1, wt.flip(2, 3), 16, 128, dt, ci_begin=b, ci_count=c, n_perm=perm)
+        assert not torch.equal(torch.einsum("bktl,tkn->bnl", cols, Bn[:, :cout, :c]).view(2, c, h, w), want[:, b:b + c])
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.float16])
+@pytest.mark.parametrize("ks", [1, 2, 3])
+def test_pack_map_mode3_against_conv2d_input(ks, dt):
+    """flat-K dgrad: one matmul gives the gradient of the im2col'ed window (ks = 2: the stride-2 patches), folded back to the image"""
+    cout, cin, h, w, b, c = 8, 6, 6, 4, 3, 2
+    g = torch.Generator().manual_seed(22)
+    stride, pad = (2, 0) if ks == 2 else (1, ks // 2)
+    wt = dyadic(g, (cout, cin, ks, ks), W_GRID)
+    dy = dyadic(g, (2, cout, h // stride, w // stride), X_GRID)
+    perm = shuf2_perm(cout)
+    B = _packed64(3, wt, 16, 128, dt, ci_begin=b, ci_count=c, n_perm=perm)[0]
+    dxcol = torch.einsum("bkl,kn->bnl", dy[:, perm].reshape(2, cout, -1), B[:cout, :c * ks * ks])
+    dx = F.fold(dxcol, (h, w), ks, padding=pad, stride=stride)
+    want = torch.nn.grad.conv2d_input((2, cin, h, w), wt, dy, padding=pad, stride=stride)
+    assert torch.equal(dx, want[:, b:b + c])
+    assert not bool(B[cout:].any()) and not bool(B[:, c * ks * ks:].any())
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("ks,cin", [(2, 5), (3, 18)])
+def test_pack_map_mode5_against_conv2d_input(ks, cin, dt):
+    """space-to-depth dgrad: one matmul over N = tap * cpad + ci, scattered back to the ks x ks patches"""
+    cout, oh, ow = 8, 3, 2
+    cpad = (cin + 15) // 16 * 16
+    g = torch.Generator().manual_seed(23)
+    wt, dy = dyadic(g, (cout, cin, ks, ks), W_GRID), dyadic(g, (2, cout, oh, ow), X_GRID)
+    n_pad = (ks * ks * cpad + 127) // 128 * 128
+    B = _packed64(5, wt, 16, n_pad, dt)[0]
+    d = torch.einsum("bkl,kn->bnl", dy.reshape(2, cout, oh * ow), B[:cout, :ks * ks * cpad]).view(2, ks, ks, cpad, oh, ow)
+    assert not bool(d[:, :, :, cin:].any()) and not bool(B[cout:].any()) and not bool(B[:, ks * ks * cpad:].any())
+    dx = d[:, :, :, :cin].permute(0, 3, 4, 1, 5, 2).reshape(2, cin, oh * ks, ow * ks)
+    assert torch.equal(dx, torch.nn.grad.conv2d_input((2, cin, oh * ks, ow * ks), wt, dy, stride=ks))
+
+
+@pytest.mark.parametrize("name", ["center_m2", "center_m3_perm", "center_m2_window", "center_m3_window"])
+def test_pack_map_centre_form_equals_the_zero_stuffed_pack(name):
+    import _pack_cases as P
+    c = P.EVERY[name]
+    for dt in P.ALL:
+        taps, k_pad, n_pad = P.geometry(name)
+        w1 = P.source(name, dt)
+        w3 = torch.zeros(c["cout"], c["cin"], 3, 3)
+        w3[:, :, 1, 1] = w1[:, :, 0, 0]                 # _Conv.weight_for
+        plain = pack_map(c["mode"], c["cout"], c["cin"], 3, k_pad, n_pad, dt, ci_begin=c["ci_begin"], ci_count=c["ci_count"],
+                         n_perm=P.perm_of(name))
+        want = pack_reference(w3, plain, dt)
+        got = P.reference(name, dt, w1)
+        assert bool((got != 0).any())
+        assert_packed_equal(got.view(torch.uint8), want, taps, n_pad, name)
+
+
+def _truncated(w, dt):
+    """f32 -> dt by dropping mantissa bits (what a conversion without rounding stores); bf16 only"""
+    assert dt == torch.bfloat16
+    return (w.view(torch.int32) >> 16).to(torch.int16).view(torch.bfloat16)
+
+
+@pytest.mark.parametrize("name,dt", [("t33_m0_all", torch.bfloat16), ("t33_m1_all", torch.float16), ("el_m2_k3_head", torch.bfloat16),
+                                     ("el_m5_k2", torch.float32)], ids=_pack_id)
+def test_assert_packed_equal_reports_each_perturbed_reference(name, dt):
+    """what the GPU comparison must catch, shown on the references of the GPU cases: the helper accepts the reference itself and
+    reports a pack with the slot swizzle dropped, with -0 in the padding, with a truncating conversion, with stale bytes, and (mode
+    1) with the taps not flipped"""
+    import _pack_cases as P
+    c = P.EVERY[name]
+    taps, k_pad, n_pad = P.geometry(name)
+    pmap = P.case_map(name, dt)
+    w = P.source(name, dt)
+    want = P.reference(name, dt, w)
+    assert_packed_equal(want.clone().view(torch.uint8), want, taps, n_pad, name)
+    eps, kch = pack_eps(dt)
+
+    def reported(got, what):
+        with pytest.raises(AssertionError, match=r"packed elements differ; first at \(chunk, tap, n, slot, e\)"):
+            assert_packed_equal(got.view(torch.uint8), want, taps, n_pad, what)
+
+    # slots in natural order for every column (the columns with bit 3 set have theirs exchanged)
+    m5 = pmap.view(k_pad // kch, taps, n_pad, 2, eps)
+    flip = ((torch.arange(n_pad) >> 3) & 1).bool().view(1, 1, -1, 1, 1)
+    reported(pack_reference(w, torch.where(flip, m5.flip(3), m5).reshape(-1), dt), "swizzle dropped")
+    # -0 in the padding
+    neg = want.clone()
+    neg[pmap < 0] = -0.0
+    reported(neg, "-0 padding")
+    # a buffer whose padding was never written (0xFF bytes)
+    stale = want.clone().view(torch.uint8).view(-1, want.element_size())
+    stale[pmap < 0] = 0xFF
+    reported(stale.view(-1), "padding not written")
+    if dt == torch.bfloat16:
+        tr = torch.zeros_like(want)
+        tr[pmap >= 0] = _truncated(w, dt).reshape(-1)[pmap[pmap >= 0]]
+        reported(tr, "truncation")
+    if c["mode"] == 1:
+        reported(pack_reference(w.flip(2, 3), pmap, dt), "taps not flipped")
+    # a source element outside the window must not matter, one inside must
+    w2 = P.source(name, dt, nan_outside=True)
+    assert_packed_equal(P.reference(name, dt, w2).view(torch.uint8), want, taps, n_pad, name)
+    assert not bool(P.reference(name, dt, w2).float().isnan().any())
+
+
+def test_pack_reference_converts_the_edge_values_to_nearest_even():
+    from _conv_exact import PACK_EDGE_BITS
+    f = torch.tensor([b - (1 << 32) if b >= 1 << 31 else b for b in PACK_EDGE_BITS], dtype=torch.int64).to(torch.int32).view(torch.float32)
+    ident = torch.arange(f.numel())
+    bits = lambda dt: [int(v) & 0xFFFF for v in pack_reference(f, ident, dt).view(torch.int16)]
+    b16, h16 = bits(torch.bfloat16), bits(torch.float16)
+    at = {b: i for i, b in enumerate(PACK_EDGE_BITS)}
+    assert b16[at[0x3F808000]] == 0x3F80 and b16[at[0x3F818000]] == 0x3F82 and b16[at[0xBF808000]] == 0xBF80
+    assert b16[at[0x3F808001]] == 0x3F81 and b16[at[0x3F807FFF]] == 0x3F80
+    assert b16[at[0x80000000]] == 0x8000 and b16[at[0x00010000]] == 0x0001 and b16[at[0x7F7F0000]] == 0x7F7F
+    assert b16[at[0x00008000]] == 0x0000 and b16[at[0x00018000]] == 0x0002 and b16[at[0x0000C000]] == 0x0001
+    assert b16[at[0x7F7FFFFF]] == 0x7F80                 # the largest f32 rounds to bf16 infinity
+    assert h16[at[0x3F801000]] == 0x3C00 and h16[at[0x3F803000]] == 0x3C02 and h16[at[0x3F801001]] == 0x3C01
+    assert h16[at[0x33800000]] == 0x0001 and h16[at[0x33000000]] == 0x0000 and h16[at[0x33C00000]] == 0x0002 and h16[at[0x33000001]] == 0x0001
+    assert h16[at[0x477FE000]] == 0x7BFF and h16[at[0x477FF000]] == 0x7C00 and h16[at[0x477FEFFF]] == 0x7BFF and h16[at[0xC77FF000]] == 0xFC00
+    assert h16[at[0x80000000]] == 0x8000 and h16[at[0x00000001]] == 0x0000 and h16[at[0x80000001]] == 0x8000
+    assert torch.equal(pack_reference(f, ident, torch.float32).view(torch.int32), f.view(torch.int32))
+    assert pack_reference(f, torch.tensor([-1]), torch.float16).view(torch.int16).item() == 0
