@@ -8,7 +8,7 @@
 // fused 3x3 loop would not fit in LDS, and these variants are in no benchmark configuration -- the im2col buffer costs 9x the
 // activation's traffic and buys the tuned GEMM loops for every dilation.
 // PSP_Pooling: k x k max pooling (k = 1, 2, 4, 8), bilinear resize back (align_corners = False) and their gradients.
-#include "common.h"
+#include "nhwc.h"
 
 namespace {
 
@@ -17,9 +17,6 @@ constexpr int TPB = 256;
 template <typename T> __device__ __forceinline__ float ld(const void* p, long i) { return (float)((const T*)p)[i]; }
 template <typename T> __device__ __forceinline__ void st(void* p, long i, float v) { ((T*)p)[i] = (T)v; }
 template <typename T> __device__ __forceinline__ float rnd(float v) { return (float)(T)v; }
-
-struct Slice { const void* p; int cs, co; };
-struct MSlice { void* p; int cs, co; };
 
 template <typename T>
 __global__ void input_plain_kernel(const float* __restrict__ x, void* out, int n, int c, long hw, int out_cs, float a, float b) {
@@ -34,7 +31,7 @@ __global__ void input_plain_kernel(const float* __restrict__ x, void* out, int n
 
 // col[pix][t * cp + ci] = act(in[pix + off_t][ci]), zero outside the image and for ci >= c
 template <typename T>
-__global__ void im2col_dil_kernel(Slice in, int c, const float* __restrict__ scale, const float* __restrict__ shift, void* col, int cp,
+__global__ void im2col_dil_kernel(Ref in, int c, const float* __restrict__ scale, const float* __restrict__ shift, void* col, int cp,
                                   int n, int h, int w, int dil) {
     const long total = (long)n * h * w * 9 * cp;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -86,7 +83,7 @@ __device__ __forceinline__ void flush(const Walk& wk, int cbase, int c, float (&
 // out[pix][ci] = sum_t dcol[pix - off_t][t * cp + ci], then (optional) the ReLU mask of the pre-activation y*scale+shift and the
 // BatchNorm-backward statistics [sum g, sum g * xhat(y)]
 template <typename T>
-__global__ void col2im_dil_kernel(const void* dcol, int cp, MSlice out, int c, int n, int h, int w, int dil, Slice y,
+__global__ void col2im_dil_kernel(const void* dcol, int cp, MRef out, int c, int n, int h, int w, int dil, Ref y,
                                   const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
                                   const float* __restrict__ invstd, double* stats) {
     __shared__ float lds[2 * TPB];
@@ -124,7 +121,7 @@ __global__ void col2im_dil_kernel(const void* dcol, int cp, MSlice out, int c, i
 
 // stats[0:c] += sum x, stats[c:2c] += sum x^2 over the pixels of an NHWC slice
 template <typename T>
-__global__ void channel_stats_kernel(Slice x, int c, long npix, double* stats) {
+__global__ void channel_stats_kernel(Ref x, int c, long npix, double* stats) {
     __shared__ float lds[2 * TPB];
     const Walk wk = make_walk(c);
     const int tid = threadIdx.x, lc = tid % wk.cw, lr = tid / wk.cw;
@@ -143,7 +140,7 @@ __global__ void channel_stats_kernel(Slice x, int c, long npix, double* stats) {
 struct SumArgs { const void* p[8]; int cs[8], co[8]; int n; };
 
 template <typename T>
-__global__ void sum_relu_kernel(SumArgs a, MSlice out, long npix, int c, int relu) {
+__global__ void sum_relu_kernel(SumArgs a, MRef out, long npix, int c, int relu) {
     const long total = npix * c;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int ci = (int)(i % c);
@@ -157,7 +154,7 @@ __global__ void sum_relu_kernel(SumArgs a, MSlice out, long npix, int c, int rel
 
 // dz = dout where out > 0 (mode 0), or out = relu(x * scale + shift) (mode 1: `a` is x, `b` unused)
 template <typename T>
-__global__ void mask_or_affine_kernel(Slice a, Slice b, const float* __restrict__ scale, const float* __restrict__ shift, MSlice out, long npix, int c,
+__global__ void mask_or_affine_kernel(Ref a, Ref b, const float* __restrict__ scale, const float* __restrict__ shift, MRef out, long npix, int c,
                                       int mode) {
     const long total = npix * c;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -173,7 +170,7 @@ __global__ void mask_or_affine_kernel(Slice a, Slice b, const float* __restrict_
 
 // F.max_pool2d(x, k): floor mode, windows [k*oy, k*oy + k)
 template <typename T>
-__global__ void maxpool_k_kernel(Slice in, MSlice out, int n, int h, int w, int c, int k) {
+__global__ void maxpool_k_kernel(Ref in, MRef out, int n, int h, int w, int c, int k) {
     const int ho = h / k, wo = w / k;
     const long total = (long)n * ho * wo * c;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -192,7 +189,7 @@ __global__ void maxpool_k_kernel(Slice in, MSlice out, int n, int h, int w, int 
 // gradient of the above: each input pixel belongs to at most one window; the gradient goes to the window's first maximum in
 // row-major scan order (torch's choice); pixels outside every window (h % k rows / w % k columns) get zero
 template <typename T>
-__global__ void maxpool_k_bwd_kernel(Slice act, Slice dpool, MSlice dx, int n, int h, int w, int c, int k) {
+__global__ void maxpool_k_bwd_kernel(Ref act, Ref dpool, MRef dx, int n, int h, int w, int c, int k) {
     const int ho = h / k, wo = w / k;
     const long total = (long)n * h * w * c;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -230,7 +227,7 @@ __device__ __forceinline__ void bil_src(int dst, int in_size, int out_size, int&
 }
 
 template <typename T>
-__global__ void bilinear_up_kernel(Slice in, MSlice out, int n, int hs, int ws, int h, int w, int c) {
+__global__ void bilinear_up_kernel(Ref in, MRef out, int n, int hs, int ws, int h, int w, int c) {
     const long total = (long)n * h * w * c;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int ci = (int)(i % c);
@@ -248,7 +245,7 @@ __global__ void bilinear_up_kernel(Slice in, MSlice out, int n, int hs, int ws, 
 
 // gradient in gather form: a source pixel collects from the destination pixels whose 2 x 2 footprint contains it
 template <typename T>
-__global__ void bilinear_up_bwd_kernel(Slice dout, MSlice din, int n, int hs, int ws, int h, int w, int c) {
+__global__ void bilinear_up_bwd_kernel(Ref dout, MRef din, int n, int hs, int ws, int h, int w, int c) {
     const long total = (long)n * hs * ws * c;
     const float ry = (float)h / (float)hs, rx = (float)w / (float)ws;      // destination pixels per source pixel (not always an integer)
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -278,27 +275,14 @@ __global__ void bilinear_up_bwd_kernel(Slice dout, MSlice din, int n, int hs, in
     }
 }
 
-inline unsigned grid_for(long total) {
-    long b = (total + TPB - 1) / TPB;
-    return (unsigned)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
-}
-
 }  // namespace
-
-#define PSSR_DT_SWITCH(dtype, CALL)                                                           \
-    switch (dtype) {                                                                          \
-    case PSSR_F32: { using T = float; CALL; } break;                                          \
-    case PSSR_BF16: { using T = bf16_t; CALL; } break;                                        \
-    case PSSR_F16: { using T = f16_t; CALL; } break;                                          \
-    default: pssr_set_error("bad dtype %d", dtype); return PSSR_ERR_ARG;                      \
-    }
 
 extern "C" int pssr_input_plain(const float* x_nchw, void* out, int n, int c, int h, int w, int out_cs, float pre_scale, float pre_shift,
                                 int dtype, pssr_stream_t s) {
     PSSR_CHECK(x_nchw && out && n > 0 && c > 0 && h > 0 && w > 0 && out_cs >= c, PSSR_ERR_ARG, "input_plain: bad args");
     const long hw = (long)h * w;
-    PSSR_DT_SWITCH(dtype, hipLaunchKernelGGL(input_plain_kernel<T>, dim3(grid_for((long)n * hw * out_cs)), dim3(TPB), 0, (hipStream_t)s, x_nchw, out, n, c, hw,
-                                             out_cs, pre_scale, pre_shift))
+    DISPATCH_T(dtype, hipLaunchKernelGGL(input_plain_kernel<T>, dim3(grid1d((long)n * hw * out_cs, 16384)), dim3(TPB), 0, (hipStream_t)s, x_nchw, out, n, c, hw,
+                                         out_cs, pre_scale, pre_shift));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -307,8 +291,8 @@ extern "C" int pssr_im2col_dil(const void* in, int in_cs, int in_co, int c, cons
                                int n, int h, int w, int dil, int dtype, pssr_stream_t s) {
     PSSR_CHECK(in && col && c > 0 && cp >= c && n > 0 && h > 0 && w > 0 && dil >= 1 && in_co + c <= in_cs, PSSR_ERR_ARG, "im2col_dil: bad args");
     PSSR_CHECK((scale == nullptr) == (shift == nullptr), PSSR_ERR_ARG, "im2col_dil: scale and shift go together");
-    PSSR_DT_SWITCH(dtype, hipLaunchKernelGGL(im2col_dil_kernel<T>, dim3(grid_for((long)n * h * w * 9 * cp)), dim3(TPB), 0, (hipStream_t)s,
-                                             Slice{in, in_cs, in_co}, c, scale, shift, col, cp, n, h, w, dil))
+    DISPATCH_T(dtype, hipLaunchKernelGGL(im2col_dil_kernel<T>, dim3(grid1d((long)n * h * w * 9 * cp, 16384)), dim3(TPB), 0, (hipStream_t)s,
+                                         Ref{in, in_cs, in_co}, c, scale, shift, col, cp, n, h, w, dil));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -322,8 +306,8 @@ extern "C" int pssr_col2im_dil(const void* dcol, int cp, void* out, int out_cs, 
     const Walk wk = make_walk(c);
     long blocks = ((long)n * h * w + wk.rows - 1) / wk.rows;
     if (blocks > 2048) blocks = 2048;
-    PSSR_DT_SWITCH(dtype, hipLaunchKernelGGL(col2im_dil_kernel<T>, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)s, dcol, cp,
-                                             MSlice{out, out_cs, out_co}, c, n, h, w, dil, Slice{y, y_cs, y_co}, scale, shift, mean, invstd, stats))
+    DISPATCH_T(dtype, hipLaunchKernelGGL(col2im_dil_kernel<T>, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)s, dcol, cp,
+                                         MRef{out, out_cs, out_co}, c, n, h, w, dil, Ref{y, y_cs, y_co}, scale, shift, mean, invstd, stats));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -333,7 +317,7 @@ extern "C" int pssr_channel_stats_nhwc(const void* x, int cs, int co, int c, int
     const Walk wk = make_walk(c);
     long blocks = (npix + wk.rows - 1) / wk.rows;
     if (blocks > 2048) blocks = 2048;
-    PSSR_DT_SWITCH(dtype, hipLaunchKernelGGL(channel_stats_kernel<T>, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)s, Slice{x, cs, co}, c, (long)npix, stats))
+    DISPATCH_T(dtype, hipLaunchKernelGGL(channel_stats_kernel<T>, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)s, Ref{x, cs, co}, c, (long)npix, stats));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -344,8 +328,8 @@ extern "C" int pssr_sum_relu(const void* const* ins, const int* in_cs, const int
     SumArgs a;
     a.n = n_in;
     for (int k = 0; k < n_in; ++k) { a.p[k] = ins[k]; a.cs[k] = in_cs[k]; a.co[k] = in_co[k]; }
-    PSSR_DT_SWITCH(dtype, hipLaunchKernelGGL(sum_relu_kernel<T>, dim3(grid_for((long)npix * c)), dim3(TPB), 0, (hipStream_t)s, a, MSlice{out, out_cs, out_co},
-                                             (long)npix, c, relu))
+    DISPATCH_T(dtype, hipLaunchKernelGGL(sum_relu_kernel<T>, dim3(grid1d((long)npix * c, 16384)), dim3(TPB), 0, (hipStream_t)s, a, MRef{out, out_cs, out_co},
+                                         (long)npix, c, relu));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -353,8 +337,8 @@ extern "C" int pssr_sum_relu(const void* const* ins, const int* in_cs, const int
 extern "C" int pssr_relu_mask(const void* dout, int do_cs, int do_co, const void* out, int o_cs, int o_co, void* dz, int dz_cs, int dz_co,
                               int64_t npix, int c, int dtype, pssr_stream_t s) {
     PSSR_CHECK(dout && out && dz && npix > 0 && c > 0, PSSR_ERR_ARG, "relu_mask: bad args");
-    PSSR_DT_SWITCH(dtype, hipLaunchKernelGGL(mask_or_affine_kernel<T>, dim3(grid_for((long)npix * c)), dim3(TPB), 0, (hipStream_t)s, Slice{dout, do_cs, do_co},
-                                             Slice{out, o_cs, o_co}, (const float*)nullptr, (const float*)nullptr, MSlice{dz, dz_cs, dz_co}, (long)npix, c, 0))
+    DISPATCH_T(dtype, hipLaunchKernelGGL(mask_or_affine_kernel<T>, dim3(grid1d((long)npix * c, 16384)), dim3(TPB), 0, (hipStream_t)s, Ref{dout, do_cs, do_co},
+                                         Ref{out, o_cs, o_co}, (const float*)nullptr, (const float*)nullptr, MRef{dz, dz_cs, dz_co}, (long)npix, c, 0));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -362,8 +346,8 @@ extern "C" int pssr_relu_mask(const void* dout, int do_cs, int do_co, const void
 extern "C" int pssr_affine_relu(const void* x, int cs, int co, const float* scale, const float* shift, void* out, int out_cs, int out_co,
                                 int64_t npix, int c, int dtype, pssr_stream_t s) {
     PSSR_CHECK(x && scale && shift && out && npix > 0 && c > 0, PSSR_ERR_ARG, "affine_relu: bad args");
-    PSSR_DT_SWITCH(dtype, hipLaunchKernelGGL(mask_or_affine_kernel<T>, dim3(grid_for((long)npix * c)), dim3(TPB), 0, (hipStream_t)s, Slice{x, cs, co},
-                                             Slice{nullptr, 0, 0}, scale, shift, MSlice{out, out_cs, out_co}, (long)npix, c, 1))
+    DISPATCH_T(dtype, hipLaunchKernelGGL(mask_or_affine_kernel<T>, dim3(grid1d((long)npix * c, 16384)), dim3(TPB), 0, (hipStream_t)s, Ref{x, cs, co},
+                                         Ref{nullptr, 0, 0}, scale, shift, MRef{out, out_cs, out_co}, (long)npix, c, 1));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -371,8 +355,8 @@ extern "C" int pssr_affine_relu(const void* x, int cs, int co, const float* scal
 extern "C" int pssr_maxpool_k(const void* in, int in_cs, int in_co, void* out, int out_cs, int out_co, int n, int h, int w, int c, int k,
                               int dtype, pssr_stream_t s) {
     PSSR_CHECK(in && out && n > 0 && c > 0 && k >= 1 && h >= k && w >= k, PSSR_ERR_ARG, "maxpool_k: bad args (k=%d on %dx%d)", k, h, w);
-    PSSR_DT_SWITCH(dtype, hipLaunchKernelGGL(maxpool_k_kernel<T>, dim3(grid_for((long)n * (h / k) * (w / k) * c)), dim3(TPB), 0, (hipStream_t)s,
-                                             Slice{in, in_cs, in_co}, MSlice{out, out_cs, out_co}, n, h, w, c, k))
+    DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_k_kernel<T>, dim3(grid1d((long)n * (h / k) * (w / k) * c, 16384)), dim3(TPB), 0, (hipStream_t)s,
+                                         Ref{in, in_cs, in_co}, MRef{out, out_cs, out_co}, n, h, w, c, k));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -380,8 +364,8 @@ extern "C" int pssr_maxpool_k(const void* in, int in_cs, int in_co, void* out, i
 extern "C" int pssr_maxpool_k_bwd(const void* act, int act_cs, int act_co, const void* dpool, int dp_cs, int dp_co, void* dx, int dx_cs, int dx_co,
                                   int n, int h, int w, int c, int k, int dtype, pssr_stream_t s) {
     PSSR_CHECK(act && dpool && dx && n > 0 && c > 0 && k >= 1 && h >= k && w >= k, PSSR_ERR_ARG, "maxpool_k_bwd: bad args");
-    PSSR_DT_SWITCH(dtype, hipLaunchKernelGGL(maxpool_k_bwd_kernel<T>, dim3(grid_for((long)n * h * w * c)), dim3(TPB), 0, (hipStream_t)s, Slice{act, act_cs, act_co},
-                                             Slice{dpool, dp_cs, dp_co}, MSlice{dx, dx_cs, dx_co}, n, h, w, c, k))
+    DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_k_bwd_kernel<T>, dim3(grid1d((long)n * h * w * c, 16384)), dim3(TPB), 0, (hipStream_t)s, Ref{act, act_cs, act_co},
+                                         Ref{dpool, dp_cs, dp_co}, MRef{dx, dx_cs, dx_co}, n, h, w, c, k));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -389,8 +373,8 @@ extern "C" int pssr_maxpool_k_bwd(const void* act, int act_cs, int act_co, const
 extern "C" int pssr_bilinear_up(const void* in, int in_cs, int in_co, void* out, int out_cs, int out_co, int n, int hs, int ws, int h, int w,
                                 int c, int dtype, pssr_stream_t s) {
     PSSR_CHECK(in && out && n > 0 && c > 0 && hs > 0 && ws > 0 && h >= hs && w >= ws, PSSR_ERR_ARG, "bilinear_up: bad args");
-    PSSR_DT_SWITCH(dtype, hipLaunchKernelGGL(bilinear_up_kernel<T>, dim3(grid_for((long)n * h * w * c)), dim3(TPB), 0, (hipStream_t)s, Slice{in, in_cs, in_co},
-                                             MSlice{out, out_cs, out_co}, n, hs, ws, h, w, c))
+    DISPATCH_T(dtype, hipLaunchKernelGGL(bilinear_up_kernel<T>, dim3(grid1d((long)n * h * w * c, 16384)), dim3(TPB), 0, (hipStream_t)s, Ref{in, in_cs, in_co},
+                                         MRef{out, out_cs, out_co}, n, hs, ws, h, w, c));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -398,8 +382,8 @@ extern "C" int pssr_bilinear_up(const void* in, int in_cs, int in_co, void* out,
 extern "C" int pssr_bilinear_up_bwd(const void* dout, int do_cs, int do_co, void* din, int di_cs, int di_co, int n, int hs, int ws, int h, int w,
                                     int c, int dtype, pssr_stream_t s) {
     PSSR_CHECK(dout && din && n > 0 && c > 0 && hs > 0 && ws > 0 && h >= hs && w >= ws, PSSR_ERR_ARG, "bilinear_up_bwd: bad args");
-    PSSR_DT_SWITCH(dtype, hipLaunchKernelGGL(bilinear_up_bwd_kernel<T>, dim3(grid_for((long)n * hs * ws * c)), dim3(TPB), 0, (hipStream_t)s, Slice{dout, do_cs, do_co},
-                                             MSlice{din, di_cs, di_co}, n, hs, ws, h, w, c))
+    DISPATCH_T(dtype, hipLaunchKernelGGL(bilinear_up_bwd_kernel<T>, dim3(grid1d((long)n * hs * ws * c, 16384)), dim3(TPB), 0, (hipStream_t)s, Ref{dout, do_cs, do_co},
+                                         MRef{din, di_cs, di_co}, n, hs, ws, h, w, c));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }

@@ -284,3 +284,5 @@ void pssr_set_error(const char* fmt, ...);
     } while (0)
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// workgroups of 256 threads that cover `total` items, at least one and at most `cap` (the kernels walk the rest with a grid stride)
+static inline int grid1d(long total, int cap) { long b = (total + 255) / 256; return (int)(b < cap ? (b > 0 ? b : 1) : cap); }

@@ -288,8 +288,6 @@ __global__ void gen_pair_geometry_kernel(const GatherItem* __restrict__ items, u
     }
 }
 
-static inline int grid1d(long total) { long b = (total + 255) / 256; return (int)(b < 8192 ? (b > 0 ? b : 1) : 8192); }
-
 }  // namespace
 
 extern "C" {
@@ -310,7 +308,7 @@ int pssr_bilinear_down_u8(const uint8_t* hr, uint8_t* tmp, uint8_t* lr, int plan
 
 int pssr_u8_to_f32(const uint8_t* in, float* out, int64_t n, pssr_stream_t s) {
     PSSR_CHECK(in && out && n > 0, PSSR_ERR_ARG, "u8_to_f32: bad args");
-    hipLaunchKernelGGL(u8_to_f32_kernel, dim3(grid1d(n)), dim3(256), 0, (hipStream_t)s, in, out, (long)n);
+    hipLaunchKernelGGL(u8_to_f32_kernel, dim3(grid1d(n, 8192)), dim3(256), 0, (hipStream_t)s, in, out, (long)n);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -319,7 +317,7 @@ int pssr_crappify_gaussian(const float* in, float* out, int tiles, int64_t per_t
                            uint64_t seed, uint64_t tile_offset, const double* noise, int flags, const uint64_t* tile_counter,
                            pssr_stream_t s) {
     PSSR_CHECK(in && out && tiles > 0 && per_tile > 0 && flags >= 0 && flags <= 3, PSSR_ERR_ARG, "crappify_gaussian: bad args");
-    hipLaunchKernelGGL(gaussian_noise_kernel, dim3(grid1d((long)tiles * per_tile)), dim3(256), 0, (hipStream_t)s, in, out, tiles, (long)per_tile,
+    hipLaunchKernelGGL(gaussian_noise_kernel, dim3(grid1d((long)tiles * per_tile, 8192)), dim3(256), 0, (hipStream_t)s, in, out, tiles, (long)per_tile,
                        intensity, gain, spread, seed, tile_offset, noise, flags, tile_counter);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
@@ -328,7 +326,7 @@ int pssr_crappify_gaussian(const float* in, float* out, int tiles, int64_t per_t
 int pssr_crappify_poisson(const float* in, float* out, int tiles, int64_t per_tile, float intensity, float gain, float spread,
                           uint64_t seed, uint64_t tile_offset, int flags, const uint64_t* tile_counter, pssr_stream_t s) {
     PSSR_CHECK(in && out && tiles > 0 && per_tile > 0 && flags >= 0 && flags <= 3, PSSR_ERR_ARG, "crappify_poisson: bad args");
-    hipLaunchKernelGGL(poisson_noise_kernel, dim3(grid1d((long)tiles * per_tile)), dim3(256), 0, (hipStream_t)s, in, out, tiles, (long)per_tile,
+    hipLaunchKernelGGL(poisson_noise_kernel, dim3(grid1d((long)tiles * per_tile, 8192)), dim3(256), 0, (hipStream_t)s, in, out, tiles, (long)per_tile,
                        intensity, gain, spread, seed, tile_offset, flags, tile_counter);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
@@ -337,7 +335,7 @@ int pssr_crappify_poisson(const float* in, float* out, int tiles, int64_t per_ti
 int pssr_crappify_poisson_samples(const float* in, const double* samples, float* out, int64_t n, double intensity, double gain, int flags,
                                   pssr_stream_t s) {
     PSSR_CHECK(in && samples && out && n > 0 && flags >= 0 && flags <= 3, PSSR_ERR_ARG, "crappify_poisson_samples: bad args");
-    hipLaunchKernelGGL(poisson_samples_kernel, dim3(grid1d((long)n)), dim3(256), 0, (hipStream_t)s, in, samples, out, (long)n, intensity, gain, flags);
+    hipLaunchKernelGGL(poisson_samples_kernel, dim3(grid1d((long)n, 8192)), dim3(256), 0, (hipStream_t)s, in, samples, out, (long)n, intensity, gain, flags);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -354,9 +352,9 @@ int pssr_counter_add(uint64_t* counter, uint64_t inc, pssr_stream_t s) {
 int pssr_gaussian_blur(const float* in, float* tmp, float* out, int planes, int h, int w, float sigma, float gain, int flags, pssr_stream_t s) {
     PSSR_CHECK(in && tmp && out && planes > 0 && h > 0 && w > 0 && sigma > 0.f && flags >= 0 && flags <= 3, PSSR_ERR_ARG, "gaussian_blur: bad args");
     const long total = (long)planes * h * w;
-    hipLaunchKernelGGL(blur_pass_kernel, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)s, in, tmp, planes, h, w, sigma, 0, 0.f, 0);
+    hipLaunchKernelGGL(blur_pass_kernel, dim3(grid1d(total, 8192)), dim3(256), 0, (hipStream_t)s, in, tmp, planes, h, w, sigma, 0, 0.f, 0);
     PSSR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(blur_pass_kernel, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)s, tmp, out, planes, h, w, sigma, 1, gain, flags);
+    hipLaunchKernelGGL(blur_pass_kernel, dim3(grid1d(total, 8192)), dim3(256), 0, (hipStream_t)s, tmp, out, planes, h, w, sigma, 1, gain, flags);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -364,7 +362,7 @@ int pssr_gaussian_blur(const float* in, float* tmp, float* out, int planes, int 
 int pssr_crappify_saltpepper(const float* in, float* out, int tiles, int64_t per_tile, float amount, float gain, float spread, uint64_t seed,
                              uint64_t tile_offset, int flags, const uint64_t* tile_counter, pssr_stream_t s) {
     PSSR_CHECK(in && out && tiles > 0 && per_tile > 0 && flags >= 0 && flags <= 3 && amount >= 0.f, PSSR_ERR_ARG, "crappify_saltpepper: bad args");
-    hipLaunchKernelGGL(saltpepper_kernel, dim3(grid1d((long)tiles * per_tile)), dim3(256), 0, (hipStream_t)s, in, out, tiles, (long)per_tile,
+    hipLaunchKernelGGL(saltpepper_kernel, dim3(grid1d((long)tiles * per_tile, 8192)), dim3(256), 0, (hipStream_t)s, in, out, tiles, (long)per_tile,
                        amount, gain, spread, seed, tile_offset, flags, tile_counter);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
@@ -375,10 +373,10 @@ int pssr_gaussian_blur_tiles(const float* in, float* tmp, float* out, int tiles,
     PSSR_CHECK(in && tmp && out && tiles > 0 && planes_per_tile > 0 && h > 0 && w > 0 && sigma >= 0.f && spread >= 0.f && flags >= 0 && flags <= 3,
                PSSR_ERR_ARG, "gaussian_blur_tiles: bad args");
     const long total = (long)tiles * planes_per_tile * h * w;
-    hipLaunchKernelGGL(blur_pass_tiles_kernel, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)s, in, tmp, tiles, planes_per_tile, h, w, sigma,
+    hipLaunchKernelGGL(blur_pass_tiles_kernel, dim3(grid1d(total, 8192)), dim3(256), 0, (hipStream_t)s, in, tmp, tiles, planes_per_tile, h, w, sigma,
                        spread, seed, tile_offset, 0, 0.f, 0, tile_counter);
     PSSR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(blur_pass_tiles_kernel, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)s, tmp, out, tiles, planes_per_tile, h, w, sigma,
+    hipLaunchKernelGGL(blur_pass_tiles_kernel, dim3(grid1d(total, 8192)), dim3(256), 0, (hipStream_t)s, tmp, out, tiles, planes_per_tile, h, w, sigma,
                        spread, seed, tile_offset, 1, gain, flags, tile_counter);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;

@@ -4,17 +4,12 @@
 // channels, so every wave touches whole 128-byte lines; per-channel reductions are accumulated in
 // registers (a thread keeps one channel group for its whole life), combined across the workgroup in
 // LDS and added to the f64 result with one atomic per channel per workgroup.
-#include "common.h"
+#include "nhwc.h"
+#include <type_traits>
 
 namespace {
 
 constexpr int TPB = 256;
-
-struct Ref { const void* p; int cs, co; };   // NHWC tensor slice: base, channel stride, channel offset
-struct MRef { void* p; int cs, co; };
-
-template <typename T> __device__ __forceinline__ const T* at(const Ref& r, long pix, int c) { return (const T*)r.p + pix * r.cs + r.co + c; }
-template <typename T> __device__ __forceinline__ T* at(const MRef& r, long pix, int c) { return (T*)r.p + pix * r.cs + r.co + c; }
 
 // Thread -> (pixel lane, channel group) assignment shared by every per-channel kernel.
 struct ChanMap {
@@ -82,16 +77,21 @@ __device__ __forceinline__ void for_items(const ChanMap& m, long npix, F f, G do
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-__global__ void nchw_stats_kernel(const float* __restrict__ x, int n, int c, long hw, float ps, float pb, double* stats) {
-    // one (image, channel) plane chunk per block column; grid = (chunks, n*c)
-    const int plane = blockIdx.y, ch = plane % c;
-    const float* src = x + (long)plane * hw;
-    float s1 = 0.f, s2 = 0.f;
-    for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < hw; i += (long)gridDim.x * TPB) {
-        const float v = fmaf(src[i], ps, pb);
-        s1 += v; s2 += v * v;
-    }
+// ---- steps that several kernels share, one copy each --------------------------------------------
+
+// flat index of an n x h x w pixel grid -> (image, row, column)
+struct PixPos { long img; int y, x; };
+__device__ __forceinline__ PixPos split_pix(long pix, int h, int w) {
+    PixPos p;
+    p.x = (int)(pix % w); pix /= w;
+    p.y = (int)(pix % h);
+    p.img = pix / h;
+    return p;
+}
+
+// Sum of two per-thread partials over the TPB threads of the workgroup (LDS tree), added to channel ch of the striped statistic rows
+// [s1][C] | [s2][C] by thread 0
+__device__ __forceinline__ void flush_plane(float s1, float s2, int ch, int c, double* stats) {
     __shared__ float r1[TPB], r2[TPB];
     r1[threadIdx.x] = s1; r2[threadIdx.x] = s2;
     __syncthreads();
@@ -103,6 +103,94 @@ __global__ void nchw_stats_kernel(const float* __restrict__ x, int n, int c, lon
         double* st = stats + (long)(blockIdx.x % PSSR_STAT_STRIPES) * 2 * c;
         stat_add(st + ch, (long)PSSR_STAT_STRIPES * 2 * c, r1[0]); stat_add(st + c + ch, (long)PSSR_STAT_STRIPES * 2 * c, r2[0]);
     }
+}
+
+// Thread -> channel group of the 16-bit kernels with a power-of-two group count cg = 1 << cg_log2: thread t0 of the launch keeps group
+// t0 & (cg - 1), `width` channels from c0, for its whole life (the grid stride is a multiple of cg); its items are t0, t0 + grid stride,
+// ... and item i belongs to pixel (or window) i >> cg_log2.  The grid stride stays in the loops.
+struct GroupMap {
+    int cg, g, c0;
+    long t0;
+    __device__ __forceinline__ GroupMap(int cg_log2, int width) {
+        cg = 1 << cg_log2;
+        t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
+        g = (int)(t0 & (cg - 1));
+        c0 = g * width;
+    }
+};
+__device__ __forceinline__ void load8(const float* p, float* v) { load4(p, v); load4(p + 4, v + 4); }
+
+// ReLU mask of N gradients by out > 0 and their BatchNorm-backward statistics: s1 += g, s2 += g * xhat
+template <int N>
+__device__ __forceinline__ void mask_accum(float* g, const float* o, const float* y, const float* mu, const float* is, float* s1, float* s2) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+        g[e] = o[e] > 0.f ? g[e] : 0.f;
+        s1[e] += g[e];
+        s2[e] += g[e] * (y[e] - mu[e]) * is[e];
+    }
+}
+
+// o[k][e] += g[e] for the FIRST maximum k of v[0..3][e] in row-major order of the 2x2 window (torch semantics), N channels.  A macro:
+// o[][] must stay in registers, and does not as an argument of a function.
+#define ROUTE_FIRST_MAX(N, v, g, o)                                                             \
+    _Pragma("unroll") for (int e_ = 0; e_ < (N); ++e_) {                                        \
+        int best_ = 0; float bv_ = (v)[0][e_];                                                  \
+        _Pragma("unroll") for (int k_ = 1; k_ < 4; ++k_) if ((v)[k_][e_] > bv_) { bv_ = (v)[k_][e_]; best_ = k_; } \
+        _Pragma("unroll") for (int k_ = 0; k_ < 4; ++k_) if (k_ == best_) (o)[k_][e_] += (g)[e_]; \
+    }
+
+// The 2x2 interleave of pixel shuffle (r = 2) on 16-bit values: e[4 c + k] <-> channel 8 g + c of high-resolution pixel k = 2 i + j
+// = (2 p.y + i, 2 p.x + j) of low-resolution pixel p (grid h x w), 16 bytes per pixel.  gather: hi -> e; else e -> hi, which takes an MRef.
+template <class R>
+__device__ __forceinline__ void quad8(R hi, PixPos p, int h, int w, int g, bool gather, unsigned short (&e)[32]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long phi = (p.img * 2 * h + 2 * p.y + (k >> 1)) * (2L * w) + 2 * p.x + (k & 1);
+        auto* hip_ = at<unsigned short>(hi, phi, g * 8);
+        unsigned short v[8];
+        if (gather) {
+            *(u32x4*)v = *(const u32x4*)hip_;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) e[4 * c + k] = v[c];
+        } else if constexpr (std::is_same<R, MRef>::value) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v[c] = e[4 * c + k];
+            *(u32x4*)hip_ = *(const u32x4*)v;
+        }
+    }
+}
+
+// Combine the 8-channel partial sums s1 / s2 that the threads of a workgroup hold for their fixed channel group (threads tid, tid + cg,
+// ... share channels; TPB is a multiple of cg) and add them to the striped f64 statistic rows: [sum][C] | [sum * xhat][C].  Group g's
+// eight channels start at g * pitch + off.
+__device__ __forceinline__ void flush_stats8(const float (&s1)[8], const float (&s2)[8], int cg, int pitch, int off, int c, double* __restrict__ stats,
+                                             float* lds) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { lds[tid * 16 + e] = s1[e]; lds[tid * 16 + 8 + e] = s2[e]; }
+    __syncthreads();
+    double* dst = stats + (long)(blockIdx.x % PSSR_STAT_STRIPES) * 2 * c;
+    for (int j = tid; j < cg * 16; j += TPB) {
+        const int g_ = j >> 4, q = j & 15;
+        float t = 0.f;
+        for (int k = g_; k < TPB; k += cg) t += lds[k * 16 + q];
+        stat_add(dst + (long)(q >> 3) * c + g_ * pitch + off + (q & 7), (long)PSSR_STAT_STRIPES * 2 * c, t);
+    }
+    __syncthreads();
+}
+
+// ------------------------------------------------------------------------------------------------
+__global__ void nchw_stats_kernel(const float* __restrict__ x, int n, int c, long hw, float ps, float pb, double* stats) {
+    // one (image, channel) plane chunk per block column; grid = (chunks, n*c)
+    const int plane = blockIdx.y, ch = plane % c;
+    const float* src = x + (long)plane * hw;
+    float s1 = 0.f, s2 = 0.f;
+    for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < hw; i += (long)gridDim.x * TPB) {
+        const float v = fmaf(src[i], ps, pb);
+        s1 += v; s2 += v * v;
+    }
+    flush_plane(s1, s2, ch, c, stats);
 }
 
 // Sum of the f64 statistic stripes for one channel with the stripes spread over SG thread groups of the workgroup (these kernels
@@ -143,13 +231,23 @@ __device__ __forceinline__ void stripe_sums(const double* __restrict__ base, lon
     }
 }
 
+// The opening of every kernel that folds striped rows: element i of this thread and its NV sums over `stripes` stripes of NV rows of n
+// doubles each.  False for the threads that have nothing to write (i >= n, or a partial-sum group).
+template <int NV>
+__device__ __forceinline__ bool fold_rows(const double* __restrict__ base, int n, int stripes, int& i, double (&sv)[NV]) {
+    i = blockIdx.x * STRIPE_CH + threadIdx.x;
+    long off[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) off[v] = (long)v * n + i;
+    stripe_sums<NV>(base, (long)NV * n, off, stripes, i < n, sv);
+    return i < n && threadIdx.y == 0;
+}
+
 __global__ void bn_finalize_kernel(const double* stats, double count, const float* gamma, const float* beta, float eps, float momentum,
                                    float* rmean, float* rvar, float* scale, float* shift, float* mean, float* invstd, int c) {
-    const int i = blockIdx.x * STRIPE_CH + threadIdx.x;
-    const long off[2] = {i, (long)c + i};
+    int i;
     double sv[2];
-    stripe_sums<2>(stats, 2L * c, off, PSSR_STAT_ROWS, i < c, sv);
-    if (i >= c || threadIdx.y != 0) return;
+    if (!fold_rows<2>(stats, c, PSSR_STAT_ROWS, i, sv)) return;
     const double s1 = sv[0], s2 = sv[1];
     const double mu = s1 / count;
     double var = s2 / count - mu * mu;
@@ -178,11 +276,9 @@ __global__ void bn_eval_kernel(const float* gamma, const float* beta, const floa
 
 __global__ void bn_bwd_coefs_kernel(const double* stats, double count, const float* gamma, const float* mean, const float* invstd,
                                     float* A, float* B, float* Cc, float* dgamma, float* dbeta, int c) {
-    const int i = blockIdx.x * STRIPE_CH + threadIdx.x;
-    const long off[2] = {i, (long)c + i};
+    int i;
     double sv[2];
-    stripe_sums<2>(stats, 2L * c, off, PSSR_STAT_ROWS, i < c, sv);
-    if (i >= c || threadIdx.y != 0) return;
+    if (!fold_rows<2>(stats, c, PSSR_STAT_ROWS, i, sv)) return;
     const double s1 = sv[0], s2 = sv[1];
     const double c1 = s1 / count, c2 = s2 / count;
     const double g = gamma[i], is = invstd[i], mu = mean[i];
@@ -200,10 +296,8 @@ __global__ void input_im2col_kernel(const float* __restrict__ x, T* __restrict__
     const long total = (long)n * h * w * xc;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int k = i % xc;
-        long pix = i / xc;
-        const int px = pix % w; pix /= w;
-        const int py = pix % h;
-        const int img = pix / h;
+        const PixPos p = split_pix(i / xc, h, w);
+        const int px = p.x, py = p.y, img = (int)p.img;
         float v = 0.f;
         if (k < 9 * c) {
             const int ch = k / 9, tap = k % 9;
@@ -244,17 +338,7 @@ __global__ void input_norm_bwd_kernel(const T* __restrict__ da, const T* __restr
         const float xh = (fmaf(x[((long)img * c + ch) * hw + i % hw], ps, pb) - mean[ch]) * invstd[ch];
         s1 += g; s2 += g * xh;
     }
-    __shared__ float r1[TPB], r2[TPB];
-    r1[threadIdx.x] = s1; r2[threadIdx.x] = s2;
-    __syncthreads();
-    for (int o = TPB / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { r1[threadIdx.x] += r1[threadIdx.x + o]; r2[threadIdx.x] += r2[threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        double* st = stats + (long)(blockIdx.x % PSSR_STAT_STRIPES) * 2 * c;
-        stat_add(st + ch, (long)PSSR_STAT_STRIPES * 2 * c, r1[0]); stat_add(st + c + ch, (long)PSSR_STAT_STRIPES * 2 * c, r2[0]);
-    }
+    flush_plane(s1, s2, ch, c, stats);
 }
 
 template <typename T>
@@ -263,10 +347,8 @@ __global__ void maxpool2_kernel(Ref in, MRef out, int n, int h, int w, int c) {
     const long total = (long)n * ho * wo * cg;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int c0 = (i % cg) * 4;
-        long pix = i / cg;
-        const int ox = pix % wo; pix /= wo;
-        const int oy = pix % ho;
-        const int img = pix / ho;
+        const PixPos p = split_pix(i / cg, ho, wo);
+        const int ox = p.x, oy = p.y, img = (int)p.img;
         const long p00 = ((long)img * h + 2 * oy) * w + 2 * ox;
         float a[4], b[4], cc[4], d[4], m[4];
         load4(at<T>(in, p00, c0), a); load4(at<T>(in, p00 + 1, c0), b);
@@ -284,10 +366,8 @@ __global__ void maxpool2_bwd_kernel(Ref act, Ref dpool, Ref dskip, MRef dout, in
     const long total = (long)n * ho * wo * cg;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int c0 = (i % cg) * 4;
-        long pix = i / cg;
-        const int ox = pix % wo; pix /= wo;
-        const int oy = pix % ho;
-        const int img = pix / ho;
+        const PixPos p = split_pix(i / cg, ho, wo);
+        const int ox = p.x, oy = p.y, img = (int)p.img;
         const long p00 = ((long)img * h + 2 * oy) * w + 2 * ox;
         const long pp[4] = {p00, p00 + 1, p00 + w, p00 + w + 1};
         float v[4][4], g[4], o[4][4];
@@ -299,14 +379,7 @@ __global__ void maxpool2_bwd_kernel(Ref act, Ref dpool, Ref dskip, MRef dout, in
             if (dskip.p) load4(at<T>(dskip, pp[k], c0), o[k]);
             else { o[k][0] = o[k][1] = o[k][2] = o[k][3] = 0.f; }
         }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            int best = 0; float bv = v[0][e];
-#pragma unroll
-            for (int k = 1; k < 4; ++k) if (v[k][e] > bv) { bv = v[k][e]; best = k; }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (k == best) o[k][e] += g[e];
-        }
+        ROUTE_FIRST_MAX(4, v, g, o)
 #pragma unroll
         for (int k = 0; k < 4; ++k) store4(at<T>(dout, pp[k], c0), o[k]);
     }
@@ -331,10 +404,8 @@ __global__ void pixel_shuffle_kernel(Ref lo, MRef hi, int n, int h, int w, int c
     const long total = (long)n * h * r * w * r * c_hi;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int c = i % c_hi;
-        long pix = i / c_hi;
-        const int X = pix % (w * r); pix /= (w * r);
-        const int Y = pix % (h * r);
-        const int img = pix / (h * r);
+        const PixPos p = split_pix(i / c_hi, h * r, w * r);
+        const int X = p.x, Y = p.y, img = (int)p.img;
         const long phi = ((long)img * h * r + Y) * (w * r) + X;
         const long plo = ((long)img * h + Y / r) * w + X / r;
         const int clo = c * r * r + (Y % r) * r + (X % r);
@@ -353,32 +424,15 @@ __global__ __launch_bounds__(TPB) void pixel_shuffle2_kernel(Ref lo, MRef hi, in
     const long total = (long)n * h * w * cg;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int g = (int)(i % cg);
-        long pix = i / cg;
-        const int x = (int)(pix % w); pix /= w;
-        const int y = (int)(pix % h);
-        const long img = pix / h;
-        const long plo = (img * h + y) * w + x;
+        const PixPos p = split_pix(i / cg, h, w);
+        const long plo = (p.img * h + p.y) * w + p.x;
         unsigned short* lop = (unsigned short*)lo.p + plo * lo.cs + lo.co + g * 32;
         unsigned short e[32];
         if (!inverse) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) *(u32x4*)(e + 8 * q) = *(const u32x4*)(lop + 8 * q);
         }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const long phi = (img * 2 * h + 2 * y + (k >> 1)) * (2L * w) + 2 * x + (k & 1);
-            unsigned short* hip_ = (unsigned short*)hi.p + phi * hi.cs + hi.co + g * 8;
-            unsigned short v[8];
-            if (!inverse) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c) v[c] = e[4 * c + k];
-                *(u32x4*)hip_ = *(const u32x4*)v;
-            } else {
-                *(u32x4*)v = *(const u32x4*)hip_;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) e[4 * c + k] = v[c];
-            }
-        }
+        quad8(hi, p, h, w, g, inverse != 0, e);
         if (inverse) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) *(u32x4*)(lop + 8 * q) = *(const u32x4*)(e + 8 * q);
@@ -401,12 +455,7 @@ __global__ void relu_bwd_stats_kernel(Ref dout, Ref out, Ref y, const float* mea
             float g[4], o[4], yv[4], mu[4], is[4];
             load4(at<T>(dout, pix, c0), g); load4(at<T>(out, pix, c0), o); load4(at<T>(y, pix, c0), yv);
             load4(mean + c0, mu); load4(invstd + c0, is);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                g[e] = o[e] > 0.f ? g[e] : 0.f;
-                acc[0][e] += g[e];
-                acc[1][e] += g[e] * (yv[e] - mu[e]) * is[e];
-            }
+            mask_accum<4>(g, o, yv, mu, is, acc[0], acc[1]);
             store4(at<T>(dz, pix, c0), g);
         },
         [&](int cg) { flush_sums<2>(m, cg, acc, stats, c, lds); reset(); });
@@ -435,13 +484,12 @@ template <typename T>
 __global__ __launch_bounds__(TPB) void bn_bwd_apply8_kernel(Ref g, Ref y, const float* __restrict__ A, const float* __restrict__ B,
                                                             const float* __restrict__ Cc, MRef dy, long npix, int c, int cg_log2) {
     using X = TT<T>;
-    const int cg = 1 << cg_log2;
-    const long t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const int c0 = (int)(t0 & (cg - 1)) * 8;
+    const GroupMap m(cg_log2, 8);
+    const int c0 = m.c0;
     float a[8], b[8], cc[8];
-    load4(A + c0, a); load4(A + c0 + 4, a + 4); load4(B + c0, b); load4(B + c0 + 4, b + 4); load4(Cc + c0, cc); load4(Cc + c0 + 4, cc + 4);
+    load8(A + c0, a); load8(B + c0, b); load8(Cc + c0, cc);
     const long total = npix << cg_log2;
-    for (long i = t0; i < total; i += (long)gridDim.x * blockDim.x) {
+    for (long i = m.t0; i < total; i += (long)gridDim.x * blockDim.x) {
         const long pix = i >> cg_log2;
         float gv[8], yv[8], o[8];
         X::unpack(*(const u32x4*)at<T>(g, pix, c0), gv);
@@ -459,13 +507,12 @@ template <typename T>
 __global__ __launch_bounds__(TPB) void bn_relu_apply8_kernel(Ref y, const float* __restrict__ scale, const float* __restrict__ shift, MRef a, long npix,
                                                              int cg_log2) {
     using X = TT<T>;
-    const int cg = 1 << cg_log2;
-    const long t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const int c0 = (int)(t0 & (cg - 1)) * 8;
+    const GroupMap m(cg_log2, 8);
+    const int c0 = m.c0;
     float sc[8], sh[8];
-    load4(scale + c0, sc); load4(scale + c0 + 4, sc + 4); load4(shift + c0, sh); load4(shift + c0 + 4, sh + 4);
+    load8(scale + c0, sc); load8(shift + c0, sh);
     const long total = npix << cg_log2;
-    for (long i = t0; i < total; i += (long)gridDim.x * blockDim.x) {
+    for (long i = m.t0; i < total; i += (long)gridDim.x * blockDim.x) {
         const long pix = i >> cg_log2;
         *(u32x4*)at<T>(a, pix, c0) = X::bn_relu(*(const u32x4*)at<T>(y, pix, c0), sc, sh);
     }
@@ -476,57 +523,23 @@ __global__ __launch_bounds__(TPB) void relu_bwd_stats8_kernel(Ref dout, Ref out,
                                                               MRef dz, double* __restrict__ stats, long npix, int c, int cg_log2) {
     using X = TT<T>;
     __shared__ float lds[TPB * 16];
-    const int cg = 1 << cg_log2;
-    const long t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const int cgi = (int)(t0 & (cg - 1)), c0 = cgi * 8;
+    const GroupMap m(cg_log2, 8);
+    const int c0 = m.c0;
     float mu[8], is[8], s1[8], s2[8];
-    load4(mean + c0, mu); load4(mean + c0 + 4, mu + 4); load4(invstd + c0, is); load4(invstd + c0 + 4, is + 4);
+    load8(mean + c0, mu); load8(invstd + c0, is);
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
     const long total = npix << cg_log2;
-    for (long i = t0; i < total; i += (long)gridDim.x * blockDim.x) {
+    for (long i = m.t0; i < total; i += (long)gridDim.x * blockDim.x) {
         const long pix = i >> cg_log2;
         float gv[8], ov[8], yv[8];
         X::unpack(*(const u32x4*)at<T>(dout, pix, c0), gv);
         X::unpack(*(const u32x4*)at<T>(out, pix, c0), ov);
         X::unpack(*(const u32x4*)at<T>(y, pix, c0), yv);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            gv[e] = ov[e] > 0.f ? gv[e] : 0.f;
-            s1[e] += gv[e];
-            s2[e] += gv[e] * (yv[e] - mu[e]) * is[e];
-        }
+        mask_accum<8>(gv, ov, yv, mu, is, s1, s2);
         *(u32x4*)at<T>(dz, pix, c0) = X::pack(gv);
     }
-    // threads tid, tid + cg, ... of the workgroup hold the same channels (TPB is a multiple of cg): combine, then f64 atomics
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { lds[tid * 16 + e] = s1[e]; lds[tid * 16 + 8 + e] = s2[e]; }
-    __syncthreads();
-    double* dst = stats + (long)(blockIdx.x % PSSR_STAT_STRIPES) * 2 * c;
-    for (int j = tid; j < cg * 16; j += TPB) {
-        const int g_ = j >> 4, q = j & 15;
-        float t = 0.f;
-        for (int k = g_; k < TPB; k += cg) t += lds[k * 16 + q];
-        stat_add(dst + (long)(q >> 3) * c + g_ * 8 + (q & 7), (long)PSSR_STAT_STRIPES * 2 * c, t);
-    }
-}
-
-// Combine the 8-channel partial sums s1 / s2 that the threads of a workgroup hold for their fixed channel group (threads tid, tid + cg,
-// ... share channels; TPB is a multiple of cg) and add them to the striped f64 statistic rows: [sum][C] | [sum * xhat][C].
-__device__ __forceinline__ void flush_stats8(const float (&s1)[8], const float (&s2)[8], int cg, int c, double* __restrict__ stats, float* lds) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { lds[tid * 16 + e] = s1[e]; lds[tid * 16 + 8 + e] = s2[e]; }
-    __syncthreads();
-    double* dst = stats + (long)(blockIdx.x % PSSR_STAT_STRIPES) * 2 * c;
-    for (int j = tid; j < cg * 16; j += TPB) {
-        const int g_ = j >> 4, q = j & 15;
-        float t = 0.f;
-        for (int k = g_; k < TPB; k += cg) t += lds[k * 16 + q];
-        stat_add(dst + (long)(q >> 3) * c + g_ * 8 + (q & 7), (long)PSSR_STAT_STRIPES * 2 * c, t);
-    }
-    __syncthreads();
+    flush_stats8(s1, s2, m.cg, 8, 0, c, stats, lds);
 }
 
 // relu_bwd_stats8 with the max-pool backward folded into its loader (round 4: 4 launches and 3 tensor passes per encoder level less on the
@@ -541,20 +554,18 @@ __global__ __launch_bounds__(TPB) void relu_bwd_stats8_pool_kernel(Ref dpool, Re
                                                                    int n, int h, int w, int c, int cg_log2) {
     using X = TT<T>;
     __shared__ float lds[TPB * 16];
-    const int cg = 1 << cg_log2;
-    const long t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const int c0 = (int)(t0 & (cg - 1)) * 8;
+    const GroupMap m(cg_log2, 8);
+    const int c0 = m.c0;
     float mu[8], is[8], s1[8], s2[8];
-    load4(mean + c0, mu); load4(mean + c0 + 4, mu + 4); load4(invstd + c0, is); load4(invstd + c0 + 4, is + 4);
+    load8(mean + c0, mu); load8(invstd + c0, is);
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
     const int ho = h >> 1, wo = w >> 1;
     const long total = ((long)n * ho * wo) << cg_log2;
-    for (long i = t0; i < total; i += (long)gridDim.x * blockDim.x) {
-        long win = i >> cg_log2;
-        const int ox = (int)(win % wo); win /= wo;
-        const int oy = (int)(win % ho);
-        const long img = win / ho;
+    for (long i = m.t0; i < total; i += (long)gridDim.x * blockDim.x) {
+        const PixPos win = split_pix(i >> cg_log2, ho, wo);
+        const int ox = win.x, oy = win.y;
+        const long img = win.img;
         const long p00 = (img * h + 2 * oy) * w + 2 * ox;
         const long pp[4] = {p00, p00 + 1, p00 + w, p00 + w + 1};
         float ov[4][8], gv[4][8], yv[4][8], gp[8];
@@ -565,28 +576,16 @@ __global__ __launch_bounds__(TPB) void relu_bwd_stats8_pool_kernel(Ref dpool, Re
             X::unpack(*(const u32x4*)at<T>(dskip, pp[k], c0), gv[k]);
             X::unpack(*(const u32x4*)at<T>(y, pp[k], c0), yv[k]);
         }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int best = 0; float bv = ov[0][e];
-#pragma unroll
-            for (int k = 1; k < 4; ++k) if (ov[k][e] > bv) { bv = ov[k][e]; best = k; }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (k == best) gv[k][e] += gp[e];
-        }
+        ROUTE_FIRST_MAX(8, ov, gp, gv)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float r[8];
             X::unpack(X::pack(gv[k]), r);            // d(out) in the storage type, as the separate max-pool backward stored it
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                r[e] = ov[k][e] > 0.f ? r[e] : 0.f;
-                s1[e] += r[e];
-                s2[e] += r[e] * (yv[k][e] - mu[e]) * is[e];
-            }
+            mask_accum<8>(r, ov[k], yv[k], mu, is, s1, s2);
             *(u32x4*)at<T>(dz, pp[k], c0) = X::pack(r);
         }
     }
-    flush_stats8(s1, s2, cg, c, stats, lds);
+    flush_stats8(s1, s2, m.cg, 8, 0, c, stats, lds);
 }
 
 // relu_bwd_stats8 with the inverse pixel shuffle (r = 2) folded into its loader: the block output was shuffled into the first c / 4
@@ -600,63 +599,33 @@ __global__ __launch_bounds__(TPB) void relu_bwd_stats8_unshuffle_kernel(Ref dhi,
     using X = TT<T>;
     static_assert(sizeof(T) == 2, "16-bit storage");
     __shared__ float lds[TPB * 16];
-    const int cg = 1 << cg_log2;                        // 32-channel groups
-    const long t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const int g32 = (int)(t0 & (cg - 1)), c0 = g32 * 32;
+    const GroupMap m(cg_log2, 32);                      // 32-channel groups
+    const int c0 = m.c0;
     float s1[4][8], s2[4][8];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
         for (int e = 0; e < 8; ++e) { s1[q][e] = 0.f; s2[q][e] = 0.f; }
     const long total = ((long)n * h * w) << cg_log2;
-    for (long i = t0; i < total; i += (long)gridDim.x * blockDim.x) {
-        long pix = i >> cg_log2;
-        const int x = (int)(pix % w); pix /= w;
-        const int yy = (int)(pix % h);
-        const long img = pix / h;
-        const long plo = (img * h + yy) * w + x;
+    for (long i = m.t0; i < total; i += (long)gridDim.x * blockDim.x) {
+        const PixPos p = split_pix(i >> cg_log2, h, w);
+        const long plo = (p.img * h + p.y) * w + p.x;
         unsigned short e16[32];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const long phi = (img * 2 * h + 2 * yy + (k >> 1)) * (2L * w) + 2 * x + (k & 1);
-            unsigned short v[8];
-            *(u32x4*)v = *(const u32x4*)((const unsigned short*)dhi.p + phi * dhi.cs + dhi.co + g32 * 8);
-#pragma unroll
-            for (int ch = 0; ch < 8; ++ch) e16[4 * ch + k] = v[ch];
-        }
+        quad8(dhi, p, h, w, m.g, true, e16);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             float gv[8], ov[8], yv[8], mu[8], is[8];
             X::unpack(*(const u32x4*)(e16 + 8 * q), gv);
             X::unpack(*(const u32x4*)at<T>(out, plo, c0 + 8 * q), ov);
             X::unpack(*(const u32x4*)at<T>(y, plo, c0 + 8 * q), yv);
-            load4(mean + c0 + 8 * q, mu); load4(mean + c0 + 8 * q + 4, mu + 4);
-            load4(invstd + c0 + 8 * q, is); load4(invstd + c0 + 8 * q + 4, is + 4);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                gv[e] = ov[e] > 0.f ? gv[e] : 0.f;
-                s1[q][e] += gv[e];
-                s2[q][e] += gv[e] * (yv[e] - mu[e]) * is[e];
-            }
+            load8(mean + c0 + 8 * q, mu); load8(invstd + c0 + 8 * q, is);
+            mask_accum<8>(gv, ov, yv, mu, is, s1[q], s2[q]);
             *(u32x4*)at<T>(dz, plo, c0 + 8 * q) = X::pack(gv);
         }
     }
     // four rounds through the 16 KB combine buffer: round q carries channels c0 + 8 q .. + 7 of every 32-channel group
-    const int tid = threadIdx.x;
-    double* dst = stats + (long)(blockIdx.x % PSSR_STAT_STRIPES) * 2 * c;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { lds[tid * 16 + e] = s1[q][e]; lds[tid * 16 + 8 + e] = s2[q][e]; }
-        __syncthreads();
-        for (int j = tid; j < cg * 16; j += TPB) {
-            const int g_ = j >> 4, r = j & 15;
-            float t = 0.f;
-            for (int k = g_; k < TPB; k += cg) t += lds[k * 16 + r];
-            stat_add(dst + (long)(r >> 3) * c + g_ * 32 + 8 * q + (r & 7), (long)PSSR_STAT_STRIPES * 2 * c, t);
-        }
-        __syncthreads();
-    }
+    for (int q = 0; q < 4; ++q) flush_stats8(s1[q], s2[q], m.cg, 32, 8 * q, c, stats, lds);
 }
 
 template <typename T>
@@ -701,40 +670,44 @@ __global__ void clip_u8_kernel(const float* __restrict__ in, uint8_t* __restrict
     }
 }
 
-__global__ void f64_to_f32_kernel(const double* in, float* out, int n, int accumulate, int stripes) {
-    const int i = blockIdx.x * STRIPE_CH + threadIdx.x;
-    const long off[1] = {i};
+// out[i] (+)= the sum over the stripes of in[stripe][i]
+__device__ __forceinline__ void fold_to_f32(const double* in, float* out, int n, int accumulate, int stripes) {
+    int i;
     double sv[1];
-    stripe_sums<1>(in, (long)n, off, stripes, i < n, sv);
-    if (i >= n || threadIdx.y != 0) return;
-    const double s = sv[0];
-    out[i] = accumulate ? out[i] + (float)s : (float)s;
+    if (!fold_rows<1>(in, n, stripes, i, sv)) return;
+    out[i] = accumulate ? out[i] + (float)sv[0] : (float)sv[0];
 }
+
+__global__ void f64_to_f32_kernel(const double* in, float* out, int n, int accumulate, int stripes) { fold_to_f32(in, out, n, accumulate, stripes); }
 
 // several folds by one launch (blockIdx.y = item): RDNet's backward pass ends ~115 bias / LayerNorm gradient sums per step this way
 __global__ void f64_to_f32_batch_kernel(pssr_fold_batch items, int stripes) {
     const int it = blockIdx.y;
     const int n = items.n[it];
     if ((int)(blockIdx.x * STRIPE_CH) >= n) return;          // (uniform per workgroup)
-    const int i = blockIdx.x * STRIPE_CH + threadIdx.x;
-    const long off[1] = {i};
-    double sv[1];
-    stripe_sums<1>(items.src[it], (long)n, off, stripes, i < n, sv);
-    if (i >= n || threadIdx.y != 0) return;
-    float* out = items.dst[it];
-    out[i] = items.accumulate[it] ? out[i] + (float)sv[0] : (float)sv[0];
+    fold_to_f32(items.src[it], items.dst[it], n, items.accumulate[it], stripes);
 }
 
-static inline int grid1d(long total) { long b = (total + TPB - 1) / TPB; return (int)(b < 8192 ? (b > 0 ? b : 1) : 8192); }
+// ---- host side: which calls take the 8-channel kernels, and with what launch ----------------------
+
+// 16-bit storage, a power-of-two channel count that one workgroup's groups cover, every slice 16-byte aligned (`align_or`: the OR of all
+// channel strides and offsets)
+bool takes_chan8(int dtype, int c, int align_or) { return dtype != PSSR_F32 && c >= 8 && c <= 8 * TPB && (c & (c - 1)) == 0 && (align_or & 7) == 0; }
+
+// log2 of the number of `width`-channel groups of c channels (c / width a power of two)
+int group_log2(int c, int width) {
+    int lg = 0;
+    while ((width << lg) < c) ++lg;
+    return lg;
+}
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL)                                             \
+// runs CALL with T = bf16_t or f16_t (the caller has excluded f32)
+#define DISPATCH_16(dtype, CALL)                                            \
     do {                                                                    \
         if ((dtype) == PSSR_BF16) { using T = bf16_t; CALL; }               \
-        else if ((dtype) == PSSR_F16) { using T = f16_t; CALL; }            \
-        else if ((dtype) == PSSR_F32) { using T = float; CALL; }            \
-        else { pssr_set_error("bad dtype %d", (dtype)); return PSSR_ERR_ARG; } \
+        else { using T = f16_t; CALL; }                                     \
     } while (0)
 
 extern "C" {
@@ -779,7 +752,7 @@ int pssr_input_im2col(const float* x, void* xcol, int n, int c, int h, int w, in
                       const float* scale, const float* shift, int dtype, pssr_stream_t s) {
     PSSR_CHECK(x && xcol && scale && shift && n > 0 && c > 0 && h > 0 && w > 0 && xc >= 9 * c && xc % 16 == 0, PSSR_ERR_ARG, "input_im2col: bad args");
     const long total = (long)n * h * w * xc;
-    DISPATCH_T(dtype, hipLaunchKernelGGL(input_im2col_kernel<T>, dim3(grid1d(total)), dim3(TPB), 0, (hipStream_t)s, x, (T*)xcol, n, c, h, w, xc,
+    DISPATCH_T(dtype, hipLaunchKernelGGL(input_im2col_kernel<T>, dim3(grid1d(total, 8192)), dim3(TPB), 0, (hipStream_t)s, x, (T*)xcol, n, c, h, w, xc,
                                          pre_scale, pre_shift, scale, shift));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
@@ -806,14 +779,11 @@ int pssr_input_norm_bwd(const void* dxcol_a, const void* dxcol_b, int xc, const 
     return pssr_input_norm_bwd2(dxcol_a, dxcol_b, xc, nullptr, 0, 0, x, pre_scale, pre_shift, mean, invstd, n, c, h, w, stats, dtype, s);
 }
 
-#define CHECK_REF(name, cs, co, c)                                                                               \
-    PSSR_CHECK((cs) % 4 == 0 && (co) % 4 == 0 && (co) + (c) <= (cs), PSSR_ERR_ARG, name ": bad channel stride/offset (%d,%d,%d)", cs, co, c)
-
 int pssr_maxpool2(const void* in, int in_cs, int in_co, void* out, int out_cs, int out_co, int n, int h, int w, int c, int dtype, pssr_stream_t s) {
     PSSR_CHECK(in && out && n > 0 && h > 1 && w > 1 && c > 0 && c % 4 == 0, PSSR_ERR_ARG, "maxpool2: bad args");
     CHECK_REF("maxpool2 in", in_cs, in_co, c); CHECK_REF("maxpool2 out", out_cs, out_co, c);
     const long total = (long)n * (h / 2) * (w / 2) * (c / 4);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool2_kernel<T>, dim3(grid1d(total)), dim3(TPB), 0, (hipStream_t)s, Ref{in, in_cs, in_co}, MRef{out, out_cs, out_co}, n, h, w, c));
+    DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool2_kernel<T>, dim3(grid1d(total, 8192)), dim3(TPB), 0, (hipStream_t)s, Ref{in, in_cs, in_co}, MRef{out, out_cs, out_co}, n, h, w, c));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -825,7 +795,7 @@ int pssr_maxpool2_bwd(const void* act, int act_cs, int act_co, const void* dpool
     CHECK_REF("maxpool2_bwd act", act_cs, act_co, c); CHECK_REF("maxpool2_bwd dpool", dp_cs, dp_co, c); CHECK_REF("maxpool2_bwd dout", do_cs, do_co, c);
     if (dskip) CHECK_REF("maxpool2_bwd dskip", ds_cs, ds_co, c);
     const long total = (long)n * (h / 2) * (w / 2) * (c / 4);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool2_bwd_kernel<T>, dim3(grid1d(total)), dim3(TPB), 0, (hipStream_t)s, Ref{act, act_cs, act_co},
+    DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool2_bwd_kernel<T>, dim3(grid1d(total, 8192)), dim3(TPB), 0, (hipStream_t)s, Ref{act, act_cs, act_co},
                                          Ref{dpool, dp_cs, dp_co}, Ref{dskip, ds_cs, ds_co}, MRef{dout, do_cs, do_co}, n, h, w, c));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
@@ -838,12 +808,12 @@ int pssr_pixel_shuffle(const void* lo, int lo_cs, int lo_co, void* hi, int hi_cs
     const long total = (long)n * h * r * w * r * c_hi;
     if (r == 2 && dtype != PSSR_F32 && c_hi % 8 == 0 && ((lo_cs | lo_co | hi_cs | hi_co) & 7) == 0) {
         const long threads = (long)n * h * w * (c_hi / 8);
-        hipLaunchKernelGGL(pixel_shuffle2_kernel<bf16_t>, dim3(grid1d(threads)), dim3(TPB), 0, (hipStream_t)s, Ref{lo, lo_cs, lo_co},
+        hipLaunchKernelGGL(pixel_shuffle2_kernel<bf16_t>, dim3(grid1d(threads, 8192)), dim3(TPB), 0, (hipStream_t)s, Ref{lo, lo_cs, lo_co},
                            MRef{hi, hi_cs, hi_co}, n, h, w, c_hi, inverse);      // a byte permutation: one build serves bf16 and fp16
         PSSR_LAUNCH_CHECK();
         return PSSR_OK;
     }
-    DISPATCH_T(dtype, hipLaunchKernelGGL(pixel_shuffle_kernel<T>, dim3(grid1d(total)), dim3(TPB), 0, (hipStream_t)s, Ref{lo, lo_cs, lo_co},
+    DISPATCH_T(dtype, hipLaunchKernelGGL(pixel_shuffle_kernel<T>, dim3(grid1d(total, 8192)), dim3(TPB), 0, (hipStream_t)s, Ref{lo, lo_cs, lo_co},
                                          MRef{hi, hi_cs, hi_co}, n, h, w, c_hi, r, inverse));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
@@ -859,16 +829,11 @@ int pssr_relu_bwd_stats_pool(const void* dpool, int dp_cs, int dp_co, const void
     PSSR_CHECK(((dp_cs | dp_co | ds_cs | ds_co | o_cs | o_co | y_cs | y_co | dz_cs | dz_co) & 7) == 0, PSSR_ERR_ARG, "relu_bwd_stats_pool: strides / offsets must be multiples of 8");
     CHECK_REF("relu_bwd_stats_pool dpool", dp_cs, dp_co, c); CHECK_REF("relu_bwd_stats_pool dskip", ds_cs, ds_co, c);
     CHECK_REF("relu_bwd_stats_pool out", o_cs, o_co, c); CHECK_REF("relu_bwd_stats_pool y", y_cs, y_co, c); CHECK_REF("relu_bwd_stats_pool dz", dz_cs, dz_co, c);
-    int lg = 0;
-    while ((8 << lg) < c) ++lg;
+    const int lg = group_log2(c, 8);
     const long threads = ((long)n * (h / 2) * (w / 2)) << lg;
-    const int grid = (int)((threads + TPB - 1) / TPB < 2048 ? (threads + TPB - 1) / TPB : 2048);
-    if (dtype == PSSR_BF16)
-        hipLaunchKernelGGL(relu_bwd_stats8_pool_kernel<bf16_t>, dim3(grid), dim3(TPB), 0, (hipStream_t)s, Ref{dpool, dp_cs, dp_co}, Ref{dskip, ds_cs, ds_co},
-                           Ref{out, o_cs, o_co}, Ref{y, y_cs, y_co}, mean, invstd, MRef{dz, dz_cs, dz_co}, stats, n, h, w, c, lg);
-    else
-        hipLaunchKernelGGL(relu_bwd_stats8_pool_kernel<f16_t>, dim3(grid), dim3(TPB), 0, (hipStream_t)s, Ref{dpool, dp_cs, dp_co}, Ref{dskip, ds_cs, ds_co},
-                           Ref{out, o_cs, o_co}, Ref{y, y_cs, y_co}, mean, invstd, MRef{dz, dz_cs, dz_co}, stats, n, h, w, c, lg);
+    DISPATCH_16(dtype, hipLaunchKernelGGL(relu_bwd_stats8_pool_kernel<T>, dim3(grid1d(threads, 2048)), dim3(TPB), 0, (hipStream_t)s, Ref{dpool, dp_cs, dp_co},
+                                          Ref{dskip, ds_cs, ds_co}, Ref{out, o_cs, o_co}, Ref{y, y_cs, y_co}, mean, invstd, MRef{dz, dz_cs, dz_co}, stats,
+                                          n, h, w, c, lg));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -883,16 +848,10 @@ int pssr_relu_bwd_stats_unshuffle(const void* dhi, int dh_cs, int dh_co, const v
     PSSR_CHECK(dh_co + c / 4 <= dh_cs, PSSR_ERR_ARG, "relu_bwd_stats_unshuffle: high-resolution slice exceeds its stride");
     CHECK_REF("relu_bwd_stats_unshuffle out", o_cs, o_co, c); CHECK_REF("relu_bwd_stats_unshuffle y", y_cs, y_co, c);
     CHECK_REF("relu_bwd_stats_unshuffle dz", dz_cs, dz_co, c);
-    int lg = 0;
-    while ((32 << lg) < c) ++lg;
+    const int lg = group_log2(c, 32);
     const long threads = ((long)n * h * w) << lg;
-    const int grid = (int)((threads + TPB - 1) / TPB < 2048 ? (threads + TPB - 1) / TPB : 2048);
-    if (dtype == PSSR_BF16)
-        hipLaunchKernelGGL(relu_bwd_stats8_unshuffle_kernel<bf16_t>, dim3(grid), dim3(TPB), 0, (hipStream_t)s, Ref{dhi, dh_cs, dh_co}, Ref{out, o_cs, o_co},
-                           Ref{y, y_cs, y_co}, mean, invstd, MRef{dz, dz_cs, dz_co}, stats, n, h, w, c, lg);
-    else
-        hipLaunchKernelGGL(relu_bwd_stats8_unshuffle_kernel<f16_t>, dim3(grid), dim3(TPB), 0, (hipStream_t)s, Ref{dhi, dh_cs, dh_co}, Ref{out, o_cs, o_co},
-                           Ref{y, y_cs, y_co}, mean, invstd, MRef{dz, dz_cs, dz_co}, stats, n, h, w, c, lg);
+    DISPATCH_16(dtype, hipLaunchKernelGGL(relu_bwd_stats8_unshuffle_kernel<T>, dim3(grid1d(threads, 2048)), dim3(TPB), 0, (hipStream_t)s, Ref{dhi, dh_cs, dh_co},
+                                          Ref{out, o_cs, o_co}, Ref{y, y_cs, y_co}, mean, invstd, MRef{dz, dz_cs, dz_co}, stats, n, h, w, c, lg));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -903,17 +862,10 @@ int pssr_relu_bwd_stats(const void* dout, int do_cs, int do_co, const void* out,
     PSSR_CHECK(dout && out && y && mean && invstd && dz && stats && npix > 0 && c > 0 && c % 4 == 0, PSSR_ERR_ARG, "relu_bwd_stats: bad args");
     CHECK_REF("relu_bwd_stats dout", do_cs, do_co, c); CHECK_REF("relu_bwd_stats out", o_cs, o_co, c);
     CHECK_REF("relu_bwd_stats y", y_cs, y_co, c); CHECK_REF("relu_bwd_stats dz", dz_cs, dz_co, c);
-    if (dtype != PSSR_F32 && c >= 8 && c <= 8 * TPB && (c & (c - 1)) == 0 && ((do_cs | do_co | o_cs | o_co | y_cs | y_co | dz_cs | dz_co) & 7) == 0) {
-        int lg = 0;
-        while ((8 << lg) < c) ++lg;
-        const long threads = npix << lg;
-        const int grid = (int)((threads + TPB - 1) / TPB < 2048 ? (threads + TPB - 1) / TPB : 2048);
-        if (dtype == PSSR_BF16)
-            hipLaunchKernelGGL(relu_bwd_stats8_kernel<bf16_t>, dim3(grid), dim3(TPB), 0, (hipStream_t)s, Ref{dout, do_cs, do_co}, Ref{out, o_cs, o_co},
-                               Ref{y, y_cs, y_co}, mean, invstd, MRef{dz, dz_cs, dz_co}, stats, (long)npix, c, lg);
-        else
-            hipLaunchKernelGGL(relu_bwd_stats8_kernel<f16_t>, dim3(grid), dim3(TPB), 0, (hipStream_t)s, Ref{dout, do_cs, do_co}, Ref{out, o_cs, o_co},
-                               Ref{y, y_cs, y_co}, mean, invstd, MRef{dz, dz_cs, dz_co}, stats, (long)npix, c, lg);
+    if (takes_chan8(dtype, c, do_cs | do_co | o_cs | o_co | y_cs | y_co | dz_cs | dz_co)) {
+        const int lg = group_log2(c, 8);
+        DISPATCH_16(dtype, hipLaunchKernelGGL(relu_bwd_stats8_kernel<T>, dim3(grid1d((long)npix << lg, 2048)), dim3(TPB), 0, (hipStream_t)s, Ref{dout, do_cs, do_co},
+                                              Ref{out, o_cs, o_co}, Ref{y, y_cs, y_co}, mean, invstd, MRef{dz, dz_cs, dz_co}, stats, (long)npix, c, lg));
         PSSR_LAUNCH_CHECK();
         return PSSR_OK;
     }
@@ -928,21 +880,14 @@ int pssr_bn_bwd_apply(const void* g, int g_cs, int g_co, const void* y, int y_cs
                       const float* coef_c, void* dy, int dy_cs, int dy_co, int64_t npix, int c, int dtype, pssr_stream_t s) {
     PSSR_CHECK(g && y && coef_a && coef_b && coef_c && dy && npix > 0 && c > 0 && c % 4 == 0, PSSR_ERR_ARG, "bn_bwd_apply: bad args");
     CHECK_REF("bn_bwd_apply g", g_cs, g_co, c); CHECK_REF("bn_bwd_apply y", y_cs, y_co, c); CHECK_REF("bn_bwd_apply dy", dy_cs, dy_co, c);
-    if (dtype != PSSR_F32 && c >= 8 && c <= 8 * TPB && (c & (c - 1)) == 0 && ((g_cs | g_co | y_cs | y_co | dy_cs | dy_co) & 7) == 0) {
-        int lg = 0;
-        while ((8 << lg) < c) ++lg;
-        const long threads = (long)npix << lg;
-        const int grid = (int)((threads + TPB - 1) / TPB < 4096 ? (threads + TPB - 1) / TPB : 4096);
-        if (dtype == PSSR_BF16)
-            hipLaunchKernelGGL(bn_bwd_apply8_kernel<bf16_t>, dim3(grid), dim3(TPB), 0, (hipStream_t)s, Ref{g, g_cs, g_co}, Ref{y, y_cs, y_co}, coef_a, coef_b,
-                               coef_c, MRef{dy, dy_cs, dy_co}, (long)npix, c, lg);
-        else
-            hipLaunchKernelGGL(bn_bwd_apply8_kernel<f16_t>, dim3(grid), dim3(TPB), 0, (hipStream_t)s, Ref{g, g_cs, g_co}, Ref{y, y_cs, y_co}, coef_a, coef_b,
-                               coef_c, MRef{dy, dy_cs, dy_co}, (long)npix, c, lg);
+    if (takes_chan8(dtype, c, g_cs | g_co | y_cs | y_co | dy_cs | dy_co)) {
+        const int lg = group_log2(c, 8);
+        DISPATCH_16(dtype, hipLaunchKernelGGL(bn_bwd_apply8_kernel<T>, dim3(grid1d((long)npix << lg, 4096)), dim3(TPB), 0, (hipStream_t)s, Ref{g, g_cs, g_co},
+                                              Ref{y, y_cs, y_co}, coef_a, coef_b, coef_c, MRef{dy, dy_cs, dy_co}, (long)npix, c, lg));
         PSSR_LAUNCH_CHECK();
         return PSSR_OK;
     }
-    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(grid1d(npix * (c / 4))), dim3(TPB), 0, (hipStream_t)s, Ref{g, g_cs, g_co},
+    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(grid1d(npix * (c / 4), 8192)), dim3(TPB), 0, (hipStream_t)s, Ref{g, g_cs, g_co},
                                          Ref{y, y_cs, y_co}, coef_a, coef_b, coef_c, MRef{dy, dy_cs, dy_co}, (long)npix, c));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
@@ -951,17 +896,12 @@ int pssr_bn_bwd_apply(const void* g, int g_cs, int g_co, const void* y, int y_cs
 int pssr_bn_relu_apply(const void* y, int y_cs, int y_co, const float* scale, const float* shift, void* a, int a_cs, int a_co, int64_t npix, int c, int dtype,
                        pssr_stream_t s) {
     PSSR_CHECK(y && scale && shift && a && npix > 0, PSSR_ERR_ARG, "bn_relu_apply: bad args");
-    PSSR_CHECK(dtype != PSSR_F32 && c >= 8 && c <= 8 * TPB && (c & (c - 1)) == 0 && ((y_cs | y_co | a_cs | a_co) & 7) == 0, PSSR_ERR_UNSUPPORTED,
+    PSSR_CHECK(takes_chan8(dtype, c, y_cs | y_co | a_cs | a_co), PSSR_ERR_UNSUPPORTED,
                "bn_relu_apply: 16-bit storage, power-of-two channel count >= 8, 16-byte aligned slices (c=%d)", c);
     CHECK_REF("bn_relu_apply y", y_cs, y_co, c); CHECK_REF("bn_relu_apply a", a_cs, a_co, c);
-    int lg = 0;
-    while ((8 << lg) < c) ++lg;
-    const long threads = (long)npix << lg;
-    const int grid = (int)((threads + TPB - 1) / TPB < 4096 ? (threads + TPB - 1) / TPB : 4096);
-    if (dtype == PSSR_BF16)
-        hipLaunchKernelGGL(bn_relu_apply8_kernel<bf16_t>, dim3(grid), dim3(TPB), 0, (hipStream_t)s, Ref{y, y_cs, y_co}, scale, shift, MRef{a, a_cs, a_co}, (long)npix, lg);
-    else
-        hipLaunchKernelGGL(bn_relu_apply8_kernel<f16_t>, dim3(grid), dim3(TPB), 0, (hipStream_t)s, Ref{y, y_cs, y_co}, scale, shift, MRef{a, a_cs, a_co}, (long)npix, lg);
+    const int lg = group_log2(c, 8);
+    DISPATCH_16(dtype, hipLaunchKernelGGL(bn_relu_apply8_kernel<T>, dim3(grid1d((long)npix << lg, 4096)), dim3(TPB), 0, (hipStream_t)s, Ref{y, y_cs, y_co}, scale, shift,
+                                          MRef{a, a_cs, a_co}, (long)npix, lg));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -983,7 +923,7 @@ int pssr_channel_sum_nhwc(const void* x, int cs, int co, int64_t npix, int c, do
 int pssr_nchw_to_nhwc(const float* in, void* out, int n, int c, int64_t hw, int out_cs, float scale, int dtype, pssr_stream_t s) {
     PSSR_CHECK(in && out && n > 0 && c > 0 && hw > 0 && out_cs >= c, PSSR_ERR_ARG, "nchw_to_nhwc: bad args");
     const long total = (long)n * hw * out_cs;
-    DISPATCH_T(dtype, hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, dim3(grid1d(total)), dim3(TPB), 0, (hipStream_t)s, in, (T*)out, n, c, (long)hw, out_cs, scale));
+    DISPATCH_T(dtype, hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, dim3(grid1d(total, 8192)), dim3(TPB), 0, (hipStream_t)s, in, (T*)out, n, c, (long)hw, out_cs, scale));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -1004,7 +944,7 @@ int pssr_copy_f32_batch(const pssr_copy_batch* items, int n_items, pssr_stream_t
 
 int pssr_clip_u8(const float* in, uint8_t* out, int64_t n, pssr_stream_t s) {
     PSSR_CHECK(in && out && n > 0, PSSR_ERR_ARG, "clip_u8: bad args");
-    hipLaunchKernelGGL(clip_u8_kernel, dim3(grid1d(n)), dim3(TPB), 0, (hipStream_t)s, in, out, (long)n);
+    hipLaunchKernelGGL(clip_u8_kernel, dim3(grid1d(n, 8192)), dim3(TPB), 0, (hipStream_t)s, in, out, (long)n);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }

@@ -1,0 +1,25 @@
+// NHWC tensor slices, their checks and the storage-type dispatch shared by the pointwise / per-channel kernel files.
+#pragma once
+#include "common.h"
+
+namespace {   // internal linkage, as the kernels that take these by value
+
+struct Ref { const void* p; int cs, co; };   // NHWC tensor slice: base, channel stride, channel offset
+struct MRef { void* p; int cs, co; };
+
+template <typename T> __device__ __forceinline__ const T* at(const Ref& r, long pix, int c) { return (const T*)r.p + pix * r.cs + r.co + c; }
+template <typename T> __device__ __forceinline__ T* at(const MRef& r, long pix, int c) { return (T*)r.p + pix * r.cs + r.co + c; }
+
+}  // namespace
+
+// runs CALL with T = the storage type of `dtype`
+#define DISPATCH_T(dtype, CALL)                                             \
+    do {                                                                    \
+        if ((dtype) == PSSR_BF16) { using T = bf16_t; CALL; }               \
+        else if ((dtype) == PSSR_F16) { using T = f16_t; CALL; }            \
+        else if ((dtype) == PSSR_F32) { using T = float; CALL; }            \
+        else { pssr_set_error("bad dtype %d", (dtype)); return PSSR_ERR_ARG; } \
+    } while (0)
+
+#define CHECK_REF(name, cs, co, c)                                                                               \
+    PSSR_CHECK((cs) % 4 == 0 && (co) % 4 == 0 && (co) + (c) <= (cs), PSSR_ERR_ARG, name ": bad channel stride/offset (%d,%d,%d)", cs, co, c)

@@ -5,20 +5,13 @@
 // All tensors are NHWC slices (pointer, channel stride, channel offset): the dense-concatenation of
 // RDNet (torch.cat of all previous features, _rdnet.py:132-138) is elided by writing every new
 // feature at its channel offset of one buffer per stage.
-#include "common.h"
+#include "nhwc.h"
 #include "tunables.h"
 #include <type_traits>
 
 namespace {
 
 constexpr int TPB = 256;
-
-struct Ref { const void* p; int cs, co; };
-struct MRef { void* p; int cs, co; };
-template <typename T> __device__ __forceinline__ const T* at(const Ref& r, long pix, int c) { return (const T*)r.p + pix * r.cs + r.co + c; }
-template <typename T> __device__ __forceinline__ T* at(const MRef& r, long pix, int c) { return (T*)r.p + pix * r.cs + r.co + c; }
-
-static inline int grid1d(long total, int cap = 8192) { long b = (total + TPB - 1) / TPB; return (int)(b < cap ? (b > 0 ? b : 1) : cap); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -928,16 +921,6 @@ __global__ __launch_bounds__(256) void ese_bwd_fused_kernel(const float* __restr
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL)                                             \
-    do {                                                                    \
-        if ((dtype) == PSSR_BF16) { using T = bf16_t; CALL; }               \
-        else if ((dtype) == PSSR_F16) { using T = f16_t; CALL; }            \
-        else if ((dtype) == PSSR_F32) { using T = float; CALL; }            \
-        else { pssr_set_error("bad dtype %d", (dtype)); return PSSR_ERR_ARG; } \
-    } while (0)
-#define CHECK_REF(name, cs, co, c)                                                                               \
-    PSSR_CHECK((cs) % 4 == 0 && (co) % 4 == 0 && (co) + (c) <= (cs), PSSR_ERR_ARG, name ": bad channel stride/offset (%d,%d,%d)", cs, co, c)
-
 extern "C" {
 
 int pssr_input_patchify(const float* x, void* xpatch, int n, int c, int h, int w, int ps, int pc, float pre_scale, float pre_shift,
@@ -945,7 +928,7 @@ int pssr_input_patchify(const float* x, void* xpatch, int n, int c, int h, int w
     PSSR_CHECK(x && xpatch && scale && shift && n > 0 && c > 0 && ps > 0 && h % ps == 0 && w % ps == 0 && pc >= c * ps * ps && pc % 16 == 0,
                PSSR_ERR_ARG, "input_patchify: bad args");
     const long total = (long)n * (h / ps) * (w / ps) * pc;
-    DISPATCH_T(dtype, hipLaunchKernelGGL(patchify_kernel<T>, dim3(grid1d(total)), dim3(TPB), 0, (hipStream_t)s, x, (T*)xpatch, n, c, h, w, ps, pc,
+    DISPATCH_T(dtype, hipLaunchKernelGGL(patchify_kernel<T>, dim3(grid1d(total, 8192)), dim3(TPB), 0, (hipStream_t)s, x, (T*)xpatch, n, c, h, w, ps, pc,
                                          pre_scale, pre_shift, scale, shift));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
@@ -1138,7 +1121,7 @@ int pssr_scale_nc(const void* t, int t_cs, int t_co, const float* gate, const fl
     PSSR_CHECK(t && gamma && out && n > 0 && hw > 0 && c > 0 && c % 4 == 0, PSSR_ERR_ARG, "scale_nc: bad args");
     CHECK_REF("scale_nc t", t_cs, t_co, c); CHECK_REF("scale_nc out", out_cs, out_co, c);
     const long npix = (long)n * hw;
-    DISPATCH_T(dtype, hipLaunchKernelGGL(scale_nc_kernel<T>, dim3(grid1d(npix * (c / 4))), dim3(TPB), 0, (hipStream_t)s, Ref{t, t_cs, t_co}, gate, gamma, add,
+    DISPATCH_T(dtype, hipLaunchKernelGGL(scale_nc_kernel<T>, dim3(grid1d(npix * (c / 4), 8192)), dim3(TPB), 0, (hipStream_t)s, Ref{t, t_cs, t_co}, gate, gamma, add,
                                          MRef{out, out_cs, out_co}, npix, hw, c));
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;

@@ -139,8 +139,6 @@ __global__ void __launch_bounds__(256) patch_stack_kernel(const uint8_t* __restr
     }
 }
 
-static inline int grid1d(long total) { long b = (total + 255) / 256; return (int)(b < 16384 ? (b > 0 ? b : 1) : 16384); }
-
 }  // namespace
 
 extern "C" {
@@ -149,7 +147,7 @@ int pssr_sliding_tiles_u8(const uint8_t* sheet, float* tiles, int c, int h, int 
     PSSR_CHECK(sheet && tiles && c > 0 && size > 0 && stride > 0 && h >= size && w >= size && ntile > 0 && tile0 >= 0, PSSR_ERR_ARG, "sliding_tiles: bad args");
     const int tiles_y = (h - size) / stride + 1, tiles_x = (w - size) / stride + 1;
     PSSR_CHECK(tile0 + ntile <= tiles_x * tiles_y, PSSR_ERR_ARG, "sliding_tiles: tile range %d+%d exceeds %d", tile0, ntile, tiles_x * tiles_y);
-    hipLaunchKernelGGL(sliding_tiles_kernel, dim3(grid1d((long)ntile * c * size * size)), dim3(256), 0, (hipStream_t)s, sheet, tiles, c, h, w, size,
+    hipLaunchKernelGGL(sliding_tiles_kernel, dim3(grid1d((long)ntile * c * size * size, 16384)), dim3(256), 0, (hipStream_t)s, sheet, tiles, c, h, w, size,
                        stride, tiles_x, tile0, ntile);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
@@ -161,7 +159,7 @@ int pssr_patch_tiles_u8(const uint8_t* tiles, uint8_t* sheet, int c, int n_rows,
                "patch_tiles: need 0 <= margin <= overlap < size (margin=%d overlap=%d size=%d)", margin, overlap, size);
     const int step = size - overlap;
     const long total = (long)c * (n_rows * step + overlap) * (n_cols * step + overlap);
-    hipLaunchKernelGGL(patch_tiles_kernel, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)s, tiles, sheet, c, n_rows, n_cols, size, overlap, margin);
+    hipLaunchKernelGGL(patch_tiles_kernel, dim3(grid1d(total, 16384)), dim3(256), 0, (hipStream_t)s, tiles, sheet, c, n_rows, n_cols, size, overlap, margin);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
