@@ -688,6 +688,24 @@ int pssr_stack_tiles_u8(const uint8_t* stack, float* tiles, int frames, int h, i
                         int tiles_y, int tiles_x, int tile0, int ntile, pssr_stream_t stream);
 int pssr_patch_stack_u8(const uint8_t* tiles, uint8_t* out, int n_slices, int c, int n_rows, int n_cols, int size, int overlap,
                         int margin, int out_h, int out_w, pssr_stream_t stream);
+/* predict_sheet's blend / ensemble path: the dihedral self-ensemble and weighted stitching, all in integers.
+ * Member d = 0 .. ensemble-1 (ensemble in {1, 2, 4, 8}) of a square plane a is T_d(a) = rot90(d & 4 ? a[..., ::-1] : a, d & 3) in numpy's
+ * terms, U_d its inverse.  Items are numbered g = tile * ensemble + d, tile slice-major as in pssr_stack_tiles_u8.
+ * pssr_dihedral_tiles_u8: tiles [nitem][m][size][size] f32 = items item0 .. item0 + nitem - 1: pssr_stack_tiles_u8's window of tile
+ *   g / ensemble (same reflection, same limits), every frame plane turned by T_(g % ensemble).  ensemble = 1 is pssr_stack_tiles_u8.
+ * pssr_clip_u8_dihedral: out [nitem][c][size][size] u8 = pssr_clip_u8's value of in (f32, same layout), plane (i, ch) stored through U_d with
+ *   d = (item0 + i) % ensemble: item0 selects the member phase only, both pointers are the batch's.  ensemble = 1 is pssr_clip_u8.
+ * pssr_blend_stack_u8: out [n_slices][c][out_h][out_w] u8 from tiles [n_slices*n_rows*n_cols*ensemble][c][size][size] u8 (item order).  With
+ *   T = max(overlap - 2 margin, 0) + 1 a tile that is first / last of its grid row or column weighs local coordinate l on that axis by
+ *     w1(l) = 0 if (!first && l < margin) || (!last && l >= size - margin), else min(T, first ? T : l - margin + 1, last ? T : size - margin - l)
+ *   (blend = 1, "linear"; blend = 0, "average": every non-zero w1 is 1), w(ly, lx) = w1_y(ly) * w1_x(lx), and
+ *     out = floor(sum_tiles w * sum_d tiles[..] / (ensemble * sum_tiles w)), 0 where no tile covers the pixel.
+ *   Integer arithmetic throughout, no atomics: the same bits on every run.  blend = 0, ensemble = 1 is pssr_patch_stack_u8. */
+int pssr_dihedral_tiles_u8(const uint8_t* stack, float* tiles, int frames, int h, int w, int m, int frame_step, int size, int stride,
+                           int tiles_y, int tiles_x, int ensemble, int item0, int nitem, pssr_stream_t stream);
+int pssr_clip_u8_dihedral(const float* in, uint8_t* out, int nitem, int c, int size, int ensemble, int item0, pssr_stream_t stream);
+int pssr_blend_stack_u8(const uint8_t* tiles, uint8_t* out, int n_slices, int c, int n_rows, int n_cols, int size, int overlap,
+                        int margin, int out_h, int out_w, int blend, int ensemble, pssr_stream_t stream);
 
 
 /* ---------------------------------------------------------------------------------------------

@@ -6,6 +6,8 @@
 // Both are pure index arithmetic + one integer divide per pixel, bit-exact.
 // The stack forms (predict_sheet's n_frames / slide / cover) number the tiles slice-major over all frame slices of a stack, read a grid
 // that leaves the sheet at the bottom / right through np.pad(mode="reflect")'s source index, and stitch every slice, cropped, in one launch.
+// The dihedral forms (predict_sheet's blend / ensemble) cut every tile in up to 8 rotations and flips, store the quantised predictions
+// turned back, and stitch them with feathered integer weights and the member average in one division.
 #include "common.h"
 
 namespace {
@@ -139,6 +141,137 @@ __global__ void __launch_bounds__(256) patch_stack_kernel(const uint8_t* __restr
     }
 }
 
+// ---- dihedral self-ensemble and weighted stitching (predict_sheet's blend / ensemble path; definitions: include/pssr_mi355.h)
+// Element (r, c) of T_d(a) is a[rev_r ? n-1-p : p][rev_c ? n-1-q : q] with (p, q) = tr ? (c, r) : (r, c); U_d = T_d^-1 has the same form.
+struct dihedral_map { int tr, rev_r, rev_c; };
+__device__ __forceinline__ dihedral_map dihedral(int d, bool inverse) {
+    const int rot = d & 3, tr = rot & 1, ry = rot >> 1, rx = (((rot + 1) >> 1) ^ (d >> 2)) & 1;
+    return tr && inverse ? dihedral_map{tr, rx, ry} : dihedral_map{tr, ry, rx};
+}
+
+// One 32 x 32 block at (r0, c0) of an n x n destination plane, dst(r, c) = fetch(source row, source column) under `mp`, by 256 threads.
+// Lanes run along destination rows when storing and along SOURCE rows when fetching: a transposing member goes through an LDS block of
+// 33-dword pitch (row writes and column reads both touch 32 different banks per 32-lane group), the others map row to row directly.
+template <typename T, typename F>
+__device__ __forceinline__ void dihedral_block(T* __restrict__ dst, int n, int r0, int c0, dihedral_map mp, float (*lds)[33], F fetch) {
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    if (!mp.tr) {
+#pragma unroll
+        for (int j = 0; j < 32; j += 8) {
+            const int r = r0 + ty + j, c = c0 + tx;
+            if (r < n && c < n) dst[(long)r * n + c] = (T)fetch(mp.rev_r ? n - 1 - r : r, mp.rev_c ? n - 1 - c : c);
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 32; j += 8) {
+        const int r = r0 + tx, c = c0 + ty + j;                   // lanes along r: along the source row
+        if (r < n && c < n) lds[ty + j][tx] = fetch(mp.rev_r ? n - 1 - c : c, mp.rev_c ? n - 1 - r : r);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 32; j += 8) {
+        const int r = r0 + ty + j, c = c0 + tx;
+        if (r < n && c < n) dst[(long)r * n + c] = (T)lds[tx][ty + j];
+    }
+    __syncthreads();
+}
+
+// stack_tiles_kernel's window of tile g / ensemble, turned by T_(g % ensemble): one item per blockIdx.y step, its m planes' 32 x 32 blocks
+// over blockIdx.x
+__global__ void __launch_bounds__(256) dihedral_tiles_kernel(const uint8_t* __restrict__ stack, float* __restrict__ out, int h, int w, int m,
+                                                             int frame_step, int size, int stride, int per_slice, int tiles_x, int ensemble,
+                                                             int item0, int nitem) {
+    __shared__ float lds[32][33];
+    const int nb = (size + 31) / 32, blocks = m * nb * nb;
+    for (int i = blockIdx.y; i < nitem; i += gridDim.y) {
+        const int g = item0 + i, tile = g / ensemble, k = tile / per_slice, t = tile % per_slice;
+        const dihedral_map mp = dihedral(g % ensemble, false);
+        const int y0 = (t / tiles_x) * stride, x0 = (t % tiles_x) * stride;
+        const uint8_t* slice = stack + (long)k * frame_step * h * w;
+        for (int b = blockIdx.x; b < blocks; b += gridDim.x) {
+            const int f = b / (nb * nb), br = b / nb % nb, bc = b % nb;
+            const uint8_t* plane = slice + (long)f * h * w;
+            dihedral_block(out + ((long)i * m + f) * size * size, size, br * 32, bc * 32, mp, lds, [&](int y, int x) {
+                int sy = y0 + y, sx = x0 + x;
+                if (sy >= h) sy = fold_reflect(sy, h);
+                if (sx >= w) sx = fold_reflect(sx, w);
+                return (float)plane[(long)sy * w + sx];
+            });
+        }
+    }
+}
+
+// clip_u8_kernel's value of plane p = item * c + channel, stored through U_d, d = (phase + item) % ensemble
+__global__ void __launch_bounds__(256) clip_u8_dihedral_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, long planes, int c, int size,
+                                                               int ensemble, int phase) {
+    __shared__ float lds[32][33];
+    const int nb = (size + 31) / 32;
+    for (long p = blockIdx.y; p < planes; p += gridDim.y) {
+        const dihedral_map mp = dihedral((int)((phase + p / c) % ensemble), true);
+        const float* src = in + p * size * size;
+        for (int b = blockIdx.x; b < nb * nb; b += gridDim.x)
+            dihedral_block(out + p * size * size, size, (b / nb) * 32, (b % nb) * 32, mp, lds,
+                           [&](int y, int x) { return fminf(fmaxf(src[(long)y * size + x], 0.f), 255.f); });   // the cast truncates toward zero
+    }
+}
+
+// weight of local coordinate l on one axis of a tile that is first / last of its grid row or column; t = max(overlap - 2 margin, 0) + 1
+__device__ __forceinline__ int blend_w1(int l, int size, int margin, int t, bool first, bool last, int blend) {
+    if ((!first && l < margin) || (!last && l >= size - margin)) return 0;
+    if (!blend) return 1;
+    int v = t;
+    if (!first && l - margin + 1 < v) v = l - margin + 1;
+    if (!last && size - margin - l < v) v = size - margin - l;
+    return v;
+}
+
+// patch_stack_kernel's gather with weights and ensemble members: one output row per blockIdx.y step (its covering tile rows and the sum
+// of their weights found once), threads along x.  Acc holds 255 * ensemble * (largest weight sum)^2: the host picks 32 or 64 bits.
+template <typename Acc>
+__global__ void __launch_bounds__(256) blend_stack_kernel(const uint8_t* __restrict__ tiles, uint8_t* __restrict__ out, long n_out_rows, int c,
+                                                          int n_rows, int n_cols, int size, int overlap, int margin, int out_h, int out_w,
+                                                          int blend, int ensemble) {
+    const int step = size - overlap;
+    const int per_slice = n_rows * n_cols;
+    const int t = (overlap > 2 * margin ? overlap - 2 * margin : 0) + 1;
+    const long plane = (long)size * size, member = plane * c;
+    for (long orow = blockIdx.y; orow < n_out_rows; orow += gridDim.y) {
+        const int y = (int)(orow % out_h);
+        const long sc = orow / out_h;                              // slice * c + channel
+        const int ch = (int)(sc % c);
+        const long first_tile = (sc / c) * per_slice;
+        const int r_lo = y >= size ? (y - size) / step + 1 : 0;
+        int r_hi = y / step; if (r_hi > n_rows - 1) r_hi = n_rows - 1;
+        Acc sum_wy = 0;
+        for (int r = r_lo; r <= r_hi; ++r) sum_wy += blend_w1(y - r * step, size, margin, t, r == 0, r == n_rows - 1, blend);
+        for (int x = blockIdx.x * 256 + threadIdx.x; x < out_w; x += gridDim.x * 256) {
+            const int c_lo = x >= size ? (x - size) / step + 1 : 0;
+            int c_hi = x / step; if (c_hi > n_cols - 1) c_hi = n_cols - 1;
+            Acc num = 0, sum_wx = 0;
+            for (int r = r_lo; r <= r_hi; ++r) {
+                const int ly = y - r * step;
+                const int wy = blend_w1(ly, size, margin, t, r == 0, r == n_rows - 1, blend);
+                if (!wy) continue;
+                Acc row = 0;
+                for (int q = c_lo; q <= c_hi; ++q) {
+                    const int lx = x - q * step;
+                    const int wx = blend_w1(lx, size, margin, t, q == 0, q == n_cols - 1, blend);
+                    if (!wx) continue;
+                    const uint8_t* px = tiles + (first_tile + r * n_cols + q) * ensemble * member + ch * plane + (long)ly * size + lx;
+                    unsigned members = 0;
+                    for (int d = 0; d < ensemble; ++d) members += px[d * member];
+                    row += (Acc)wx * members;
+                }
+                num += (Acc)wy * row;
+            }
+            for (int q = c_lo; q <= c_hi; ++q) sum_wx += blend_w1(x - q * step, size, margin, t, q == 0, q == n_cols - 1, blend);
+            const Acc den = (Acc)ensemble * sum_wy * sum_wx;
+            out[orow * out_w + x] = den ? (uint8_t)(num / den) : 0;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -164,30 +297,56 @@ int pssr_patch_tiles_u8(const uint8_t* tiles, uint8_t* sheet, int c, int n_rows,
     return PSSR_OK;
 }
 
-int pssr_stack_tiles_u8(const uint8_t* stack, float* tiles, int frames, int h, int w, int m, int frame_step, int size, int stride, int tiles_y,
-                        int tiles_x, int tile0, int ntile, pssr_stream_t s) {
-    PSSR_CHECK(stack && tiles, PSSR_ERR_ARG, "stack_tiles: null pointer");
+// the argument checks the two cutting entry points share; tiles tile0 .. tile0 + ntile - 1 of the slice-major order are touched
+static int check_stack_args(const char* who, const void* stack, const void* tiles, int frames, int h, int w, int m, int frame_step, int size, int stride,
+                            int tiles_y, int tiles_x, long tile0, long ntile) {
+    PSSR_CHECK(stack && tiles, PSSR_ERR_ARG, "%s: null pointer", who);
     PSSR_CHECK(frames > 0 && h > 0 && w > 0 && m > 0 && frame_step > 0 && size > 0 && stride > 0 && tiles_y > 0 && tiles_x > 0 && ntile > 0 && tile0 >= 0,
-               PSSR_ERR_ARG, "stack_tiles: sizes must be positive and tile0 >= 0 (frames=%d h=%d w=%d m=%d frame_step=%d size=%d stride=%d grid=%dx%d tile0=%d ntile=%d)",
-               frames, h, w, m, frame_step, size, stride, tiles_y, tiles_x, tile0, ntile);
-    const long per_slice = (long)tiles_y * tiles_x, last = (long)tile0 + ntile - 1;
+               PSSR_ERR_ARG, "%s: sizes must be positive and tile0 >= 0 (frames=%d h=%d w=%d m=%d frame_step=%d size=%d stride=%d grid=%dx%d tile0=%ld ntile=%ld)",
+               who, frames, h, w, m, frame_step, size, stride, tiles_y, tiles_x, tile0, ntile);
+    const long per_slice = (long)tiles_y * tiles_x, last = tile0 + ntile - 1;
     const long ext_h = (long)(tiles_y - 1) * stride + size, ext_w = (long)(tiles_x - 1) * stride + size;
     PSSR_CHECK(per_slice <= INT_MAX && last < INT_MAX && ext_h <= INT_MAX / 2 && ext_w <= INT_MAX / 2 && (long)m * size <= INT_MAX / 2,
-               PSSR_ERR_ARG, "stack_tiles: tile grid %dx%d, tile range %d+%d or extents exceed 32-bit indexing", tiles_y, tiles_x, tile0, ntile);
+               PSSR_ERR_ARG, "%s: tile grid %dx%d, tile range %ld+%ld or extents exceed 32-bit indexing", who, tiles_y, tiles_x, tile0, ntile);
     const long k_last = last / per_slice;
-    PSSR_CHECK(k_last * frame_step + m <= frames, PSSR_ERR_ARG, "stack_tiles: slice %ld (frames %ld..%ld) leaves the stack of %d frames", k_last,
+    PSSR_CHECK(k_last * frame_step + m <= frames, PSSR_ERR_ARG, "%s: slice %ld (frames %ld..%ld) leaves the stack of %d frames", who, k_last,
                k_last * frame_step, k_last * frame_step + m - 1, frames);
-    PSSR_CHECK(ext_h <= h || h >= 2, PSSR_ERR_ARG, "stack_tiles: the grid is %ld rows high but an axis of length %d cannot be reflected", ext_h, h);
-    PSSR_CHECK(ext_w <= w || w >= 2, PSSR_ERR_ARG, "stack_tiles: the grid is %ld columns wide but an axis of length %d cannot be reflected", ext_w, w);
+    PSSR_CHECK(ext_h <= h || h >= 2, PSSR_ERR_ARG, "%s: the grid is %ld rows high but an axis of length %d cannot be reflected", who, ext_h, h);
+    PSSR_CHECK(ext_w <= w || w >= 2, PSSR_ERR_ARG, "%s: the grid is %ld columns wide but an axis of length %d cannot be reflected", who, ext_w, w);
+    return PSSR_OK;
+}
+
+// ... and the two stitching entry points
+static int check_patch_args(const char* who, const void* tiles, const void* out, int n_slices, int c, int n_rows, int n_cols, int size, int overlap,
+                            int margin, int out_h, int out_w) {
+    PSSR_CHECK(tiles && out, PSSR_ERR_ARG, "%s: null pointer", who);
+    PSSR_CHECK(n_slices > 0 && c > 0 && n_rows > 0 && n_cols > 0 && size > 0, PSSR_ERR_ARG, "%s: bad args", who);
+    PSSR_CHECK(overlap >= 0 && overlap < size && margin >= 0 && margin <= overlap && 2 * margin < size, PSSR_ERR_ARG,
+               "%s: need 0 <= margin <= overlap < size (margin=%d overlap=%d size=%d)", who, margin, overlap, size);
+    const int step = size - overlap;
+    const long full_h = (long)n_rows * step + overlap, full_w = (long)n_cols * step + overlap;
+    PSSR_CHECK((long)n_rows * n_cols <= INT_MAX && full_h <= INT_MAX && full_w <= INT_MAX, PSSR_ERR_ARG, "%s: tile grid %dx%d exceeds 32-bit indexing",
+               who, n_rows, n_cols);
+    PSSR_CHECK(out_h >= 1 && out_h <= full_h && out_w >= 1 && out_w <= full_w, PSSR_ERR_ARG,
+               "%s: crop %dx%d must lie within the stitched sheet of %ldx%ld", who, out_h, out_w, full_h, full_w);
+    return PSSR_OK;
+}
+
+static bool ensemble_ok(int e) { return e == 1 || e == 2 || e == 4 || e == 8; }
+
+int pssr_stack_tiles_u8(const uint8_t* stack, float* tiles, int frames, int h, int w, int m, int frame_step, int size, int stride, int tiles_y,
+                        int tiles_x, int tile0, int ntile, pssr_stream_t s) {
+    if (const int e = check_stack_args("stack_tiles", stack, tiles, frames, h, w, m, frame_step, size, stride, tiles_y, tiles_x, tile0, ntile)) return e;
+    const int per_slice = tiles_y * tiles_x;
     const bool vec = size % 4 == 0 && (uintptr_t)tiles % 16 == 0;
     const int groups = vec ? size / 4 : size, gx = groups < 256 ? groups : 256, rows_per_pass = 256 / gx;
     const int bx = cdiv(m * size, rows_per_pass);
     const dim3 grid(bx < 1024 ? bx : 1024, ntile < 65535 ? ntile : 65535);
     if (vec)
-        hipLaunchKernelGGL(stack_tiles_kernel<4>, grid, dim3(256), 0, (hipStream_t)s, stack, tiles, h, w, m, frame_step, size, stride, (int)per_slice,
+        hipLaunchKernelGGL(stack_tiles_kernel<4>, grid, dim3(256), 0, (hipStream_t)s, stack, tiles, h, w, m, frame_step, size, stride, per_slice,
                            tiles_x, tile0, ntile);
     else
-        hipLaunchKernelGGL(stack_tiles_kernel<1>, grid, dim3(256), 0, (hipStream_t)s, stack, tiles, h, w, m, frame_step, size, stride, (int)per_slice,
+        hipLaunchKernelGGL(stack_tiles_kernel<1>, grid, dim3(256), 0, (hipStream_t)s, stack, tiles, h, w, m, frame_step, size, stride, per_slice,
                            tiles_x, tile0, ntile);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
@@ -195,20 +354,66 @@ int pssr_stack_tiles_u8(const uint8_t* stack, float* tiles, int frames, int h, i
 
 int pssr_patch_stack_u8(const uint8_t* tiles, uint8_t* out, int n_slices, int c, int n_rows, int n_cols, int size, int overlap, int margin, int out_h,
                         int out_w, pssr_stream_t s) {
-    PSSR_CHECK(tiles && out, PSSR_ERR_ARG, "patch_stack: null pointer");
-    PSSR_CHECK(n_slices > 0 && c > 0 && n_rows > 0 && n_cols > 0 && size > 0, PSSR_ERR_ARG, "patch_stack: bad args");
-    PSSR_CHECK(overlap >= 0 && overlap < size && margin >= 0 && margin <= overlap && 2 * margin < size, PSSR_ERR_ARG,
-               "patch_stack: need 0 <= margin <= overlap < size (margin=%d overlap=%d size=%d)", margin, overlap, size);
-    const int step = size - overlap;
-    const long full_h = (long)n_rows * step + overlap, full_w = (long)n_cols * step + overlap;
-    PSSR_CHECK((long)n_rows * n_cols <= INT_MAX && full_h <= INT_MAX && full_w <= INT_MAX, PSSR_ERR_ARG, "patch_stack: tile grid %dx%d exceeds 32-bit indexing",
-               n_rows, n_cols);
-    PSSR_CHECK(out_h >= 1 && out_h <= full_h && out_w >= 1 && out_w <= full_w, PSSR_ERR_ARG,
-               "patch_stack: crop %dx%d must lie within the stitched sheet of %ldx%ld", out_h, out_w, full_h, full_w);
+    if (const int e = check_patch_args("patch_stack", tiles, out, n_slices, c, n_rows, n_cols, size, overlap, margin, out_h, out_w)) return e;
     const long n_out_rows = (long)n_slices * c * out_h;
     const int bx = cdiv(out_w, 256);
     hipLaunchKernelGGL(patch_stack_kernel, dim3(bx < 1024 ? bx : 1024, (unsigned)(n_out_rows < 65535 ? n_out_rows : 65535)), dim3(256), 0, (hipStream_t)s, tiles,
                        out, n_out_rows, c, n_rows, n_cols, size, overlap, margin, out_h, out_w);
+    PSSR_LAUNCH_CHECK();
+    return PSSR_OK;
+}
+
+int pssr_dihedral_tiles_u8(const uint8_t* stack, float* tiles, int frames, int h, int w, int m, int frame_step, int size, int stride, int tiles_y,
+                           int tiles_x, int ensemble, int item0, int nitem, pssr_stream_t s) {
+    PSSR_CHECK(ensemble_ok(ensemble), PSSR_ERR_ARG, "dihedral_tiles: ensemble must be 1, 2, 4 or 8 (got %d)", ensemble);
+    PSSR_CHECK(item0 >= 0 && nitem > 0 && (long)item0 + nitem - 1 < INT_MAX, PSSR_ERR_ARG,
+               "dihedral_tiles: item range %d+%d must be non-empty, start at item0 >= 0 and stay within 32-bit indexing", item0, nitem);
+    const long tile0 = item0 / ensemble, tile_last = ((long)item0 + nitem - 1) / ensemble;
+    if (const int e = check_stack_args("dihedral_tiles", stack, tiles, frames, h, w, m, frame_step, size, stride, tiles_y, tiles_x, tile0,
+                                       tile_last - tile0 + 1))
+        return e;
+    const int nb = cdiv(size, 32);
+    const long blocks = (long)m * nb * nb;
+    PSSR_CHECK(blocks <= INT_MAX, PSSR_ERR_ARG, "dihedral_tiles: %d planes of %d pixels square exceed 32-bit indexing", m, size);
+    hipLaunchKernelGGL(dihedral_tiles_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024), nitem < 65535 ? nitem : 65535), dim3(256), 0, (hipStream_t)s,
+                       stack, tiles, h, w, m, frame_step, size, stride, tiles_y * tiles_x, tiles_x, ensemble, item0, nitem);
+    PSSR_LAUNCH_CHECK();
+    return PSSR_OK;
+}
+
+int pssr_clip_u8_dihedral(const float* in, uint8_t* out, int nitem, int c, int size, int ensemble, int item0, pssr_stream_t s) {
+    PSSR_CHECK(in && out, PSSR_ERR_ARG, "clip_u8_dihedral: null pointer");
+    PSSR_CHECK(ensemble_ok(ensemble), PSSR_ERR_ARG, "clip_u8_dihedral: ensemble must be 1, 2, 4 or 8 (got %d)", ensemble);
+    PSSR_CHECK(nitem > 0 && c > 0 && size > 0 && item0 >= 0 && size <= INT_MAX - 31, PSSR_ERR_ARG,
+               "clip_u8_dihedral: sizes must be positive and item0 >= 0 (nitem=%d c=%d size=%d item0=%d)", nitem, c, size, item0);
+    const long planes = (long)nitem * c, nb = cdiv(size, 32);
+    PSSR_CHECK(nb * nb <= INT_MAX, PSSR_ERR_ARG, "clip_u8_dihedral: planes of %d pixels square exceed 32-bit indexing", size);
+    hipLaunchKernelGGL(clip_u8_dihedral_kernel, dim3((unsigned)(nb * nb < 1024 ? nb * nb : 1024), (unsigned)(planes < 65535 ? planes : 65535)), dim3(256), 0,
+                       (hipStream_t)s, in, out, planes, c, size, ensemble, item0 % ensemble);
+    PSSR_LAUNCH_CHECK();
+    return PSSR_OK;
+}
+
+int pssr_blend_stack_u8(const uint8_t* tiles, uint8_t* out, int n_slices, int c, int n_rows, int n_cols, int size, int overlap, int margin, int out_h,
+                        int out_w, int blend, int ensemble, pssr_stream_t s) {
+    if (const int e = check_patch_args("blend_stack", tiles, out, n_slices, c, n_rows, n_cols, size, overlap, margin, out_h, out_w)) return e;
+    PSSR_CHECK(blend == 0 || blend == 1, PSSR_ERR_ARG, "blend_stack: blend must be 0 (average) or 1 (linear) (got %d)", blend);
+    PSSR_CHECK(ensemble_ok(ensemble), PSSR_ERR_ARG, "blend_stack: ensemble must be 1, 2, 4 or 8 (got %d)", ensemble);
+    // at most `over` tiles cover a pixel on an axis, each with a weight of at most t (1 for the average): the numerator is at most
+    // 255 * ensemble * (weight sum on y) * (weight sum on x)
+    const int step = size - overlap, over = cdiv(size, step), t = blend ? (overlap > 2 * margin ? overlap - 2 * margin : 0) + 1 : 1;
+    const unsigned __int128 sum_y = (unsigned __int128)(over < n_rows ? over : n_rows) * t, sum_x = (unsigned __int128)(over < n_cols ? over : n_cols) * t;
+    const unsigned __int128 bound = sum_y * sum_x * 255 * ensemble;
+    PSSR_CHECK(bound >> 64 == 0, PSSR_ERR_ARG, "blend_stack: the weighted sum of overlap=%d margin=%d size=%d may exceed 64 bits", overlap, margin, size);
+    const long n_out_rows = (long)n_slices * c * out_h;
+    const int bx = cdiv(out_w, 256);
+    const dim3 grid(bx < 1024 ? bx : 1024, (unsigned)(n_out_rows < 65535 ? n_out_rows : 65535));
+    if (bound >> 32 == 0)
+        hipLaunchKernelGGL(blend_stack_kernel<uint32_t>, grid, dim3(256), 0, (hipStream_t)s, tiles, out, n_out_rows, c, n_rows, n_cols, size, overlap, margin,
+                           out_h, out_w, blend, ensemble);
+    else
+        hipLaunchKernelGGL(blend_stack_kernel<uint64_t>, grid, dim3(256), 0, (hipStream_t)s, tiles, out, n_out_rows, c, n_rows, n_cols, size, overlap, margin,
+                           out_h, out_w, blend, ensemble);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }

@@ -563,6 +563,41 @@ def patch_stack_u8(tiles, n_slices, n_rows, n_cols, overlap, margin, out_h, out_
     return out
 
 
+BLENDS = {"average": 0, "linear": 1}        # predict_sheet's / reassemble_sheets' ``blend`` -> pssr_blend_stack_u8's
+ENSEMBLES = (1, 2, 4, 8)
+
+
+def dihedral_tiles_u8(stack, m, frame_step, size, stride, tiles_y, tiles_x, ensemble, item0, nitem):
+    """``stack_tiles_u8`` with the dihedral self-ensemble: float32 [nitem, m, size, size], items ``item0 ..`` of the sequence
+    ``tile * ensemble + d`` whose member ``d`` is the tile with every frame plane turned by ``T_d`` (include/pssr_mi355.h)."""
+    assert stack.dtype == torch.uint8 and stack.is_contiguous()
+    frames, h, w = stack.shape
+    out = torch.empty(nitem, m, size, size, dtype=torch.float32, device=stack.device)
+    L.check(L.lib().pssr_dihedral_tiles_u8(L.ptr(stack), L.ptr(out), frames, h, w, m, frame_step, size, stride, tiles_y, tiles_x, ensemble, item0, nitem,
+                                           L.stream_ptr()), "pssr_dihedral_tiles_u8")
+    return out
+
+
+def clip_u8_dihedral(x, out, ensemble, item0):
+    """``clip_u8`` of float32 [n, C, S, S] into uint8 ``out`` of that shape, item ``i`` turned back by ``U_d``, ``d = (item0 + i) % ensemble``."""
+    n, c, size, size_x = x.shape
+    assert size == size_x and x.dtype == torch.float32 and x.is_contiguous()
+    assert out.shape == x.shape and out.dtype == torch.uint8 and out.is_contiguous()
+    L.check(L.lib().pssr_clip_u8_dihedral(L.ptr(x), L.ptr(out), n, c, size, ensemble, item0, L.stream_ptr()), "pssr_clip_u8_dihedral")
+
+
+def blend_stack_u8(tiles, n_slices, n_rows, n_cols, overlap, margin, out_h, out_w, blend="average", ensemble=1):
+    """uint8 member predictions [n_slices*n_rows*n_cols*ensemble, C, S, S] (item order, all in the sheet's orientation) -> uint8
+    [n_slices, C, out_h, out_w]: the floored weighted mean over covering tiles and members (``blend``: a key of ``BLENDS``), cropped, in one
+    launch.  ``blend="average", ensemble=1`` is ``patch_stack_u8``."""
+    t, c, size, _ = tiles.shape
+    assert t == n_slices * n_rows * n_cols * ensemble and tiles.dtype == torch.uint8 and tiles.is_contiguous()
+    out = torch.empty(n_slices, c, max(out_h, 0), max(out_w, 0), dtype=torch.uint8, device=tiles.device)
+    L.check(L.lib().pssr_blend_stack_u8(L.ptr(tiles), L.ptr(out), n_slices, c, n_rows, n_cols, size, overlap, margin, out_h, out_w, BLENDS[blend], ensemble,
+                                        L.stream_ptr()), "pssr_blend_stack_u8")
+    return out
+
+
 def head_conv_bwd(g, g_scale, weight, act, dact, blk, dw, bias_sum, n, h, w, cin, cout, dtype, *, act_coff=0, dact_coff=0):
     """dgrad + wgrad (+ the bias sums of the pixel-shuffle conv in front) in one pass over the activation."""
     L.check(L.lib().pssr_head_conv_bwd(L.ptr(g), C.c_float(g_scale), L.ptr(weight), L.ptr(act), act.shape[-1], act_coff, L.ptr(dact), dact.shape[-1], dact_coff,

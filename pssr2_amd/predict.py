@@ -250,7 +250,8 @@ def _slice_plan(frames: int, n_frames, slide: bool):
 
 
 def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 32, margin: int = 0, batch_size: int = 128,
-                  device: str = "cuda", to_numpy: bool = True, *, n_frames=-1, slide: bool = False, cover: bool = False):
+                  device: str = "cuda", to_numpy: bool = True, *, n_frames=-1, slide: bool = False, cover: bool = False,
+                  blend: str = "average", ensemble: int = 1):
     r"""Whole-sheet prediction entirely on the device: what ``predict_images`` on a ``SlidingDataset`` in LR mode
     (pssr/data.py:132-266, pssr/predict.py:11-83) followed by ``reassemble_sheets`` (pssr/util.py:54-137) computes, without
     the per-tile host round trips.  ``sheet``: uint8 array or tensor [C, H, W] (or [H, W]) of the low-resolution image.
@@ -265,7 +266,22 @@ def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 3
 
     ``n_frames=m`` or ``[lr, hr]`` (with ``slide`` as in the sheet datasets) reads ``sheet`` as a stack [F, H, W] and runs the model on
     every frame slice ``[k * step, k * step + max(n_frames))``: returns uint8 [S, C_out, H', W'], slice ``k`` first.  The tiles of all
-    slices form one slice-major sequence cut into batches of ``batch_size`` (a batch may span slices), and one launch stitches them."""
+    slices form one slice-major sequence cut into batches of ``batch_size`` (a batch may span slices), and one launch stitches them.
+
+    ``blend="linear"`` feathers the overlaps (the reference has only the plain average, whose value jumps wherever the set of covering
+    tiles changes): on each axis a tile's weight ramps 1, 2, ... up to ``T = max(overlap * scale - 2 * margin, 0) + 1`` from every inner
+    edge (after ``margin`` trimming) and stays ``T`` inside and at the sheet's border; a pixel's weight is the product of the two axes, and
+    the result is the floored weighted mean, in integers.  ``ensemble=E`` (1, 2, 4 or 8) is the geometric self-ensemble: every tile is also
+    predicted rotated / flipped (member ``d``: ``np.rot90(a[..., ::-1] if d & 4 else a, d & 3)``), each prediction is turned back and the
+    ``E`` of them are averaged inside the same integer division.  It multiplies the model evaluations by ``E``; ``batch_size`` then counts
+    items (tile x member).  Every combination but ``blend="average", ensemble=1`` (which runs exactly the kernels it always ran) takes
+    ``pssr_dihedral_tiles_u8`` / ``pssr_clip_u8_dihedral`` / ``pssr_blend_stack_u8`` and keeps all member predictions in HBM until the one
+    stitching launch: ``n_tiles * E * C_out * (tile_res * scale) ** 2`` bytes, about 1 GB for ``ensemble=8`` on a 2048 x 2048 sheet at 4x
+    with the default tiles."""
+    if blend not in ops.BLENDS:
+        raise ValueError(f"blend must be one of {sorted(ops.BLENDS)}. Given {blend!r}.")
+    if ensemble not in ops.ENSEMBLES:
+        raise ValueError(f"ensemble must be one of {ops.ENSEMBLES}. Given {ensemble!r}.")
     if margin > overlap:
         raise ValueError(f"The value of margin cannot be greater than overlap. Given {margin} and {overlap} respectively.")
     sheet = torch.as_tensor(np.asarray(sheet) if not torch.is_tensor(sheet) else sheet)
@@ -279,31 +295,41 @@ def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 3
     n_rows, n_cols = _sheet_grid(h, w, tile_res, stride, cover)
     m, step, n_slices = _slice_plan(c, n_frames, slide)
     # the plain call keeps the kernels it has always used (pssr_sliding_tiles_u8 / pssr_patch_tiles_u8); stacks and covered sheets take
-    # the slice-major, reflecting pair (pssr_stack_tiles_u8 / pssr_patch_stack_u8)
+    # the slice-major, reflecting pair (pssr_stack_tiles_u8 / pssr_patch_stack_u8); a blend or an ensemble takes the dihedral, weighted
+    # form of that pair (pssr_dihedral_tiles_u8 / pssr_clip_u8_dihedral / pssr_blend_stack_u8), which subsumes both
     stacked = _get_n_frames(n_frames) is not None
-    plain = not cover and not stacked
-    n_tiles = n_slices * n_rows * n_cols
+    mixed = blend != "average" or ensemble != 1
+    plain = not cover and not stacked and not mixed
+    n_items = n_slices * n_rows * n_cols * ensemble
     model.to(device)
     model.eval()
     preds = None
     with torch.no_grad():
-        for t0 in range(0, n_tiles, batch_size):
-            nt = min(batch_size, n_tiles - t0)
+        for t0 in range(0, n_items, batch_size):
+            nt = min(batch_size, n_items - t0)
             if plain:
                 lr = ops.sliding_tiles_u8(sheet, tile_res, stride, t0, nt)
+            elif mixed:
+                lr = ops.dihedral_tiles_u8(sheet, m, step, tile_res, stride, n_rows, n_cols, ensemble, t0, nt)
             else:
                 lr = ops.stack_tiles_u8(sheet, m, step, tile_res, stride, n_rows, n_cols, t0, nt)
             y = model(lr).contiguous().float()
             if preds is None:
-                preds = torch.empty(n_tiles, *y.shape[1:], dtype=torch.uint8, device=y.device)
-            ops.clip_u8(y, preds[t0:t0 + nt])
+                preds = torch.empty(n_items, *y.shape[1:], dtype=torch.uint8, device=y.device)
+            if mixed:
+                ops.clip_u8_dihedral(y, preds[t0:t0 + nt], ensemble, t0)
+            else:
+                ops.clip_u8(y, preds[t0:t0 + nt])
     scale = preds.shape[-1] // tile_res
     # upstream passes overlap*lr_scale and the raw margin to _patch_images (pssr/util.py:99)
     if plain:
         out = ops.patch_tiles_u8(preds, n_rows, n_cols, overlap * scale, margin)
     else:
         out_h, out_w = ((h, w) if cover else (n_rows * stride + overlap, n_cols * stride + overlap))
-        out = ops.patch_stack_u8(preds, n_slices, n_rows, n_cols, overlap * scale, margin, out_h * scale, out_w * scale)
+        if mixed:
+            out = ops.blend_stack_u8(preds, n_slices, n_rows, n_cols, overlap * scale, margin, out_h * scale, out_w * scale, blend, ensemble)
+        else:
+            out = ops.patch_stack_u8(preds, n_slices, n_rows, n_cols, overlap * scale, margin, out_h * scale, out_w * scale)
         out = out if stacked else out[0]
     return out.cpu().numpy() if to_numpy else out
 

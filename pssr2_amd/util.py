@@ -289,16 +289,19 @@ def _sort_tiles(name: str):
     return int(parts[-2]), int(parts[-3])
 
 
-def reassemble_sheets(pred_path, lr_path, lr_scale: int, overlap: int = 0, margin: int = 0, out_dir: str = "sheets"):
+def reassemble_sheets(pred_path, lr_path, lr_scale: int, overlap: int = 0, margin: int = 0, out_dir: str = "sheets", *, blend: str = "average"):
     r"""Reassembles image sheets from the tiles predicted for a sliding dataset (pssr/util.py:54-108): same arguments, file naming
     and return value.  ``pred_path`` is a directory of tile images or the dict returned by ``predict_images``; the overlap-averaged
     stitching (with ``margin`` trimming) runs on the MI355X (``pssr_patch_tiles_u8``, bit-exact with ``_patch_images`` + the
-    uint8 cast).  Multi-frame sheets are written through Pillow (the reference uses tifffile)."""
+    uint8 cast).  Multi-frame sheets are written through Pillow (the reference uses tifffile).  ``blend="linear"`` (keyword-only, not in
+    the reference) feathers the overlaps as ``predict_sheet(blend="linear")`` does (``pssr_blend_stack_u8``, all slices in one launch)."""
     import glob
     import os
     import numpy as np
     from PIL import Image
     from . import ops
+    if blend not in ops.BLENDS:
+        raise ValueError(f"blend must be one of {sorted(ops.BLENDS)}. Given {blend!r}.")
     if margin > overlap:
         raise ValueError(f"The value of margin cannot be greater than overlap. Given {margin} and {overlap} respectively.")
     sheet_files = glob.glob(f"{lr_path}/*.tif", recursive=True)
@@ -330,8 +333,13 @@ def reassemble_sheets(pred_path, lr_path, lr_scale: int, overlap: int = 0, margi
         n_cols = (lr_shape[2] * lr_scale - batched.shape[2]) // (batched.shape[2] - overlap * lr_scale) + 1
         per = n_rows * n_cols
         tiles = torch.as_tensor(np.ascontiguousarray(batched.astype(np.uint8))).cuda()
-        image = np.stack([ops.patch_tiles_u8(tiles[i * per:(i + 1) * per, None].contiguous(), n_rows, n_cols, overlap * lr_scale, margin)[0].cpu().numpy()
-                          for i in range(batched.shape[0] // per)])
+        if blend == "average":
+            image = np.stack([ops.patch_tiles_u8(tiles[i * per:(i + 1) * per, None].contiguous(), n_rows, n_cols, overlap * lr_scale, margin)[0].cpu().numpy()
+                              for i in range(batched.shape[0] // per)])
+        else:
+            n_slices, step = batched.shape[0] // per, size - overlap * lr_scale
+            image = ops.blend_stack_u8(tiles[:n_slices * per, None].contiguous(), n_slices, n_rows, n_cols, overlap * lr_scale, margin,
+                                       n_rows * step + overlap * lr_scale, n_cols * step + overlap * lr_scale, blend)[:, 0].cpu().numpy()
         if out_dir:
             ims = [Image.fromarray(f) for f in image]
             ims[0].save(f"{out_dir}/{stem}.tif", save_all=len(ims) > 1, append_images=ims[1:])
