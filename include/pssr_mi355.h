@@ -706,6 +706,23 @@ int pssr_dihedral_tiles_u8(const uint8_t* stack, float* tiles, int frames, int h
 int pssr_clip_u8_dihedral(const float* in, uint8_t* out, int nitem, int c, int size, int ensemble, int item0, pssr_stream_t stream);
 int pssr_blend_stack_u8(const uint8_t* tiles, uint8_t* out, int n_slices, int c, int n_rows, int n_cols, int size, int overlap,
                         int margin, int out_h, int out_w, int blend, int ensemble, pssr_stream_t stream);
+/* The self-ensemble of a batch of square items (predict_images' / test_metrics' ensemble) and the per-pixel spread of the members, in integers.
+ * pssr_dihedral_batch_u8 / pssr_dihedral_batch_f32: out [n*ensemble][m][size][size] f32 from in [n][m][size][size] (u8 / f32, contiguous): item
+ *   i*ensemble + d = T_d(in[i]), every frame plane turned.  ensemble = 1 is a conversion / a copy.
+ * pssr_ensemble_reduce_u8: in [n*ensemble][c][size][size] f32 (that member order) -> mean, spread [n][c][size][size] u8.  With
+ *   q[i][d] = U_d(pssr_clip_u8's value of in[i*ensemble + d]) (clip to [0, 255], truncation, NaN gives 0):
+ *     mean[i] = floor(sum_d q[i][d] / ensemble),   spread[i] = max_d q[i][d] - min_d q[i][d].
+ *   spread may be null (not written).  mean is pssr_clip_u8_dihedral + pssr_blend_stack_u8 of a one-tile sheet without overlap, bit for bit;
+ *   ensemble = 1 is pssr_clip_u8 and a zero spread.  The members are never stored: 4*ensemble bytes read, 1 - 2 written per output pixel.
+ * pssr_spread_stack_u8: out [n_slices][c][out_h][out_w] u8 from pssr_blend_stack_u8's tiles: max - min of tiles[tile*ensemble + d] over every
+ *   member d and every tile that covers the pixel with w1_y * w1_x != 0 (the support is the same for both blends); 0 where no tile does.
+ *   Same argument checks as pssr_blend_stack_u8, the crop included.
+ * Integer sums, min and max in registers: no atomics, no floating-point accumulation, the same bits on every run. */
+int pssr_dihedral_batch_u8(const uint8_t* in, float* out, int n, int m, int size, int ensemble, pssr_stream_t stream);
+int pssr_dihedral_batch_f32(const float* in, float* out, int n, int m, int size, int ensemble, pssr_stream_t stream);
+int pssr_ensemble_reduce_u8(const float* in, uint8_t* mean, uint8_t* spread, int n, int c, int size, int ensemble, pssr_stream_t stream);
+int pssr_spread_stack_u8(const uint8_t* tiles, uint8_t* out, int n_slices, int c, int n_rows, int n_cols, int size, int overlap,
+                         int margin, int out_h, int out_w, int ensemble, pssr_stream_t stream);
 
 
 /* ---------------------------------------------------------------------------------------------

@@ -8,6 +8,8 @@
 // that leaves the sheet at the bottom / right through np.pad(mode="reflect")'s source index, and stitch every slice, cropped, in one launch.
 // The dihedral forms (predict_sheet's blend / ensemble) cut every tile in up to 8 rotations and flips, store the quantised predictions
 // turned back, and stitch them with feathered integer weights and the member average in one division.
+// The batch forms (predict_images' / test_metrics' ensemble) turn a batch of square items into its members and reduce the members' predictions
+// to their integer mean and spread without storing them; the spread of a stitched sheet is the stitch's gather with min / max (§7 (15)).
 #include "common.h"
 
 namespace {
@@ -152,29 +154,49 @@ __device__ __forceinline__ dihedral_map dihedral(int d, bool inverse) {
 // One 32 x 32 block at (r0, c0) of an n x n destination plane, dst(r, c) = fetch(source row, source column) under `mp`, by 256 threads.
 // Lanes run along destination rows when storing and along SOURCE rows when fetching: a transposing member goes through an LDS block of
 // 33-dword pitch (row writes and column reads both touch 32 different banks per 32-lane group), the others map row to row directly.
-template <typename T, typename F>
-__device__ __forceinline__ void dihedral_block(T* __restrict__ dst, int n, int r0, int c0, dihedral_map mp, float (*lds)[33], F fetch) {
+// The gather half leaves a thread the values of its four destination pixels (r0 + ty + 8 k, c0 + tx), k < 4 (0 outside the plane); the store
+// half writes them.  A kernel that reduces over members keeps the four in registers between the two (ensemble_reduce_kernel).
+template <typename F>
+__device__ __forceinline__ void dihedral_gather(float (&v)[4], int n, int r0, int c0, dihedral_map mp, float (*lds)[33], F fetch) {
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     if (!mp.tr) {
 #pragma unroll
-        for (int j = 0; j < 32; j += 8) {
-            const int r = r0 + ty + j, c = c0 + tx;
-            if (r < n && c < n) dst[(long)r * n + c] = (T)fetch(mp.rev_r ? n - 1 - r : r, mp.rev_c ? n - 1 - c : c);
+        for (int k = 0; k < 4; ++k) {
+            const int r = r0 + ty + 8 * k, c = c0 + tx;
+            v[k] = r < n && c < n ? fetch(mp.rev_r ? n - 1 - r : r, mp.rev_c ? n - 1 - c : c) : 0.f;
         }
         return;
     }
 #pragma unroll
-    for (int j = 0; j < 32; j += 8) {
-        const int r = r0 + tx, c = c0 + ty + j;                   // lanes along r: along the source row
-        if (r < n && c < n) lds[ty + j][tx] = fetch(mp.rev_r ? n - 1 - c : c, mp.rev_c ? n - 1 - r : r);
+    for (int k = 0; k < 4; ++k) {
+        const int r = r0 + tx, c = c0 + ty + 8 * k;               // lanes along r: along the source row
+        if (r < n && c < n) lds[ty + 8 * k][tx] = fetch(mp.rev_r ? n - 1 - c : c, mp.rev_c ? n - 1 - r : r);
     }
     __syncthreads();
 #pragma unroll
-    for (int j = 0; j < 32; j += 8) {
-        const int r = r0 + ty + j, c = c0 + tx;
-        if (r < n && c < n) dst[(long)r * n + c] = (T)lds[tx][ty + j];
+    for (int k = 0; k < 4; ++k) {
+        const int r = r0 + ty + 8 * k, c = c0 + tx;
+        v[k] = r < n && c < n ? lds[tx][ty + 8 * k] : 0.f;
     }
     __syncthreads();
+}
+
+template <typename T>
+__device__ __forceinline__ void dihedral_store(T* __restrict__ dst, int n, int r0, int c0, const T (&v)[4]) {
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int r = r0 + ty + 8 * k, c = c0 + tx;
+        if (r < n && c < n) dst[(long)r * n + c] = v[k];
+    }
+}
+
+template <typename T, typename F>
+__device__ __forceinline__ void dihedral_block(T* __restrict__ dst, int n, int r0, int c0, dihedral_map mp, float (*lds)[33], F fetch) {
+    float v[4];
+    dihedral_gather(v, n, r0, c0, mp, lds, fetch);
+    const T t[4] = {(T)v[0], (T)v[1], (T)v[2], (T)v[3]};
+    dihedral_store(dst, n, r0, c0, t);
 }
 
 // stack_tiles_kernel's window of tile g / ensemble, turned by T_(g % ensemble): one item per blockIdx.y step, its m planes' 32 x 32 blocks
@@ -268,6 +290,98 @@ __global__ void __launch_bounds__(256) blend_stack_kernel(const uint8_t* __restr
             for (int q = c_lo; q <= c_hi; ++q) sum_wx += blend_w1(x - q * step, size, margin, t, q == 0, q == n_cols - 1, blend);
             const Acc den = (Acc)ensemble * sum_wy * sum_wx;
             out[orow * out_w + x] = den ? (uint8_t)(num / den) : 0;
+        }
+    }
+}
+
+// ---- the self-ensemble of a batch of square items (predict_images' / test_metrics' ensemble; definitions: include/pssr_mi355.h)
+// Plane p = (i * ensemble + d) * m + f of the output is T_d of plane i * m + f of the input: one output plane per blockIdx.y step, its
+// 32 x 32 blocks over blockIdx.x
+template <typename In>
+__global__ void __launch_bounds__(256) dihedral_batch_kernel(const In* __restrict__ in, float* __restrict__ out, long planes, int m, int size,
+                                                             int ensemble) {
+    __shared__ float lds[32][33];
+    const int nb = (size + 31) / 32;
+    const long plane = (long)size * size;
+    for (long p = blockIdx.y; p < planes; p += gridDim.y) {
+        const long item = p / m;
+        const dihedral_map mp = dihedral((int)(item % ensemble), false);
+        const In* src = in + (item / ensemble * m + p % m) * plane;
+        for (int b = blockIdx.x; b < nb * nb; b += gridDim.x)
+            dihedral_block(out + p * plane, size, (b / nb) * 32, (b % nb) * 32, mp, lds, [&](int y, int x) { return (float)src[(long)y * size + x]; });
+    }
+}
+
+// Plane p = i * c + ch of mean / spread from planes (i * ensemble + d) * c + ch of the input, d < ensemble, each fetched through U_d with
+// clip_u8_kernel's value: a thread keeps the integer sum, minimum and maximum of its four pixels of the 32 x 32 output block over the
+// members and stores once (shift = log2 ensemble; spread may be null)
+__global__ void __launch_bounds__(256) ensemble_reduce_kernel(const float* __restrict__ in, uint8_t* __restrict__ mean, uint8_t* __restrict__ spread,
+                                                              long planes, int c, int size, int ensemble, int shift) {
+    __shared__ float lds[32][33];
+    const int nb = (size + 31) / 32;
+    const long plane = (long)size * size;
+    for (long p = blockIdx.y; p < planes; p += gridDim.y) {
+        const float* first = in + (p / c * ensemble * c + p % c) * plane;
+        for (int b = blockIdx.x; b < nb * nb; b += gridDim.x) {
+            const int r0 = (b / nb) * 32, c0 = (b % nb) * 32;
+            int sum[4] = {0, 0, 0, 0}, lo[4] = {255, 255, 255, 255}, hi[4] = {0, 0, 0, 0};
+            for (int d = 0; d < ensemble; ++d) {
+                const float* src = first + (long)d * c * plane;
+                float v[4];
+                dihedral_gather(v, size, r0, c0, dihedral(d, true), lds,
+                                [&](int y, int x) { return fminf(fmaxf(src[(long)y * size + x], 0.f), 255.f); });
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int q = (int)v[k];                        // the cast truncates toward zero
+                    sum[k] += q;
+                    lo[k] = q < lo[k] ? q : lo[k];
+                    hi[k] = q > hi[k] ? q : hi[k];
+                }
+            }
+            const uint8_t avg[4] = {(uint8_t)(sum[0] >> shift), (uint8_t)(sum[1] >> shift), (uint8_t)(sum[2] >> shift), (uint8_t)(sum[3] >> shift)};
+            dihedral_store(mean + p * plane, size, r0, c0, avg);
+            if (spread) {
+                const uint8_t dif[4] = {(uint8_t)(hi[0] - lo[0]), (uint8_t)(hi[1] - lo[1]), (uint8_t)(hi[2] - lo[2]), (uint8_t)(hi[3] - lo[3])};
+                dihedral_store(spread + p * plane, size, r0, c0, dif);
+            }
+        }
+    }
+}
+
+// blend_stack_kernel's gather with the minimum and the maximum in place of the weighted sum: over every member of every tile that covers the
+// pixel with a non-zero weight (blend_w1's support does not depend on the blend)
+__global__ void __launch_bounds__(256) spread_stack_kernel(const uint8_t* __restrict__ tiles, uint8_t* __restrict__ out, long n_out_rows, int c,
+                                                           int n_rows, int n_cols, int size, int overlap, int margin, int out_h, int out_w,
+                                                           int ensemble) {
+    const int step = size - overlap;
+    const int per_slice = n_rows * n_cols;
+    const long plane = (long)size * size, member = plane * c;
+    for (long orow = blockIdx.y; orow < n_out_rows; orow += gridDim.y) {
+        const int y = (int)(orow % out_h);
+        const long sc = orow / out_h;                              // slice * c + channel
+        const int ch = (int)(sc % c);
+        const long first_tile = (sc / c) * per_slice;
+        const int r_lo = y >= size ? (y - size) / step + 1 : 0;
+        int r_hi = y / step; if (r_hi > n_rows - 1) r_hi = n_rows - 1;
+        for (int x = blockIdx.x * 256 + threadIdx.x; x < out_w; x += gridDim.x * 256) {
+            const int c_lo = x >= size ? (x - size) / step + 1 : 0;
+            int c_hi = x / step; if (c_hi > n_cols - 1) c_hi = n_cols - 1;
+            int lo = 255, hi = 0;
+            for (int r = r_lo; r <= r_hi; ++r) {
+                const int ly = y - r * step;
+                if (!blend_w1(ly, size, margin, 1, r == 0, r == n_rows - 1, 0)) continue;
+                for (int q = c_lo; q <= c_hi; ++q) {
+                    const int lx = x - q * step;
+                    if (!blend_w1(lx, size, margin, 1, q == 0, q == n_cols - 1, 0)) continue;
+                    const uint8_t* px = tiles + (first_tile + r * n_cols + q) * ensemble * member + ch * plane + (long)ly * size + lx;
+                    for (int d = 0; d < ensemble; ++d) {
+                        const int v = px[d * member];
+                        lo = v < lo ? v : lo;
+                        hi = v > hi ? v : hi;
+                    }
+                }
+            }
+            out[orow * out_w + x] = hi >= lo ? (uint8_t)(hi - lo) : 0;
         }
     }
 }
@@ -414,6 +528,57 @@ int pssr_blend_stack_u8(const uint8_t* tiles, uint8_t* out, int n_slices, int c,
     else
         hipLaunchKernelGGL(blend_stack_kernel<uint64_t>, grid, dim3(256), 0, (hipStream_t)s, tiles, out, n_out_rows, c, n_rows, n_cols, size, overlap, margin,
                            out_h, out_w, blend, ensemble);
+    PSSR_LAUNCH_CHECK();
+    return PSSR_OK;
+}
+
+// the checks pssr_dihedral_batch_* and pssr_ensemble_reduce_u8 share: `items` square planes-of-`ch` times `ensemble` members
+static int check_ensemble_args(const char* who, bool pointers, int items, int ch, int size, int ensemble) {
+    PSSR_CHECK(pointers, PSSR_ERR_ARG, "%s: null pointer", who);
+    PSSR_CHECK(ensemble_ok(ensemble), PSSR_ERR_ARG, "%s: ensemble must be 1, 2, 4 or 8 (got %d)", who, ensemble);
+    PSSR_CHECK(items > 0 && ch > 0 && size > 0, PSSR_ERR_ARG, "%s: sizes must be positive (n=%d planes per item=%d size=%d)", who, items, ch, size);
+    const long nb = ((long)size + 31) / 32;
+    PSSR_CHECK((long)items * ensemble <= INT_MAX && size <= INT_MAX - 31 && nb * nb <= INT_MAX, PSSR_ERR_ARG,
+               "%s: %d items of %d members or planes of %d pixels square exceed 32-bit indexing", who, items, ensemble, size);
+    return PSSR_OK;
+}
+
+extern "C++" template <typename In>
+static int dihedral_batch(const char* who, const In* in, float* out, int n, int m, int size, int ensemble, pssr_stream_t s) {
+    if (const int e = check_ensemble_args(who, in && out, n, m, size, ensemble)) return e;
+    const long planes = (long)n * ensemble * m, nb = cdiv(size, 32);
+    hipLaunchKernelGGL(dihedral_batch_kernel<In>, dim3((unsigned)(nb * nb < 1024 ? nb * nb : 1024), (unsigned)(planes < 65535 ? planes : 65535)), dim3(256), 0,
+                       (hipStream_t)s, in, out, planes, m, size, ensemble);
+    PSSR_LAUNCH_CHECK();
+    return PSSR_OK;
+}
+
+int pssr_dihedral_batch_u8(const uint8_t* in, float* out, int n, int m, int size, int ensemble, pssr_stream_t s) {
+    return dihedral_batch("dihedral_batch_u8", in, out, n, m, size, ensemble, s);
+}
+
+int pssr_dihedral_batch_f32(const float* in, float* out, int n, int m, int size, int ensemble, pssr_stream_t s) {
+    return dihedral_batch("dihedral_batch_f32", in, out, n, m, size, ensemble, s);
+}
+
+int pssr_ensemble_reduce_u8(const float* in, uint8_t* mean, uint8_t* spread, int n, int c, int size, int ensemble, pssr_stream_t s) {
+    if (const int e = check_ensemble_args("ensemble_reduce", in && mean, n, c, size, ensemble)) return e;
+    const long planes = (long)n * c, nb = cdiv(size, 32);
+    const int shift = ensemble == 8 ? 3 : ensemble >> 1;
+    hipLaunchKernelGGL(ensemble_reduce_kernel, dim3((unsigned)(nb * nb < 1024 ? nb * nb : 1024), (unsigned)(planes < 65535 ? planes : 65535)), dim3(256), 0,
+                       (hipStream_t)s, in, mean, spread, planes, c, size, ensemble, shift);
+    PSSR_LAUNCH_CHECK();
+    return PSSR_OK;
+}
+
+int pssr_spread_stack_u8(const uint8_t* tiles, uint8_t* out, int n_slices, int c, int n_rows, int n_cols, int size, int overlap, int margin, int out_h,
+                         int out_w, int ensemble, pssr_stream_t s) {
+    if (const int e = check_patch_args("spread_stack", tiles, out, n_slices, c, n_rows, n_cols, size, overlap, margin, out_h, out_w)) return e;
+    PSSR_CHECK(ensemble_ok(ensemble), PSSR_ERR_ARG, "spread_stack: ensemble must be 1, 2, 4 or 8 (got %d)", ensemble);
+    const long n_out_rows = (long)n_slices * c * out_h;
+    const int bx = cdiv(out_w, 256);
+    hipLaunchKernelGGL(spread_stack_kernel, dim3(bx < 1024 ? bx : 1024, (unsigned)(n_out_rows < 65535 ? n_out_rows : 65535)), dim3(256), 0, (hipStream_t)s,
+                       tiles, out, n_out_rows, c, n_rows, n_cols, size, overlap, margin, out_h, out_w, ensemble);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }

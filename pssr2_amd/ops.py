@@ -598,6 +598,41 @@ def blend_stack_u8(tiles, n_slices, n_rows, n_cols, overlap, margin, out_h, out_
     return out
 
 
+def dihedral_batch(x, ensemble):
+    """uint8 or float32 [n, m, s, s] on the device -> float32 [n * ensemble, m, s, s]: item ``i * ensemble + d`` is ``x[i]`` with every frame
+    plane turned by ``T_d`` (include/pssr_mi355.h).  ``ensemble=1`` converts / copies."""
+    n, m, size, size_x = x.shape
+    assert size == size_x and x.dtype in (torch.uint8, torch.float32) and x.is_contiguous()
+    out = torch.empty(n * ensemble, m, size, size, dtype=torch.float32, device=x.device)
+    name = "pssr_dihedral_batch_u8" if x.dtype == torch.uint8 else "pssr_dihedral_batch_f32"
+    L.check(getattr(L.lib(), name)(L.ptr(x), L.ptr(out), n, m, size, ensemble, L.stream_ptr()), name)
+    return out
+
+
+def ensemble_reduce_u8(y, ensemble, spread=False):
+    """float32 member predictions [n * ensemble, C, S, S] (``dihedral_batch``'s order) -> uint8 [n, C, S, S]: the floored integer mean of the
+    members, each quantised as ``clip_u8`` and turned back by ``U_d``; with ``spread`` also their max - min: ``(mean, spread)``.  One launch;
+    the quantised members are never stored."""
+    items, c, size, size_x = y.shape
+    assert size == size_x and items % ensemble == 0 and y.dtype == torch.float32 and y.is_contiguous()
+    mean = torch.empty(items // ensemble, c, size, size, dtype=torch.uint8, device=y.device)
+    dif = torch.empty_like(mean) if spread else None
+    L.check(L.lib().pssr_ensemble_reduce_u8(L.ptr(y), L.ptr(mean), L.ptr(dif), items // ensemble, c, size, ensemble, L.stream_ptr()),
+            "pssr_ensemble_reduce_u8")
+    return (mean, dif) if spread else mean
+
+
+def spread_stack_u8(tiles, n_slices, n_rows, n_cols, overlap, margin, out_h, out_w, ensemble=1):
+    """``blend_stack_u8``'s member predictions -> uint8 [n_slices, C, out_h, out_w]: max - min over every member of every tile that covers
+    the pixel (the support of either blend), 0 where none does, cropped, in one launch."""
+    t, c, size, _ = tiles.shape
+    assert t == n_slices * n_rows * n_cols * ensemble and tiles.dtype == torch.uint8 and tiles.is_contiguous()
+    out = torch.empty(n_slices, c, max(out_h, 0), max(out_w, 0), dtype=torch.uint8, device=tiles.device)
+    L.check(L.lib().pssr_spread_stack_u8(L.ptr(tiles), L.ptr(out), n_slices, c, n_rows, n_cols, size, overlap, margin, out_h, out_w, ensemble,
+                                         L.stream_ptr()), "pssr_spread_stack_u8")
+    return out
+
+
 def head_conv_bwd(g, g_scale, weight, act, dact, blk, dw, bias_sum, n, h, w, cin, cout, dtype, *, act_coff=0, dact_coff=0):
     """dgrad + wgrad (+ the bias sums of the pixel-shuffle conv in front) in one pass over the activation."""
     L.check(L.lib().pssr_head_conv_bwd(L.ptr(g), C.c_float(g_scale), L.ptr(weight), L.ptr(act), act.shape[-1], act_coff, L.ptr(dact), dact.shape[-1], dact_coff,

@@ -42,10 +42,55 @@ def _pred_tensor(data: torch.Tensor, n_frames: int = 1):
     return _slice_center(out, n_frames)
 
 
+def _check_ensemble(ensemble, device, spread=False):
+    """The keyword checks of ``predict_images`` / ``test_metrics``, before model, dataset or device are touched."""
+    if ensemble not in ops.ENSEMBLES:
+        raise ValueError(f"ensemble must be one of {ops.ENSEMBLES}. Given {ensemble!r}.")
+    if spread and ensemble == 1:
+        raise ValueError("spread=True compares the members of a self-ensemble: with ensemble=1 there is nothing to compare.")
+    if ensemble > 1 and torch.device(device).type != "cuda":
+        raise RuntimeError("pssr2_amd.predict runs on an MI355X (HIP) device only; there is no CPU fallback")
+
+
+def _ensemble_pred(model: nn.Module, lr: torch.Tensor, ensemble: int, batch_size: int, spread: bool = False):
+    """The ensembled uint8 prediction of a device batch ``lr`` [n, m, s, s] (uint8 or float32): ``mean`` or ``(mean, spread)``, uint8
+    [n, C, S, S] in HBM (include/pssr_mi355.h: ``mean = floor(sum_d q_d / E)``, ``spread = max_d q_d - min_d q_d`` of the quantised members
+    turned back).  One ``pssr_dihedral_batch_*`` launch makes the ``n * E`` members, item ``i * E + d = T_d(lr[i])``; one
+    ``pssr_ensemble_reduce_u8`` launch reduces their float32 predictions.
+
+    Chunk rule: the members go through the model in sequence order in consecutive chunks of at most ``batch_size`` items,
+    ``[0, batch_size), [batch_size, 2 * batch_size), ...``, the last one shorter; a chunk may span images.  A model whose result depends
+    on the batch composition (any bf16 model here: the tiling follows the batch) is reproduced bit for bit only with the same chunks."""
+    if lr.dim() != 4 or lr.shape[-1] != lr.shape[-2]:
+        raise ValueError(f"ensemble > 1 rotates the items, which must be square [n, m, s, s]; got {tuple(lr.shape)}")
+    if not lr.is_cuda:
+        raise RuntimeError("pssr2_amd.predict runs on an MI355X (HIP) device only; there is no CPU fallback")
+    lr = lr.detach().contiguous()
+    members = ops.dihedral_batch(lr if lr.dtype == torch.uint8 else lr.float(), ensemble)
+    ys = None
+    for g0 in range(0, len(members), batch_size):
+        y = model(members[g0:g0 + batch_size])
+        if y.dim() != 4 or y.shape[-1] != y.shape[-2]:
+            raise ValueError(f"ensemble > 1 turns the predictions back, which must be square; the model returned {tuple(y.shape)}")
+        if ys is None:
+            ys = torch.empty(len(members), *y.shape[1:], dtype=torch.float32, device=y.device)
+        ys[g0:g0 + len(y)] = y
+    return ops.ensemble_reduce_u8(ys, ensemble, spread)
+
+
 def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batch_size=None, out_dir: str = "preds", norm: bool = False,
-                   prefix: str = None, dataloader_kwargs=None, callbacks=None):
+                   prefix: str = None, dataloader_kwargs=None, callbacks=None, *, ensemble: int = 1, spread: bool = False):
     r"""Predicts high-resolution images for ``dataset.val_idx``; returns ``{name: uint8 [C,H,W]}`` when
-    ``out_dir`` is None, else writes ``{out_dir}/{prefix_}{name}.tif`` through Pillow."""
+    ``out_dir`` is None, else writes ``{out_dir}/{prefix_}{name}.tif`` through Pillow.
+
+    ``ensemble=E`` (1, 2, 4 or 8; keyword-only, the reference has none) is ``predict_sheet``'s geometric self-ensemble for tiles: every item
+    is also predicted rotated / flipped, the quantised predictions are turned back and their floored integer mean is the prediction
+    (``_ensemble_pred``: two launches per batch beside the ``E`` times larger forward pass; ``batch_size`` also bounds the member chunks).
+    It takes the ordinary loop (no captured graph), needs square items and a square output, and multiplies the model evaluations by
+    ``E``.  ``spread=True`` also gives the per-pixel ``max - min`` of the members, where the network disagrees with itself: written as
+    ``{out_dir}/{prefix_}{name}_spread.tif``, or with ``out_dir=None`` returned as a second dict, ``(preds, spreads)``, with the same keys.
+    ``norm`` normalises the ensembled prediction (not the spread); the crop applies to both.  The defaults are the call without them."""
+    _check_ensemble(ensemble, device, spread)
     dataloader_kwargs = {} if dataloader_kwargs is None else dataloader_kwargs
     batch_size = 1 if batch_size is None else batch_size
     if norm and dataset.is_lr:
@@ -67,8 +112,8 @@ def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batc
     # device-made batches replayed as a hipGraph when the dataset offers them (pssr2_amd/fastpath.py); ``dataset.device_outputs``
     # (an extension of such datasets) keeps the uint8 predictions in HBM: the dict then holds device tensors
     from . import fastpath
-    fast = fastpath.supports(model, dataset, device) and not dataloader_kwargs and len(idx) > 0
-    host_fast = not fast and fastpath.supports_host(model, dataset, device) and len(idx) > 0
+    fast = ensemble == 1 and fastpath.supports(model, dataset, device) and not dataloader_kwargs and len(idx) > 0
+    host_fast = ensemble == 1 and not fast and fastpath.supports_host(model, dataset, device) and len(idx) > 0
     keep_dev = bool(getattr(dataset, "device_outputs", False)) and not out_dir and not norm
     compact = False
     if host_fast:
@@ -97,7 +142,7 @@ def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batc
         dataloader = range(evaler.begin(idx))
     else:
         dataloader = DataLoader(dataset, batch_size, sampler=idx, **dataloader_kwargs)
-    outs, cur_idx = {}, first
+    outs, spreads, cur_idx = {}, {}, first
     from .train import _restore_compact
     with torch.no_grad(), _restore_compact(dataset, host_fast and compact):
         for item in tqdm(dataloader, disable=rank != 0):
@@ -107,25 +152,38 @@ def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batc
             else:
                 lr = item if dataset.is_lr else item[1]
                 lr = lr.to(device)
-                hr_hat = _pred_array(model(lr))
+                if ensemble > 1:
+                    reduced = _ensemble_pred(model, lr, ensemble, batch_size, spread)
+                    hr_hat, dif = reduced if spread else (reduced, None)
+                    hr_hat = _slice_center(hr_hat.cpu().numpy(), 1)
+                else:
+                    hr_hat = _pred_array(model(lr))
             if norm:      # pssr/predict.py:63-64: intensities matched to the ground truth of the paired dataset
                 from .util import normalize_preds
                 _, hr_hat = normalize_preds(_pred_array(hr_dev if (fast or host_fast) else item[0].to(device)), hr_hat)
             crop_res = dataset.crop_res if not dataset.is_lr else dataset.crop_res * (hr_hat.shape[-1] // lr.shape[-1])
             hr_hat = hr_hat[:, :, :crop_res, :crop_res]
+            if spread:
+                dif = _slice_center(dif.cpu().numpy(), 1)[:, :, :crop_res, :crop_res]
             for batch_idx, image_idx in enumerate(range(cur_idx, min(cur_idx + batch_size, first + len(idx)))):
                 name = dataset._get_name(image_idx)
                 if out_dir:
                     from PIL import Image
                     frames = [Image.fromarray(f) for f in hr_hat[batch_idx]]
                     frames[0].save(f"{out_dir}/{prefix + '_' if prefix else ''}{name}.tif", save_all=len(frames) > 1, append_images=frames[1:])
+                    if spread:
+                        frames = [Image.fromarray(f) for f in dif[batch_idx]]
+                        frames[0].save(f"{out_dir}/{prefix + '_' if prefix else ''}{name}_spread.tif", save_all=len(frames) > 1,
+                                       append_images=frames[1:])
                 else:
                     outs[name] = hr_hat[batch_idx]
+                    if spread:
+                        spreads[name] = dif[batch_idx]
                 for i, callback in enumerate(callbacks):
                     callback(locals()) if callback_locals[i] else callback()
             cur_idx += batch_size
     if out_dir is None:
-        return outs
+        return (outs, spreads) if spread else outs
 
 
 def _center_crop_view(t: torch.Tensor, rows: int, cols: int):
@@ -251,7 +309,7 @@ def _slice_plan(frames: int, n_frames, slide: bool):
 
 def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 32, margin: int = 0, batch_size: int = 128,
                   device: str = "cuda", to_numpy: bool = True, *, n_frames=-1, slide: bool = False, cover: bool = False,
-                  blend: str = "average", ensemble: int = 1):
+                  blend: str = "average", ensemble: int = 1, spread: bool = False):
     r"""Whole-sheet prediction entirely on the device: what ``predict_images`` on a ``SlidingDataset`` in LR mode
     (pssr/data.py:132-266, pssr/predict.py:11-83) followed by ``reassemble_sheets`` (pssr/util.py:54-137) computes, without
     the per-tile host round trips.  ``sheet``: uint8 array or tensor [C, H, W] (or [H, W]) of the low-resolution image.
@@ -277,7 +335,12 @@ def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 3
     items (tile x member).  Every combination but ``blend="average", ensemble=1`` (which runs exactly the kernels it always ran) takes
     ``pssr_dihedral_tiles_u8`` / ``pssr_clip_u8_dihedral`` / ``pssr_blend_stack_u8`` and keeps all member predictions in HBM until the one
     stitching launch: ``n_tiles * E * C_out * (tile_res * scale) ** 2`` bytes, about 1 GB for ``ensemble=8`` on a 2048 x 2048 sheet at 4x
-    with the default tiles."""
+    with the default tiles.
+
+    ``spread=True`` returns ``(sheet, spread)``: next to the sheet, which it leaves as it is, a uint8 map of the same shape with the
+    ``max - min`` of all predictions of each pixel -- every member of every tile that covers it with a non-zero weight -- from one more
+    launch (``pssr_spread_stack_u8``) over the predictions the call already holds, on the plain, covered, stacked and blended paths alike.
+    With ``ensemble=1`` and an overlap it shows where neighbouring tiles disagree at the seams; without either it is zero."""
     if blend not in ops.BLENDS:
         raise ValueError(f"blend must be one of {sorted(ops.BLENDS)}. Given {blend!r}.")
     if ensemble not in ops.ENSEMBLES:
@@ -331,19 +394,28 @@ def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 3
         else:
             out = ops.patch_stack_u8(preds, n_slices, n_rows, n_cols, overlap * scale, margin, out_h * scale, out_w * scale)
         out = out if stacked else out[0]
+    if spread:
+        out_h, out_w = ((h, w) if cover else (n_rows * stride + overlap, n_cols * stride + overlap))
+        dif = ops.spread_stack_u8(preds, n_slices, n_rows, n_cols, overlap * scale, margin, out_h * scale, out_w * scale, ensemble)
+        dif = dif if stacked else dif[0]
+        return (out.cpu().numpy(), dif.cpu().numpy()) if to_numpy else (out, dif)
     return out.cpu().numpy() if to_numpy else out
 
 
 def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metrics=("mse", "pixel", "psnr", "ssim"), avg: bool = True,
-                 norm: bool = True, callbacks=None):
+                 norm: bool = True, callbacks=None, *, ensemble: int = 1):
     r"""Image restoration metrics of predicted vs ground truth images over ``dataset.val_idx`` (pssr/predict.py:144-211): same
     arguments and return value.  Prediction, uint8 cast, (``norm``) intensity normalisation and the per-image statistics all run on
     the MI355X (csrc/metrics.hip): the squared-difference sum is an exact integer and ``ssim`` is scikit-image's
     ``structural_similarity(data_range=255)`` (uniform 7x7 windows, sample covariance, interior mean) evaluated from exact integer
     window sums; only two doubles per image come back to the host.  Like the reference (pssr/predict.py:180) every iteration
-    evaluates ``dataset[0]``."""
+    evaluates ``dataset[0]``.
+
+    ``ensemble=E`` (keyword-only) scores ``predict_images(ensemble=E)``'s prediction: the ensembled uint8 image (``_ensemble_pred``, its
+    ``E`` members in one chunk) takes the place of the quantised model output, everything after it is the same."""
     import math
     from .util import pixel_metric
+    _check_ensemble(ensemble, device)
     callbacks, callback_locals = _get_callbacks(callbacks)
     image_range = 255
     metrics = [metrics] if type(metrics) is str else list(metrics)
@@ -355,8 +427,12 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
         for _ in tqdm(dataset.val_idx):
             hr, lr = dataset[0]
             hr, lr = hr.to(device).unsqueeze(0), lr.to(device).unsqueeze(0)
-            hr_hat = model(lr)
-            hr_dev, hat_dev = _pred_tensor(hr), _pred_tensor(hr_hat)
+            if ensemble > 1:
+                hr_hat = _ensemble_pred(model, lr, ensemble, ensemble)
+                hr_dev, hat_dev = _pred_tensor(hr), _slice_center(hr_hat, 1)
+            else:
+                hr_hat = model(lr)
+                hr_dev, hat_dev = _pred_tensor(hr), _pred_tensor(hr_hat)
             crop_res = dataset.crop_res if not dataset.is_lr else dataset.crop_res * (hr_hat.shape[-1] // lr.shape[-1])
             hr_dev, hat_dev = hr_dev[:, :, :crop_res, :crop_res].contiguous(), hat_dev[:, :, :crop_res, :crop_res].contiguous()
             if norm:
