@@ -754,6 +754,34 @@ int64_t pssr_image_metrics_workspace_bytes(int n_images, int h, int w);
 int pssr_image_metrics_u8(const uint8_t* hr, const uint8_t* hr_hat, double* out, int n_images, int h, int w, void* workspace,
                           pssr_stream_t stream);
 
+/* Consistency of a prediction with its own low-resolution input (pssr2_amd.util.consistency_map; csrc/consistency.hip): the
+ * resolution-scaled error of the super-resolution microscopy literature, for which no ground truth is needed.  Per plane pair
+ * Y [s*h][s*w] (the uint8 prediction) and L [h][w] (the uint8 LR input), s an integer in 1 .. 16, n = h w:
+ *   1. D = PIL.Image.resize(Y, (w, h), BILINEAR) bit for bit: pssr_bilinear_down_u8's two-pass 22-bit fixed-point resampler with the
+ *      uint8 rounding between the passes (one copy of the tap arithmetic: csrc/pil_taps.h).
+ *   2. Sd = sum D, Sl = sum L, Sdd = sum D^2, Sdl = sum D L, Sll = sum L^2: exact unsigned 64-bit integers over the plane.
+ *   3. (host, from the integers) num = n Sdl - Sd Sl, den = n Sdd - Sd^2, denl = n Sll - Sl^2; fit "affine": alpha = num / den,
+ *      beta = (Sl - alpha Sd) / n (den == 0: alpha = 0, beta = Sl / n); fit "identity": alpha = 1, beta = 0;
+ *      rsp = num / sqrt(den denl) if den > 0 and denl > 0 else 0, the Pearson correlation of D and L.
+ *   4. (host) P[v] = min(max(round_half_even(256 (alpha v + beta)), -65536), 131071), v = 0 .. 255, int32: the fitted expected LR
+ *      value in 1/256 grey levels.
+ *   5. e = |256 L - P[D]|; map = min(255, (e + 128) >> 8) u8 [h][w]; sse = sum e^2, an exact unsigned 64-bit integer (e < 2^18, so
+ *      up to 2^28 pixels per plane; larger planes are PSSR_ERR_ARG); rse = sqrt(sse / n) / 256 grey levels.
+ * pssr_reduce_moments_u8: steps 1 and 2 in one fused pass.  y [planes][s*h][s*w], l and d [planes][h][w], sums [planes][5] in the order
+ *   of step 2.  Every byte of y is read from HBM about once (plus a halo of s rows and columns per 32 x 32 outputs); the horizontally
+ *   reduced intermediate stays in LDS.  d equals pssr_bilinear_down_u8(y), bit for bit.
+ * pssr_consistency_map_u8: step 5.  d, l and map [planes][pixels], lut [planes][256] (step 4), sse [planes].
+ * Both validate before anything is launched (null pointers, planes, sizes, s outside 1 .. 16, an axis of y of 2^30 or more, more than
+ * 2^28 pixels per plane): PSSR_ERR_ARG.  Integer sums through per-workgroup 64-bit partials in the workspace and a second small launch:
+ * no atomics, no fence, no floating-point accumulation, the same bits on every run.  Workspaces of
+ * pssr_reduce_moments_workspace_bytes / pssr_consistency_map_workspace_bytes bytes (0 for arguments the entry point rejects). */
+int64_t pssr_reduce_moments_workspace_bytes(int planes, int h, int w, int s);
+int pssr_reduce_moments_u8(const uint8_t* y, const uint8_t* l, uint8_t* d, uint64_t* sums, int planes, int h, int w, int s,
+                           void* workspace, pssr_stream_t stream);
+int64_t pssr_consistency_map_workspace_bytes(int planes, int64_t pixels);
+int pssr_consistency_map_u8(const uint8_t* d, const uint8_t* l, const int32_t* lut, uint8_t* map, uint64_t* sse, int planes,
+                            int64_t pixels, void* workspace, pssr_stream_t stream);
+
 /* Several small f32 device-to-device copies in one launch (host struct passed by value to the kernel): the hand-written
  * backward pass moves side results (dbeta doubling as a bias gradient, centre taps, ...) into the flat gradient buffer the
  * all-reduce and AdamW read (the reference leaves this to autograd's .grad accumulation). */

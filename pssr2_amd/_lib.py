@@ -131,6 +131,13 @@ def lib():
         _lib.pssr_window_attn_workspace_bytes.argtypes = [c_int] * 5
         _lib.pssr_window_attn_fwd.argtypes = [c_void_p] * 4 + [c_int] * 7 + [c_float, c_int, c_void_p]
         _lib.pssr_window_attn_bwd.argtypes = [c_void_p] * 7 + [c_i64] + [c_int] * 7 + [c_float, c_int, c_void_p]
+        # consistency maps (csrc/consistency.hip)
+        _lib.pssr_reduce_moments_workspace_bytes.restype = c_i64
+        _lib.pssr_reduce_moments_workspace_bytes.argtypes = [c_int] * 4
+        _lib.pssr_reduce_moments_u8.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 2
+        _lib.pssr_consistency_map_workspace_bytes.restype = c_i64
+        _lib.pssr_consistency_map_workspace_bytes.argtypes = [c_int, c_i64]
+        _lib.pssr_consistency_map_u8.argtypes = [c_void_p] * 5 + [c_int, c_i64] + [c_void_p] * 2
         # one-pass backward of a flat-K source (csrc/pre_xcol_bwd.hip)
         _lib.pssr_flatk_bwd_pair_supported.argtypes = [c_int] * 3
         _lib.pssr_flatk_bwd_pair_parts.argtypes = [c_i64]

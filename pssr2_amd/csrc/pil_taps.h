@@ -1,0 +1,39 @@
+// Pillow's 8-bit-per-channel resampling taps (ImagingResample, BILINEAR), the one copy shared by the two-launch reduction of
+// crappify.hip (pssr_bilinear_down_u8) and the fused reduction + moments of consistency.hip (pssr_reduce_moments_u8).
+#pragma once
+#include "common.h"
+
+constexpr int PRECISION_BITS = 32 - 8 - 2;   // Pillow ImagingResample 8bpc fixed point
+
+// Pillow's precompute_coeffs + normalize_coeffs_8bpc for one output index (bilinear = triangle filter).
+// Evaluated in double in Pillow's operation order, so the integer taps are the ones Pillow uses.
+struct Taps { int xmin, n; int k[40]; };
+__device__ __forceinline__ void pil_taps(int xx, int in_size, int out_size, Taps& t) {
+    const double scale = (double)in_size / (double)out_size;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = 1.0 * filterscale;
+    const double center = (xx + 0.5) * scale;
+    const double ss = 1.0 / filterscale;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in_size) xmax = in_size;
+    const int n = xmax - xmin;
+    double w[40];
+    double ww = 0.0;
+    for (int x = 0; x < n && x < 40; ++x) {
+        double a = (x + xmin - center + 0.5) * ss;
+        if (a < 0.0) a = -a;
+        const double v = a < 1.0 ? 1.0 - a : 0.0;
+        w[x] = v; ww += v;
+    }
+    t.xmin = xmin; t.n = n < 40 ? n : 40;
+    for (int x = 0; x < t.n; ++x) {
+        const double v = ww != 0.0 ? w[x] / ww : w[x];
+        t.k[x] = v < 0 ? (int)(-0.5 + v * (1 << PRECISION_BITS)) : (int)(0.5 + v * (1 << PRECISION_BITS));
+    }
+}
+__device__ __forceinline__ uint8_t clip8(int v) {
+    v >>= PRECISION_BITS;
+    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}

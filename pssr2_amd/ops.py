@@ -1078,3 +1078,53 @@ def noise_profile_loss(pred_hist, pred_sum, target_hist, target_sum, per_image, 
     L.check(L.lib().pssr_noise_profile_loss(L.ptr(pred_hist), L.ptr(pred_sum), L.ptr(target_hist), L.ptr(target_sum), images, per_image, width,
                                             L.ptr(loss), L.ptr(parts), L.ptr(mean), L.stream_ptr()), "pssr_noise_profile_loss")
     return (loss, mean, parts) if terms else (loss, mean)
+
+
+# ----------------------------------------------------------------------------------------------
+# consistency of a prediction with its own LR input (csrc/consistency.hip; definitions in include/pssr_mi355.h)
+FITS = ("affine", "identity")        # consistency_map's ``fit``
+
+
+def reduce_moments_u8(y, l):
+    """uint8 device tensors ``y`` [..., s*h, s*w] (the prediction) and ``l`` [..., h, w] (the LR input), the same leading dimensions, ``s`` an
+    integer in 1 .. 16 -> ``(d, sums)``: ``d`` uint8 like ``l``, ``bilinear_down_u8(y, h, w)`` bit for bit, and ``sums`` int64 [planes, 5],
+    the exact ``sum d, sum l, sum d*d, sum d*l, sum l*l`` of each plane (all below 2**63).  One fused pass over ``y``."""
+    if y.dtype != torch.uint8 or l.dtype != torch.uint8 or not (y.is_cuda and l.is_cuda) or y.dim() < 2 or y.dim() != l.dim() \
+            or y.shape[:-2] != l.shape[:-2]:
+        raise ValueError("reduce_moments_u8 needs two uint8 device tensors [..., s*h, s*w] and [..., h, w] with the same leading dimensions")
+    (H, W), (h, w) = y.shape[-2:], l.shape[-2:]
+    s = H // h if h else 0
+    if h < 1 or w < 1 or not 1 <= s <= 16 or H != s * h or W != s * w:
+        raise ValueError(f"reduce_moments_u8: a {H}x{W} prediction is no integer multiple (1 .. 16) of the {h}x{w} LR image")
+    if h * w > 1 << 28:
+        raise ValueError(f"reduce_moments_u8: {h * w} pixels per reduced plane (at most 2**28)")
+    y, l = y.contiguous(), l.contiguous()
+    planes = l.numel() // (h * w)
+    lib = L.lib()
+    ws = torch.empty(lib.pssr_reduce_moments_workspace_bytes(planes, h, w, s), dtype=torch.uint8, device=y.device)
+    d = torch.empty_like(l)
+    sums = torch.empty(planes, 5, dtype=torch.int64, device=y.device)
+    L.check(lib.pssr_reduce_moments_u8(L.ptr(y), L.ptr(l), L.ptr(d), L.ptr(sums), planes, h, w, s, L.ptr(ws), L.stream_ptr()), "pssr_reduce_moments_u8")
+    return d, sums
+
+
+def consistency_map_u8(d, l, lut):
+    """uint8 device tensors ``d`` and ``l`` of the same shape [..., h, w] and the int32 device tables ``lut`` [planes, 256] (the fitted
+    expected LR value of every reduced value, in 1/256 grey levels) -> ``(map, sse)``: ``map`` uint8 like ``d``,
+    ``min(255, (|256 l - lut[d]| + 128) >> 8)``, and ``sse`` int64 [planes], the exact sum of ``|256 l - lut[d]|**2`` of each plane."""
+    if d.dtype != torch.uint8 or l.dtype != torch.uint8 or d.shape != l.shape or not (d.is_cuda and l.is_cuda) or d.dim() < 2:
+        raise ValueError("consistency_map_u8 needs two uint8 device tensors of the same shape [..., h, w]")
+    pixels = d.shape[-1] * d.shape[-2]
+    planes = d.numel() // pixels if pixels else 0
+    if pixels < 1 or planes < 1 or pixels > 1 << 28:
+        raise ValueError(f"consistency_map_u8: {planes} planes of {pixels} pixels (at least one, at most 2**28 pixels each)")
+    if lut.dtype != torch.int32 or not lut.is_cuda or tuple(lut.shape) != (planes, 256):
+        raise ValueError(f"consistency_map_u8 needs an int32 device table [{planes}, 256], one row per plane")
+    d, l, lut = d.contiguous(), l.contiguous(), lut.contiguous()
+    lib = L.lib()
+    ws = torch.empty(lib.pssr_consistency_map_workspace_bytes(planes, pixels), dtype=torch.uint8, device=d.device)
+    out = torch.empty_like(d)
+    sse = torch.empty(planes, dtype=torch.int64, device=d.device)
+    L.check(lib.pssr_consistency_map_u8(L.ptr(d), L.ptr(l), L.ptr(lut), L.ptr(out), L.ptr(sse), planes, pixels, L.ptr(ws), L.stream_ptr()),
+            "pssr_consistency_map_u8")
+    return out, sse

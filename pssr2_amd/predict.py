@@ -78,8 +78,34 @@ def _ensemble_pred(model: nn.Module, lr: torch.Tensor, ensemble: int, batch_size
     return ops.ensemble_reduce_u8(ys, ensemble, spread)
 
 
+def _check_consistency(consistency, fit, device):
+    """The ``consistency`` / ``fit`` keyword checks of the drivers, before model, dataset or device are touched."""
+    if fit not in ops.FITS:
+        raise ValueError(f"fit must be one of {ops.FITS}. Given {fit!r}.")
+    if consistency and torch.device(device).type != "cuda":
+        raise RuntimeError("pssr2_amd.predict runs on an MI355X (HIP) device only; there is no CPU fallback")
+
+
+def _score_items(lr: torch.Tensor, hat: torch.Tensor, crop_res: int, scale: int, fit: str):
+    """``util.consistency_map`` of a device batch for ``predict_images`` / ``test_metrics``: the cropped uint8 predictions ``hat``
+    [n, C, H', W'] (not normalised, in HBM) against their LR items ``lr`` [n, m, h, w] cut to ``crop_res // scale`` as the predictions were
+    cut to ``crop_res`` (``scale``: the model's).  A float item is quantised as a prediction is (``ops.clip_u8``); the datasets hand out
+    integers, for which that is the identity."""
+    from .util import consistency_map
+    if scale < 1 or crop_res % scale:
+        raise ValueError(f"consistency=True compares the cropped prediction with the LR item cut to crop_res // scale: the crop ({crop_res}) "
+                         f"must be a multiple of the model's scale ({scale}).")
+    if lr.dtype != torch.uint8:
+        x = lr.detach().contiguous().float()
+        lr = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+        ops.clip_u8(x, lr)
+    cut = crop_res // scale
+    return consistency_map(lr[:, :, :cut, :cut].contiguous(), hat.contiguous(), fit=fit)
+
+
 def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batch_size=None, out_dir: str = "preds", norm: bool = False,
-                   prefix: str = None, dataloader_kwargs=None, callbacks=None, *, ensemble: int = 1, spread: bool = False):
+                   prefix: str = None, dataloader_kwargs=None, callbacks=None, *, ensemble: int = 1, spread: bool = False,
+                   consistency: bool = False, fit: str = "affine"):
     r"""Predicts high-resolution images for ``dataset.val_idx``; returns ``{name: uint8 [C,H,W]}`` when
     ``out_dir`` is None, else writes ``{out_dir}/{prefix_}{name}.tif`` through Pillow.
 
@@ -89,8 +115,16 @@ def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batc
     It takes the ordinary loop (no captured graph), needs square items and a square output, and multiplies the model evaluations by
     ``E``.  ``spread=True`` also gives the per-pixel ``max - min`` of the members, where the network disagrees with itself: written as
     ``{out_dir}/{prefix_}{name}_spread.tif``, or with ``out_dir=None`` returned as a second dict, ``(preds, spreads)``, with the same keys.
-    ``norm`` normalises the ensembled prediction (not the spread); the crop applies to both.  The defaults are the call without them."""
+    ``norm`` normalises the ensembled prediction (not the spread); the crop applies to both.  The defaults are the call without them.
+
+    ``consistency=True`` (keyword-only; ``fit`` as ``util.consistency_map``) scores every prediction against its own LR item, for which no
+    ground truth is needed: the (ensembled) uint8 prediction, cropped but before ``norm``, against the item cut to ``crop // scale`` (a
+    crop that the model's scale does not divide is a ``ValueError``).  It takes the ordinary loop as ``ensemble > 1`` does and adds
+    ``consistency_map``'s few small launches and its two copies to the host per batch.  The maps are written as ``{out_dir}/{prefix_}{name}_consistency.tif``; with ``out_dir=None`` a dict
+    ``name -> Consistency`` (``map`` uint8 [C, h, w] for the [C, H, W] handed out, ``alpha, beta, rse, rsp`` float64 [C]) is appended to the
+    returned tuple, after ``spreads`` when both are asked for."""
     _check_ensemble(ensemble, device, spread)
+    _check_consistency(consistency, fit, device)
     dataloader_kwargs = {} if dataloader_kwargs is None else dataloader_kwargs
     batch_size = 1 if batch_size is None else batch_size
     if norm and dataset.is_lr:
@@ -112,8 +146,8 @@ def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batc
     # device-made batches replayed as a hipGraph when the dataset offers them (pssr2_amd/fastpath.py); ``dataset.device_outputs``
     # (an extension of such datasets) keeps the uint8 predictions in HBM: the dict then holds device tensors
     from . import fastpath
-    fast = ensemble == 1 and fastpath.supports(model, dataset, device) and not dataloader_kwargs and len(idx) > 0
-    host_fast = ensemble == 1 and not fast and fastpath.supports_host(model, dataset, device) and len(idx) > 0
+    fast = ensemble == 1 and not consistency and fastpath.supports(model, dataset, device) and not dataloader_kwargs and len(idx) > 0
+    host_fast = ensemble == 1 and not consistency and not fast and fastpath.supports_host(model, dataset, device) and len(idx) > 0
     keep_dev = bool(getattr(dataset, "device_outputs", False)) and not out_dir and not norm
     compact = False
     if host_fast:
@@ -142,8 +176,9 @@ def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batc
         dataloader = range(evaler.begin(idx))
     else:
         dataloader = DataLoader(dataset, batch_size, sampler=idx, **dataloader_kwargs)
-    outs, spreads, cur_idx = {}, {}, first
+    outs, spreads, scores, cur_idx = {}, {}, {}, first
     from .train import _restore_compact
+    from .util import Consistency
     with torch.no_grad(), _restore_compact(dataset, host_fast and compact):
         for item in tqdm(dataloader, disable=rank != 0):
             if fast or host_fast:
@@ -155,13 +190,19 @@ def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batc
                 if ensemble > 1:
                     reduced = _ensemble_pred(model, lr, ensemble, batch_size, spread)
                     hr_hat, dif = reduced if spread else (reduced, None)
+                    hat_dev = _slice_center(hr_hat, 1) if consistency else None
                     hr_hat = _slice_center(hr_hat.cpu().numpy(), 1)
+                elif consistency:
+                    hat_dev = _pred_tensor(model(lr))
+                    hr_hat = hat_dev.cpu().numpy()
                 else:
                     hr_hat = _pred_array(model(lr))
             if norm:      # pssr/predict.py:63-64: intensities matched to the ground truth of the paired dataset
                 from .util import normalize_preds
                 _, hr_hat = normalize_preds(_pred_array(hr_dev if (fast or host_fast) else item[0].to(device)), hr_hat)
             crop_res = dataset.crop_res if not dataset.is_lr else dataset.crop_res * (hr_hat.shape[-1] // lr.shape[-1])
+            if consistency:       # the prediction as it is handed out, but before norm
+                cons = _score_items(lr, hat_dev[:, :, :crop_res, :crop_res], crop_res, hat_dev.shape[-1] // lr.shape[-1], fit)
             hr_hat = hr_hat[:, :, :crop_res, :crop_res]
             if spread:
                 dif = _slice_center(dif.cpu().numpy(), 1)[:, :, :crop_res, :crop_res]
@@ -175,14 +216,22 @@ def predict_images(model: nn.Module, dataset: Dataset, device: str = "cpu", batc
                         frames = [Image.fromarray(f) for f in dif[batch_idx]]
                         frames[0].save(f"{out_dir}/{prefix + '_' if prefix else ''}{name}_spread.tif", save_all=len(frames) > 1,
                                        append_images=frames[1:])
+                    if consistency:
+                        frames = [Image.fromarray(f) for f in cons.map[batch_idx]]
+                        frames[0].save(f"{out_dir}/{prefix + '_' if prefix else ''}{name}_consistency.tif", save_all=len(frames) > 1,
+                                       append_images=frames[1:])
                 else:
                     outs[name] = hr_hat[batch_idx]
                     if spread:
                         spreads[name] = dif[batch_idx]
+                    if consistency:
+                        scores[name] = Consistency(*(v[batch_idx] for v in cons))
                 for i, callback in enumerate(callbacks):
                     callback(locals()) if callback_locals[i] else callback()
             cur_idx += batch_size
     if out_dir is None:
+        if consistency:
+            return (outs, spreads, scores) if spread else (outs, scores)
         return (outs, spreads) if spread else outs
 
 
@@ -309,7 +358,7 @@ def _slice_plan(frames: int, n_frames, slide: bool):
 
 def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 32, margin: int = 0, batch_size: int = 128,
                   device: str = "cuda", to_numpy: bool = True, *, n_frames=-1, slide: bool = False, cover: bool = False,
-                  blend: str = "average", ensemble: int = 1, spread: bool = False):
+                  blend: str = "average", ensemble: int = 1, spread: bool = False, consistency: bool = False, fit: str = "affine"):
     r"""Whole-sheet prediction entirely on the device: what ``predict_images`` on a ``SlidingDataset`` in LR mode
     (pssr/data.py:132-266, pssr/predict.py:11-83) followed by ``reassemble_sheets`` (pssr/util.py:54-137) computes, without
     the per-tile host round trips.  ``sheet``: uint8 array or tensor [C, H, W] (or [H, W]) of the low-resolution image.
@@ -340,7 +389,16 @@ def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 3
     ``spread=True`` returns ``(sheet, spread)``: next to the sheet, which it leaves as it is, a uint8 map of the same shape with the
     ``max - min`` of all predictions of each pixel -- every member of every tile that covers it with a non-zero weight -- from one more
     launch (``pssr_spread_stack_u8``) over the predictions the call already holds, on the plain, covered, stacked and blended paths alike.
-    With ``ensemble=1`` and an overlap it shows where neighbouring tiles disagree at the seams; without either it is zero."""
+    With ``ensemble=1`` and an overlap it shows where neighbouring tiles disagree at the seams; without either it is zero.
+
+    ``consistency=True`` also scores the returned sheet against the low-resolution region it covers, ``sheet[..., :H' // scale, :W' // scale]``
+    of each slice's frames (``util.consistency_map`` with ``fit``; no ground truth is needed, and unlike the spread it sees a structure that
+    every member invents alike): after whichever stitch ran, one fused reduction + moments launch and one map launch over what the call
+    already holds in HBM, one fit per output plane of the whole sheet.  Returns ``(sheet, cons)``, or ``(sheet, spread, cons)`` with
+    ``spread=True``; ``cons`` is a ``Consistency`` with ``map`` uint8 [C_out, h', w'] and ``alpha, beta, rse, rsp`` float64 [C_out] ([S, ...]
+    for stacks).  A model with more output planes than the slice has frames is a ``ValueError``."""
+    if fit not in ops.FITS:
+        raise ValueError(f"fit must be one of {ops.FITS}. Given {fit!r}.")
     if blend not in ops.BLENDS:
         raise ValueError(f"blend must be one of {sorted(ops.BLENDS)}. Given {blend!r}.")
     if ensemble not in ops.ENSEMBLES:
@@ -394,16 +452,26 @@ def predict_sheet(model: nn.Module, sheet, tile_res: int = 128, overlap: int = 3
         else:
             out = ops.patch_stack_u8(preds, n_slices, n_rows, n_cols, overlap * scale, margin, out_h * scale, out_w * scale)
         out = out if stacked else out[0]
+    extra = ()
+    if consistency:
+        from .util import Consistency, consistency_map
+        hat = out if stacked else out[None]
+        lh, lw = hat.shape[-2] // scale, hat.shape[-1] // scale
+        lr = torch.stack([sheet[k * step:k * step + m, :lh, :lw] for k in range(n_slices)])
+        cons = consistency_map(lr, hat, fit=fit, to_numpy=to_numpy)
+        extra = (cons if stacked else Consistency(*(v[0] for v in cons)),)
     if spread:
         out_h, out_w = ((h, w) if cover else (n_rows * stride + overlap, n_cols * stride + overlap))
         dif = ops.spread_stack_u8(preds, n_slices, n_rows, n_cols, overlap * scale, margin, out_h * scale, out_w * scale, ensemble)
         dif = dif if stacked else dif[0]
-        return (out.cpu().numpy(), dif.cpu().numpy()) if to_numpy else (out, dif)
+        return ((out.cpu().numpy(), dif.cpu().numpy()) if to_numpy else (out, dif)) + extra
+    if consistency:
+        return (out.cpu().numpy() if to_numpy else out,) + extra
     return out.cpu().numpy() if to_numpy else out
 
 
 def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metrics=("mse", "pixel", "psnr", "ssim"), avg: bool = True,
-                 norm: bool = True, callbacks=None, *, ensemble: int = 1):
+                 norm: bool = True, callbacks=None, *, ensemble: int = 1, fit: str = "affine"):
     r"""Image restoration metrics of predicted vs ground truth images over ``dataset.val_idx`` (pssr/predict.py:144-211): same
     arguments and return value.  Prediction, uint8 cast, (``norm``) intensity normalisation and the per-image statistics all run on
     the MI355X (csrc/metrics.hip): the squared-difference sum is an exact integer and ``ssim`` is scikit-image's
@@ -412,10 +480,15 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
     evaluates ``dataset[0]``.
 
     ``ensemble=E`` (keyword-only) scores ``predict_images(ensemble=E)``'s prediction: the ensembled uint8 image (``_ensemble_pred``, its
-    ``E`` members in one chunk) takes the place of the quantised model output, everything after it is the same."""
+    ``E`` members in one chunk) takes the place of the quantised model output, everything after it is the same.
+
+    ``metrics`` may also name ``"rse"`` and ``"rsp"`` (not in the default tuple): the two summary numbers of ``util.consistency_map``
+    (with ``fit``) of the cropped prediction, before ``norm``, against the item's own LR side -- the resolution-scaled error in grey
+    levels and the Pearson correlation, which need no ground truth -- per image the mean over its planes."""
     import math
     from .util import pixel_metric
     _check_ensemble(ensemble, device)
+    _check_consistency(False, fit, device)
     callbacks, callback_locals = _get_callbacks(callbacks)
     image_range = 255
     metrics = [metrics] if type(metrics) is str else list(metrics)
@@ -435,6 +508,11 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
                 hr_dev, hat_dev = _pred_tensor(hr), _pred_tensor(hr_hat)
             crop_res = dataset.crop_res if not dataset.is_lr else dataset.crop_res * (hr_hat.shape[-1] // lr.shape[-1])
             hr_dev, hat_dev = hr_dev[:, :, :crop_res, :crop_res].contiguous(), hat_dev[:, :, :crop_res, :crop_res].contiguous()
+            if "rse" in out or "rsp" in out:
+                cons = _score_items(lr, hat_dev, crop_res, hr_hat.shape[-1] // lr.shape[-1], fit)
+                for name in ("rse", "rsp"):
+                    if name in out:
+                        out[name].extend(sum(v.tolist()) / len(v) for v in getattr(cons, name))
             if norm:
                 hr_dev, hat_dev = ops.normalize_preds_u8(hr_dev, hat_dev)
             n, c, h, w = hr_dev.shape

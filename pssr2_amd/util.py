@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import inspect
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -279,6 +280,90 @@ def normalize_preds(hr, hr_hat, pmin: float = 0.1, pmax: float = 99.9):
     shape = a.shape
     a2, b2 = ops.normalize_preds_u8(a.to(dev).reshape(-1, *shape[-2:]), b.to(dev).reshape(-1, *shape[-2:]), pmin, pmax)
     return a2.reshape(shape).cpu().numpy(), b2.reshape(shape).cpu().numpy()
+
+
+Consistency = namedtuple("Consistency", "map alpha beta rse rsp")
+
+
+def _check_fit(fit):
+    if fit not in ops.FITS:
+        raise ValueError(f"fit must be one of {ops.FITS}. Given {fit!r}.")
+
+
+def _consistency_fit(n: int, sums, fit: str):
+    """``(alpha, beta, rsp, table)`` of one plane from its five exact sums ``Sd, Sl, Sdd, Sdl, Sll`` over ``n`` pixels (Python ints), in
+    exactly the expressions of include/pssr_mi355.h: the least-squares line ``L ~ alpha D + beta`` (or the identity), the Pearson
+    correlation of D and L, and the int32 table ``P[d]`` of the expected LR value in 1/256 grey levels (``round`` is half-to-even)."""
+    sd, sl, sdd, sdl, sll = (int(v) for v in sums)
+    num, den, denl = n * sdl - sd * sl, n * sdd - sd * sd, n * sll - sl * sl
+    if fit == "identity":
+        alpha, beta = 1.0, 0.0
+    elif den == 0:
+        alpha, beta = 0.0, sl / n
+    else:
+        alpha = num / den
+        beta = (sl - alpha * sd) / n
+    rsp = num / math.sqrt(den * denl) if den > 0 and denl > 0 else 0.0
+    table = [min(max(round(256.0 * (alpha * d + beta)), -65536), 131071) for d in range(256)]
+    return alpha, beta, rsp, table
+
+
+def consistency_map(lr, hr_hat, *, fit: str = "affine", to_numpy: bool = True):
+    r"""Scores predictions against their own low-resolution input, without ground truth: the resolution-scaled error map of the
+    super-resolution microscopy literature under this package's forward model (``_gen_pair``'s Pillow-bilinear reduction).  ``lr``: uint8
+    array or device tensor [N, m, h, w]; ``hr_hat``: uint8 [N, C, s*h, s*w], ``s`` an integer in 1 .. 16 (or both 3-D, without the batch
+    axis).  Plane ``j`` of a prediction is compared with frame ``j`` of the ``C`` centre frames of its input (``_slice_center``, the rule of
+    ``n_frames=[lr, hr]``).  Per plane: ``D`` = the prediction reduced to the LR grid (bit for bit ``PIL.Image.resize(..., BILINEAR)``), the
+    line ``L ~ alpha D + beta`` fitted by least squares over the plane (``fit="affine"``; ``"identity"``: ``alpha = 1, beta = 0``), and
+
+    * ``map``: uint8 [N, C, h, w], ``|L - (alpha D + beta)|`` rounded to grey levels (saturating at 255): where the prediction, seen through
+      the forward model, does not reproduce what was measured;
+    * ``rse``: the root mean square of that residual in grey levels, ``rsp``: the Pearson correlation of ``D`` and ``L`` (whatever ``fit``);
+    * ``alpha``, ``beta``: the fit.  The four statistics are float64 arrays [N, C].
+
+    One fused reduction + moments launch (``pssr_reduce_moments_u8``), one copy of ``5 N C`` integers to the host, the fit and the 256-entry
+    tables in Python from those integers (exact; include/pssr_mi355.h has the expressions), one upload, one map launch
+    (``pssr_consistency_map_u8``).  Everything after the fit is integer arithmetic: the result is a pure function of the bytes.
+    ``to_numpy=False`` leaves ``map`` in HBM."""
+    _check_fit(fit)
+    tensors = []
+    for name, t in (("lr", lr), ("hr_hat", hr_hat)):
+        if not torch.is_tensor(t):
+            t = torch.as_tensor(np.ascontiguousarray(t))
+        elif not t.is_cuda:
+            raise RuntimeError("pssr2_amd.util.consistency_map runs on an MI355X (HIP) device only; there is no CPU fallback")
+        if t.dtype != torch.uint8:
+            raise TypeError(f"consistency_map takes uint8 images (the LR acquisition and the output of _pred_array); {name} is {t.dtype}")
+        tensors.append(t)
+    lr, hr_hat = tensors
+    if lr.dim() != hr_hat.dim() or lr.dim() not in (3, 4):
+        raise ValueError(f"lr and hr_hat must both be [N, m, h, w] / [N, C, H, W] or both 3-D without the batch axis. Shapes are "
+                         f"{tuple(lr.shape)} and {tuple(hr_hat.shape)} respectively.")
+    batched = lr.dim() == 4
+    if not batched:
+        lr, hr_hat = lr[None], hr_hat[None]
+    (n_img, m, h, w), (n_hat, c, H, W) = lr.shape, hr_hat.shape
+    if n_img != n_hat:
+        raise ValueError(f"lr and hr_hat must have the same number of images. Received {n_img} and {n_hat} images respectively.")
+    if c > m:
+        raise ValueError(f"A prediction of {c} planes cannot be compared with an input of {m} frames.")
+    scale = H // h if h else 0
+    if min(n_img, c, h, w) < 1 or not 1 <= scale <= 16 or H != scale * h or W != scale * w:
+        raise ValueError(f"The prediction's size must be an integer multiple (1 to 16) of the input's. Sizes are {H}x{W} and {h}x{w} respectively.")
+    if h * w > 1 << 28:
+        raise ValueError(f"An input plane of {h * w} pixels is above the 2**28 up to which the squared-error sum is exact.")
+    from .data import _slice_center
+    dev = hr_hat.device if hr_hat.is_cuda else (lr.device if lr.is_cuda else "cuda")
+    frames = _slice_center(lr.to(dev), c).contiguous()
+    d, sums = ops.reduce_moments_u8(hr_hat.to(dev).contiguous(), frames)
+    fits = [_consistency_fit(h * w, row, fit) for row in sums.cpu().tolist()]
+    tables = torch.tensor([f[3] for f in fits], dtype=torch.int32).to(dev)
+    cmap, sse = ops.consistency_map_u8(d, frames, tables)
+    stats = [np.array([f[k] for f in fits], dtype=np.float64).reshape(n_img, c) for k in range(3)]
+    rse = np.array([math.sqrt(v / (h * w)) / 256 for v in sse.cpu().tolist()], dtype=np.float64).reshape(n_img, c)
+    if not batched:
+        cmap, stats, rse = cmap[0], [v[0] for v in stats], rse[0]
+    return Consistency(cmap.cpu().numpy() if to_numpy else cmap, stats[0], stats[1], rse, stats[2])
 
 
 def _sort_tiles(name: str):
