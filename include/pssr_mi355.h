@@ -546,10 +546,13 @@ int pssr_input_patchify(const float* x_nchw, void* xpatch, int n, int c, int h, 
 /* Depthwise 7x7 conv, stride 1, zero padding 3 (nn.Conv2d(C, C, groups=C, kernel_size=7, padding=3), _rdnet.py:182,197).
  * pssr_dwconv7_pack: torch weight [C,1,7,7] f32 -> [49][C] f32 (flip = 1: rotated by 180 degrees, for the input gradient).
  * pssr_dwconv7: out (+)= bias + conv(in, packed)  (accumulate = 1 adds into `out`: the gradient of a dense-stage input
- * that several blocks read).  pssr_dwconv7_wgrad: dw[C][49] += sum_pixels dy * shifted x (f32 atomics, caller zeroes).
- * pssr_dwconv7_wgrad_ws (w % 8 == 0): the same sums without atomics -- one [C][49] slab per workgroup in `workspace`
- * (pssr_dwconv7_wgrad_workspace_bytes), added to dw in a fixed order: reproducible bit for bit, and not bound by the
- * L2 atomic rate (2.7 M atomics on 21 k addresses cost ~150 us whatever the map size). */
+ * that several blocks read).  Weight gradient, dw[C][49] += sum_pixels dy * shifted x, in two forms:
+ * pssr_dwconv7_wgrad (any w) adds every workgroup's partial sums to dw with f32 atomics, so the order of the additions and
+ * the last bits of the result vary from run to run (one kernel for w % 8 != 0, a row-segment kernel for w % 8 == 0);
+ * pssr_dwconv7_wgrad_ws (w % 8 == 0 only) uses no atomics -- the row-segment kernel writes one [C][49] slab per workgroup
+ * into `workspace` (pssr_dwconv7_wgrad_workspace_bytes) and a second kernel adds the slabs to dw in a fixed order:
+ * reproducible bit for bit, and not bound by the L2 atomic rate (2.7 M atomics on 21 k addresses cost ~150 us whatever
+ * the map size).  Both add to what dw holds (the caller zeroes it or keeps a running gradient). */
 int pssr_dwconv7_pack(const float* w, float* packed, int c, int flip, pssr_stream_t stream);
 /* pssr_dwconv7_pack of up to PSSR_DWPACK_BATCH_MAX weights by one launch (every block's forward and 180-degree-rotated copy: the
  * depthwise weights of pssr/models/rdnet.py:71-73 change once per optimizer step). */

@@ -338,74 +338,10 @@ static void launch_dw_tile(const void* in, int in_cs, int in_co, const float* wp
                        MRef{out, out_cs, out_co}, n, h, w, c, accumulate, tiles_x, tiles_y, ctiles);
 }
 
-// blockIdx.y = ky; a thread keeps one channel group and walks row segments of 8 pixels
-template <typename T>
-__global__ __launch_bounds__(256) void dwconv7_wgrad_seg_kernel(Ref dy, Ref x, float* __restrict__ dw, int n, int h, int w, int c) {
-    __shared__ float lds[TPB * 28];
-    const int cgc = c / 4, ws = w / 8;
-    const int ky = blockIdx.y;
-    const long nseg = (long)n * h * ws;
-    const int ppb = cgc <= TPB ? TPB / cgc : 1;
-    for (int cg0 = 0; cg0 < cgc; cg0 += TPB) {
-        const int cg = cg0 + (cgc <= TPB ? (int)threadIdx.x % cgc : (int)threadIdx.x);
-        const int pl = cgc <= TPB ? (int)threadIdx.x / cgc : 0;
-        const bool active = cg < cgc && pl < ppb;
-        float acc[7][4];
-#pragma unroll
-        for (int k = 0; k < 7; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[k][e] = 0.f;
-        if (active) {
-            for (long sgi = (long)blockIdx.x * ppb + pl; sgi < nseg; sgi += (long)gridDim.x * ppb) {
-                long t = sgi;
-                const int xs = (t % ws) * 8; t /= ws;
-                const int y = t % h;
-                const long img_base = (t / h) * h * w;
-                const int sy = y + ky - 3;
-                if (sy < 0 || sy >= h) continue;
-                float g[8][4], v[14][4];
-#pragma unroll
-                for (int o = 0; o < 8; ++o) load4(at<T>(dy, img_base + (long)y * w + xs + o, cg * 4), g[o]);
-#pragma unroll
-                for (int j = 0; j < 14; ++j) {
-                    const int sx = xs - 3 + j;
-                    if (sx >= 0 && sx < w) load4(at<T>(x, img_base + (long)sy * w + sx, cg * 4), v[j]);
-                    else { v[j][0] = v[j][1] = v[j][2] = v[j][3] = 0.f; }
-                }
-#pragma unroll
-                for (int kx = 0; kx < 7; ++kx)
-#pragma unroll
-                    for (int o = 0; o < 8; ++o)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[kx][e] = fmaf(g[o][e], v[o + kx][e], acc[kx][e]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 7; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) lds[threadIdx.x * 28 + k * 4 + e] = active ? acc[k][e] : 0.f;
-        __syncthreads();
-        if (cgc <= TPB) {
-            if ((int)threadIdx.x < cgc) {
-                for (int k = 0; k < 7; ++k)
-                    for (int e = 0; e < 4; ++e) {
-                        float t = 0.f;
-                        for (int q = 0; q < ppb; ++q) t += lds[(q * cgc + threadIdx.x) * 28 + k * 4 + e];
-                        atomicAdd(dw + (long)(threadIdx.x * 4 + e) * 49 + ky * 7 + k, t);
-                    }
-            }
-        } else if (active) {
-            for (int k = 0; k < 7; ++k)
-                for (int e = 0; e < 4; ++e) atomicAdd(dw + (long)(cg * 4 + e) * 49 + ky * 7 + k, acc[k][e]);
-        }
-        __syncthreads();
-    }
-}
-
-// Same sums with the 7 kernel rows spread over the THREADS of a workgroup instead of blockIdx.y: a thread is (kernel row ky,
+// Same sums as dwconv7_wgrad_kernel, for W % 8 == 0, with the 7 kernel rows spread over the THREADS of a workgroup instead of blockIdx.y: a thread is (kernel row ky,
 // channel group) and the workgroup walks consecutive output rows of one 8-pixel column, so the dy segment is fetched once
 // per workgroup (the 7 ky threads hit the same lines) and an input row serves the 7 kernel rows on consecutive iterations
-// from L1/L2 -- the blockIdx.y version above streams both tensors 7 times from HBM.
+// from L1/L2 -- the blockIdx.y version streams both tensors 7 times from HBM.
 template <typename T>
 __global__ __launch_bounds__(224) void dwconv7_wgrad_rows_kernel(Ref dy, Ref x, float* __restrict__ dw, int n, int h, int w, int c, long per_block,
                                                                  float* __restrict__ part) {
