@@ -271,6 +271,14 @@ __device__ __forceinline__ long pix_index(int gi, int gy, int gx, int H, int W, 
     return ((((long)gi * (H >> blk) + (gy >> blk)) * (W >> blk) + (gx >> blk)) << (2 * blk)) + ((gy & (R - 1)) << blk) + (gx & (R - 1));
 }
 
+// Workgroup `block` of a 1-D grid of `grid` -> the tile it works on.  Workgroups go round-robin to the 8 XCDs, so with tile = block
+// neighbouring tiles sit in 8 different L2s; this gives XCD k the k-th eighth of the tiles, consecutive tiles back to back on ONE
+// XCD's L2, which then serves what they share.  The grid's remainder modulo 8 keeps its numbers.
+__device__ __forceinline__ int xcd_remap(int block, unsigned grid) {
+    const int per = grid >> 3;
+    return block < per * 8 ? (block & 7) * per + (block >> 3) : block;
+}
+
 // status helpers for the C ABI
 void pssr_set_error(const char* fmt, ...);
 #define PSSR_CHECK(cond, code, ...)                         \

@@ -499,10 +499,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs p) {
     // its neighbour along x -- run on ONE XCD, whose L2 then serves the shared input tile (with bid % tiles_n on different XCDs every
     // L2 fetched it again: up to 8 x for the 1024-channel layers) and the shared halo columns (round 3; the 1x1 kernel below had it)
     int bid = blockIdx.x;
-    if (p.ksplit <= 1 && !(p.dbg & 64)) {
-        const int per = gridDim.x >> 3;
-        if (bid < per * 8) bid = (bid & 7) * per + (bid >> 3);
-    }
+    if (p.ksplit <= 1 && !(p.dbg & 64)) bid = xcd_remap(bid, gridDim.x);
     const int tn = bid % p.tiles_n;
     int tmi = bid / p.tiles_n;
     const int tile_x = tmi % p.tiles_x; tmi /= p.tiles_x;
@@ -781,10 +778,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC <= 4 ? 3
     // run back to back on ONE XCD -- its L2 then serves the shared input tile and merges the 256-byte output segments of a
     // pixel row before they go to HBM (with bid % tiles_n on 8 different XCDs every L2 wrote its own fragment of each row)
     int bid = blockIdx.x;
-    if (p.ksplit <= 1) {
-        const int per = gridDim.x >> 3;
-        if (bid < per * 8) bid = (bid & 7) * per + (bid >> 3);
-    }
+    if (p.ksplit <= 1) bid = xcd_remap(bid, gridDim.x);
     const int tn = bid % p.tiles_n;
     int tmi = bid / p.tiles_n;
     const int tile_x = tmi % p.tiles_x; tmi /= p.tiles_x;

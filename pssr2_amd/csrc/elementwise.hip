@@ -79,16 +79,6 @@ __device__ __forceinline__ void for_items(const ChanMap& m, long npix, F f, G do
 
 // ---- steps that several kernels share, one copy each --------------------------------------------
 
-// flat index of an n x h x w pixel grid -> (image, row, column)
-struct PixPos { long img; int y, x; };
-__device__ __forceinline__ PixPos split_pix(long pix, int h, int w) {
-    PixPos p;
-    p.x = (int)(pix % w); pix /= w;
-    p.y = (int)(pix % h);
-    p.img = pix / h;
-    return p;
-}
-
 // Sum of two per-thread partials over the TPB threads of the workgroup (LDS tree), added to channel ch of the striped statistic rows
 // [s1][C] | [s2][C] by thread 0
 __device__ __forceinline__ void flush_plane(float s1, float s2, int ch, int c, double* stats) {

@@ -10,6 +10,16 @@ struct MRef { void* p; int cs, co; };
 template <typename T> __device__ __forceinline__ const T* at(const Ref& r, long pix, int c) { return (const T*)r.p + pix * r.cs + r.co + c; }
 template <typename T> __device__ __forceinline__ T* at(const MRef& r, long pix, int c) { return (T*)r.p + pix * r.cs + r.co + c; }
 
+// flat index of an n x h x w pixel grid -> (image, row, column)
+struct PixPos { long img; int y, x; };
+__device__ __forceinline__ PixPos split_pix(long pix, int h, int w) {
+    PixPos p;
+    p.x = (int)(pix % w); pix /= w;
+    p.y = (int)(pix % h);
+    p.img = pix / h;
+    return p;
+}
+
 }  // namespace
 
 // runs CALL with T = the storage type of `dtype`

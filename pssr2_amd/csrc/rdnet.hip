@@ -19,6 +19,70 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// ---- steps that several kernels share, one copy each --------------------------------------------
+
+// acc[e] = fma(a[e], b[e], acc[e]) for 4 channels as two packed f32 FMAs (v_pk_fma_f32): the depthwise kernels are bound by the vector ALU
+__device__ __forceinline__ void fma4(const float* a, const float* b, float* acc) {
+    const pssr_v2f r01 = pk_fma(pssr_v2f{a[0], a[1]}, pssr_v2f{b[0], b[1]}, pssr_v2f{acc[0], acc[1]});
+    const pssr_v2f r23 = pk_fma(pssr_v2f{a[2], a[3]}, pssr_v2f{b[2], b[3]}, pssr_v2f{acc[2], acc[3]});
+    acc[0] = r01[0]; acc[1] = r01[1]; acc[2] = r23[0]; acc[3] = r23[1];
+}
+
+// acc (+)= *p for 4 channels of T, stored back to p: the end of every kernel that can add to its output
+template <typename T>
+__device__ __forceinline__ void accum_store4(T* p, int accumulate, float* acc) {
+    if (accumulate) {
+        float prev[4];
+        load4(p, prev);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] += prev[e];
+    }
+    store4(p, acc);
+}
+
+// The 8 outputs x 4 channels a thread of the row-segment kernels keeps: start from the bias (or 0) ...
+__device__ __forceinline__ void dw_bias_init(const float* bias, int c0, float (&acc)[8][4]) {
+    float b4[4] = {0.f, 0.f, 0.f, 0.f};
+    if (bias) load4(bias + c0, b4);
+#pragma unroll
+    for (int o = 0; o < 8; ++o)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[o][e] = b4[e];
+}
+// ... one kernel row: acc[o] += v[o + kx] * w[kx] for the 7 taps, tap kx's 4 weights at wrow + kx * stride ...
+__device__ __forceinline__ void dw_row_step(const float (&v)[14][4], const float* wrow, int stride, float (&acc)[8][4]) {
+#pragma unroll
+    for (int kx = 0; kx < 7; ++kx) {
+        float wv[4];
+        load4(wrow + kx * stride, wv);
+#pragma unroll
+        for (int o = 0; o < 8; ++o) fma4(v[o + kx], wv, acc[o]);
+    }
+}
+// ... and out[prow + o, c0..c0+3] (+)= acc[o].  The sum goes to a copy: added into acc through the reference, every output's branch
+// came with a block of register moves (+290 instructions, +12 VGPRs in dwconv7_seg_kernel)
+template <typename T>
+__device__ __forceinline__ void dw_store8(MRef out, long prow, int c0, int accumulate, const float (&acc)[8][4]) {
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        float r[4] = {acc[o][0], acc[o][1], acc[o][2], acc[o][3]};
+        accum_store4(at<T>(out, prow + o, c0), accumulate, r);
+    }
+}
+
+// v[j] = 4 channels of pixel xs - 3 + j of an image row, j = 0..13, xrow = the address of pixel xs: one base, constant strides; only
+// the first / last 8-pixel segment of a row needs the left / right zero padding
+template <typename T>
+__device__ __forceinline__ void load_row14(const T* xrow, int cs, int xs, int w, float (&v)[14][4]) {
+    const bool left = xs == 0, right = xs + 8 == w;
+#pragma unroll
+    for (int j = 0; j < 14; ++j) {
+        const bool pad = (j < 3 && left) || (j >= 11 && right);
+        if (!pad) load4(xrow + (long)(j - 3) * cs, v[j]);
+        else { v[j][0] = v[j][1] = v[j][2] = v[j][3] = 0.f; }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // xpatch[n, oy, ox, ci*ps*ps + dy*ps + dx] = bn(x[n, ci, oy*ps+dy, ox*ps+dx]*pre_scale + pre_shift)
 template <typename T>
@@ -42,17 +106,8 @@ __global__ void patchify_kernel(const float* __restrict__ x, T* __restrict__ xp,
     }
 }
 
-// packed depthwise weight: wp[tap][c] = w[c][flip ? 48 - tap : tap]
-__global__ void dw_pack_kernel(const float* __restrict__ w, float* __restrict__ wp, int c, int flip) {
-    const int total = 49 * c;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int ch = i % c, tap = i / c;
-        wp[i] = w[ch * 49 + (flip ? 48 - tap : tap)];
-    }
-}
-
-// every depthwise weight of a model (both orientations) by one launch, blockIdx.y = item: RDNet packed 42 of them per training step,
-// each a launch of its own at the head of a dependent chain
+// packed depthwise weight: wp[tap][c] = w[c][flip ? 48 - tap : tap], blockIdx.y = item.  Every depthwise weight of a model (both
+// orientations) goes by one launch: RDNet packed 42 of them per training step, each a launch of its own at the head of a dependent chain
 __global__ void dw_pack_batch_kernel(pssr_dwpack_batch items) {
     const int it = blockIdx.y;
     const float* __restrict__ w = items.w[it];
@@ -73,18 +128,17 @@ __global__ void dwconv7_kernel(Ref in, const float* __restrict__ wp, const float
     const long total = (long)n * h * w * cg;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int c0 = (i % cg) * 4;
-        long pix = i / cg;
-        const int px = pix % w;
-        const int py = (pix / w) % h;
-        const long img_base = (pix / ((long)w * h)) * h * w;
+        const long pix = i / cg;
+        const PixPos p = split_pix(pix, h, w);
+        const long img_base = p.img * h * w;
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         if (bias) load4(bias + c0, acc);
         for (int ky = 0; ky < 7; ++ky) {
-            const int sy = py + ky - 3;
+            const int sy = p.y + ky - 3;
             if (sy < 0 || sy >= h) continue;
 #pragma unroll
             for (int kx = 0; kx < 7; ++kx) {
-                const int sx = px + kx - 3;
+                const int sx = p.x + kx - 3;
                 if (sx < 0 || sx >= w) continue;
                 float v[4];
                 load4(at<T>(in, img_base + (long)sy * w + sx, c0), v);
@@ -93,13 +147,7 @@ __global__ void dwconv7_kernel(Ref in, const float* __restrict__ wp, const float
                 acc[2] = fmaf(v[2], wv.z, acc[2]); acc[3] = fmaf(v[3], wv.w, acc[3]);
             }
         }
-        if (accumulate) {
-            float o[4];
-            load4(at<T>(out, pix, c0), o);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[e] += o[e];
-        }
-        store4(at<T>(out, pix, c0), acc);
+        accum_store4(at<T>(out, pix, c0), accumulate, acc);
     }
 }
 
@@ -122,16 +170,15 @@ __global__ void dwconv7_wgrad_kernel(Ref dy, Ref x, float* __restrict__ dw, int 
             for (int e = 0; e < 4; ++e) acc[k][e] = 0.f;
         if (active) {
             for (long pix = (long)blockIdx.x * ppb + pl; pix < npix; pix += (long)gridDim.x * ppb) {
-                const int px = pix % w;
-                const int py = (pix / w) % h;
-                const int sy = py + ky - 3;
+                const PixPos p = split_pix(pix, h, w);
+                const int sy = p.y + ky - 3;
                 if (sy < 0 || sy >= h) continue;
                 float g[4];
                 load4(at<T>(dy, pix, cg * 4), g);
-                const long row = pix - px + (long)(ky - 3) * w;
+                const long row = pix - p.x + (long)(ky - 3) * w;
 #pragma unroll
                 for (int kx = 0; kx < 7; ++kx) {
-                    const int sx = px + kx - 3;
+                    const int sx = p.x + kx - 3;
                     if (sx < 0 || sx >= w) continue;
                     float v[4];
                     load4(at<T>(x, row + sx, cg * 4), v);
@@ -172,52 +219,19 @@ __global__ __launch_bounds__(256) void dwconv7_seg_kernel(Ref in, const float* _
     const long total = (long)n * h * ws * cg;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int c0 = (i % cg) * 4;
-        long t = i / cg;
-        const int xs = (t % ws) * 8; t /= ws;
-        const int y = t % h;
-        const long img_base = (t / h) * h * w;
+        const PixPos p = split_pix(i / cg, h, ws);                  // (image, row, 8-pixel segment)
+        const int xs = p.x * 8;
+        const long img_base = p.img * h * w;
         float acc[8][4];
-        float b4[4] = {0.f, 0.f, 0.f, 0.f};
-        if (bias) load4(bias + c0, b4);
-#pragma unroll
-        for (int o = 0; o < 8; ++o)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[o][e] = b4[e];
+        dw_bias_init(bias, c0, acc);
         for (int ky = 0; ky < 7; ++ky) {
-            const int sy = y + ky - 3;
+            const int sy = p.y + ky - 3;
             if (sy < 0 || sy >= h) continue;
             float v[14][4];
-            const T* xrow = at<T>(in, img_base + (long)sy * w + xs, c0);      // one base per row, constant strides, edge padding only
-            const bool left = xs == 0, right = xs + 8 == w;
-#pragma unroll
-            for (int j = 0; j < 14; ++j) {
-                const bool pad = (j < 3 && left) || (j >= 11 && right);
-                if (!pad) load4(xrow + (long)(j - 3) * in.cs, v[j]);
-                else { v[j][0] = v[j][1] = v[j][2] = v[j][3] = 0.f; }
-            }
-#pragma unroll
-            for (int kx = 0; kx < 7; ++kx) {      // packed f32 FMAs (v_pk_fma_f32): the kernel is bound by the vector ALU
-                const float4 wv = *(const float4*)(wp + (ky * 7 + kx) * c + c0);
-                const f32x2 w01 = {wv.x, wv.y}, w23 = {wv.z, wv.w};
-#pragma unroll
-                for (int o = 0; o < 8; ++o) {
-                    const f32x2 a01 = __builtin_elementwise_fma(f32x2{v[o + kx][0], v[o + kx][1]}, w01, f32x2{acc[o][0], acc[o][1]});
-                    const f32x2 a23 = __builtin_elementwise_fma(f32x2{v[o + kx][2], v[o + kx][3]}, w23, f32x2{acc[o][2], acc[o][3]});
-                    acc[o][0] = a01[0]; acc[o][1] = a01[1]; acc[o][2] = a23[0]; acc[o][3] = a23[1];
-                }
-            }
+            load_row14(at<T>(in, img_base + (long)sy * w + xs, c0), in.cs, xs, w, v);
+            dw_row_step(v, wp + ky * 7 * c + c0, c, acc);
         }
-        const long prow = img_base + (long)y * w + xs;
-#pragma unroll
-        for (int o = 0; o < 8; ++o) {
-            if (accumulate) {
-                float prev[4];
-                load4(at<T>(out, prow + o, c0), prev);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[o][e] += prev[e];
-            }
-            store4(at<T>(out, prow + o, c0), acc[o]);
-        }
+        dw_store8<T>(out, img_base + (long)p.y * w + xs, c0, accumulate, acc);
     }
 }
 
@@ -233,6 +247,9 @@ template <typename T> struct DwTile {
     static constexpr int W_BYTES = 49 * CT * 4;
     static constexpr int lds_bytes(int ty) { return (ty + 6) * HXP * PS + W_BYTES; }
 };
+// item `it` of the halo staging -> (channel group of 4, halo column, halo row), channel groups fastest.  A macro: as a function or a
+// constructor the decode cost dwconv7_tile_kernel<float, 8> 2 VGPRs (130), and with them a wave of occupancy
+#define DW_HALO_ITEM(it, cgi, col, row) const int cgi = (it) & 15, col = ((it) >> 4) % D::HX, row = ((it) >> 4) / D::HX
 
 template <typename T, int TY>
 __global__ __launch_bounds__(32 * TY) void dwconv7_tile_kernel(Ref in, const float* __restrict__ wp, const float* __restrict__ bias, MRef out,
@@ -244,11 +261,7 @@ __global__ __launch_bounds__(32 * TY) void dwconv7_tile_kernel(Ref in, const flo
     char* halo = smem;                                                   // [HY][23] pixels of PS bytes (22 used)
     float* wl = (float*)(smem + HY * D::HXP * D::PS);                    // [49][64]
     const int tid = threadIdx.x;
-    int b = blockIdx.x;
-    {   // consecutive tiles on ONE XCD (workgroups go round-robin to the 8 XCDs): neighbouring tiles share their halo in its L2
-        const int per = gridDim.x >> 3;
-        if (b < per * 8) b = (b & 7) * per + (b >> 3);
-    }
+    int b = xcd_remap(blockIdx.x, gridDim.x);                           // neighbouring tiles share their halo in one XCD's L2
     const int ct = b % ctiles; b /= ctiles;
     const int tx = b % tiles_x; b /= tiles_x;
     const int ty = b % tiles_y;
@@ -262,8 +275,7 @@ __global__ __launch_bounds__(32 * TY) void dwconv7_tile_kernel(Ref in, const flo
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
         const int it = tid + k * NT;
-        const int cgi = it & 15, px = it >> 4;
-        const int col = px % D::HX, row = px / D::HX;
+        DW_HALO_ITEM(it, cgi, col, row);
         const int gy = y0 + row - 3, gx = x0 + col - 3;
         V v = {};
         if (it < HY * D::HX * 16 && gy >= 0 && gy < h && gx >= 0 && gx < w && cb + cgi * 4 < c)
@@ -273,8 +285,7 @@ __global__ __launch_bounds__(32 * TY) void dwconv7_tile_kernel(Ref in, const flo
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
         const int it = tid + k * NT;
-        const int cgi = it & 15, px = it >> 4;
-        const int col = px % D::HX, row = px / D::HX;
+        DW_HALO_ITEM(it, cgi, col, row);
         if (it < HY * D::HX * 16) *(V*)(halo + (row * D::HXP + col) * D::PS + cgi * 4 * (int)sizeof(T)) = stage[k];
     }
     for (int it = tid; it < 49 * 16; it += NT) {
@@ -289,41 +300,16 @@ __global__ __launch_bounds__(32 * TY) void dwconv7_tile_kernel(Ref in, const flo
     const int c0 = cb + cgi * 4, y = y0 + row, xs = x0 + xseg * 8;
     if (c0 >= c || y >= h || xs >= w) return;
     float acc[8][4];
-    float b4[4] = {0.f, 0.f, 0.f, 0.f};
-    if (bias) load4(bias + c0, b4);
-#pragma unroll
-    for (int o = 0; o < 8; ++o)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[o][e] = b4[e];
+    dw_bias_init(bias, c0, acc);
 #pragma unroll 1
     for (int ky = 0; ky < 7; ++ky) {
         float v[14][4];
         const char* hrow = halo + ((row + ky) * D::HXP + xseg * 8) * D::PS + cgi * 4 * (int)sizeof(T);
 #pragma unroll
         for (int j = 0; j < 14; ++j) load4((const T*)(hrow + j * D::PS), v[j]);
-#pragma unroll
-        for (int kx = 0; kx < 7; ++kx) {
-            const float4 wv = *(const float4*)(wl + (ky * 7 + kx) * D::CT + cgi * 4);
-            const f32x2 w01 = {wv.x, wv.y}, w23 = {wv.z, wv.w};
-#pragma unroll
-            for (int o = 0; o < 8; ++o) {
-                const f32x2 a01 = __builtin_elementwise_fma(f32x2{v[o + kx][0], v[o + kx][1]}, w01, f32x2{acc[o][0], acc[o][1]});
-                const f32x2 a23 = __builtin_elementwise_fma(f32x2{v[o + kx][2], v[o + kx][3]}, w23, f32x2{acc[o][2], acc[o][3]});
-                acc[o][0] = a01[0]; acc[o][1] = a01[1]; acc[o][2] = a23[0]; acc[o][3] = a23[1];
-            }
-        }
+        dw_row_step(v, wl + ky * 7 * D::CT + cgi * 4, D::CT, acc);
     }
-    const long prow = img_base + (long)y * w + xs;
-#pragma unroll
-    for (int o = 0; o < 8; ++o) {
-        if (accumulate) {
-            float prev[4];
-            load4(at<T>(out, prow + o, c0), prev);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[o][e] += prev[e];
-        }
-        store4(at<T>(out, prow + o, c0), acc[o]);
-    }
+    dw_store8<T>(out, img_base + (long)y * w + xs, c0, accumulate, acc);
 }
 
 template <typename T, int TY>
@@ -349,11 +335,7 @@ __global__ __launch_bounds__(224) void dwconv7_wgrad_rows_kernel(Ref dy, Ref x, 
     const int ky = threadIdx.x / 32, cg = blockIdx.y * 32 + threadIdx.x % 32;
     if (cg >= cgc) return;
     const long nseg = (long)n * ws * h;                        // segment index = (img * ws + xseg) * h + y: y fastest
-    int bx = blockIdx.x;                                        // consecutive segment runs on ONE XCD: they share input rows in its L2
-    {
-        const int per = gridDim.x >> 3;
-        if (bx < per * 8) bx = (bx & 7) * per + (bx >> 3);
-    }
+    const int bx = xcd_remap(blockIdx.x, gridDim.x);            // consecutive segment runs share input rows in one XCD's L2
     const long s0 = (long)bx * per_block, s1 = s0 + per_block < nseg ? s0 + per_block : nseg;
     float acc[7][4];
 #pragma unroll
@@ -368,27 +350,16 @@ __global__ __launch_bounds__(224) void dwconv7_wgrad_rows_kernel(Ref dy, Ref x, 
         const int sy = y + ky - 3;
         if (sy < 0 || sy >= h) continue;
         float g[8][4], v[14][4];
-        // one base address per row segment, constant strides from it; only the first / last segment of a row needs the
-        // left / right zero padding (the per-load 64-bit index arithmetic and range tests were most of this kernel's VALU work)
+        // one base address per row segment, constant strides from it (the per-load 64-bit index arithmetic and range tests were
+        // most of this kernel's VALU work)
         const T* grow = at<T>(dy, img_base + (long)y * w + xs, cg * 4);
-        const T* xrow = at<T>(x, img_base + (long)sy * w + xs, cg * 4);
 #pragma unroll
         for (int o = 0; o < 8; ++o) load4(grow + (long)o * dy.cs, g[o]);
-        const bool left = xs == 0, right = xs + 8 == w;
+        load_row14(at<T>(x, img_base + (long)sy * w + xs, cg * 4), x.cs, xs, w, v);
 #pragma unroll
-        for (int j = 0; j < 14; ++j) {
-            const bool pad = (j < 3 && left) || (j >= 11 && right);
-            if (!pad) load4(xrow + (long)(j - 3) * x.cs, v[j]);
-            else { v[j][0] = v[j][1] = v[j][2] = v[j][3] = 0.f; }
-        }
+        for (int kx = 0; kx < 7; ++kx)
 #pragma unroll
-        for (int kx = 0; kx < 7; ++kx)       // packed f32 FMAs (v_pk_fma_f32): the kernel is bound by the vector ALU
-#pragma unroll
-            for (int o = 0; o < 8; ++o) {
-                const f32x2 a01 = __builtin_elementwise_fma(f32x2{g[o][0], g[o][1]}, f32x2{v[o + kx][0], v[o + kx][1]}, f32x2{acc[kx][0], acc[kx][1]});
-                const f32x2 a23 = __builtin_elementwise_fma(f32x2{g[o][2], g[o][3]}, f32x2{v[o + kx][2], v[o + kx][3]}, f32x2{acc[kx][2], acc[kx][3]});
-                acc[kx][0] = a01[0]; acc[kx][1] = a01[1]; acc[kx][2] = a23[0]; acc[kx][3] = a23[1];
-            }
+            for (int o = 0; o < 8; ++o) fma4(g[o], v[o + kx], acc[kx]);
     }
     if (part) {      // one slab [gridDim.y * 128 channels][49] per workgroup, summed in a fixed order by dwconv7_wgrad_reduce_kernel
         float* slab = part + (long)bx * gridDim.y * 128 * 49;
@@ -433,6 +404,9 @@ __global__ __launch_bounds__(1024) void dwconv7_wgrad_reduce_kernel(const float*
 // LayerNorm2d: one wave per pixel, lane l holds channel groups l, l+64, ...  (C <= 256*LN_MAXIT)
 constexpr int LN_MAXIT = 8;
 
+// where pixel `pix` goes in the output: itself, or its 2x2 space-to-depth cell and the channel base of its place in the cell.  The
+// split is spelled out here: through split_pix (nhwc.h) all twelve forward kernels come out ~150 instructions shorter and
+// ln_fwd_kernel<float, 2, 2> / ln_bwd_kernel<16-bit, 4, 512> change occupancy (7 -> 8, 3 -> 4), which is a tuning step of its own
 __device__ __forceinline__ void ln_out_pos(long pix, int h, int w, int s2d, int cpad, long& opix, int& cbase) {
     if (!s2d) { opix = pix; cbase = 0; return; }
     const int px = pix % w;
@@ -441,6 +415,9 @@ __device__ __forceinline__ void ln_out_pos(long pix, int h, int w, int s2d, int 
     opix = (img * (h / 2) + py / 2) * (w / 2) + px / 2;
     cbase = ((py & 1) * 2 + (px & 1)) * cpad;
 }
+
+// first channel of slice `it` of a lane's walk over the channels of a pixel: 4 channels per lane, 256 per slice
+__device__ __forceinline__ int slice_c0(int lane, int it) { return (lane + 64 * it) * 4; }
 
 // NIT = channel slices of 256 a lane walks, PP = pixels a wave keeps in flight: a pixel is a load -> two wave reductions -> store
 // chain of ~3 us, so with one pixel per wave the kernel ran at the rate of that chain (1.2 TB/s on 64 x 64 x 128 channels)
@@ -460,7 +437,7 @@ __global__ __launch_bounds__(TPB) void ln_fwd_kernel(Ref in, const float* __rest
             const long pix = pix0 + u < npix ? pix0 + u : npix - 1;          // the tail repeats the last pixel (stores are guarded)
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
-                const int c0 = (lane + 64 * it) * 4;
+                const int c0 = slice_c0(lane, it);
                 if (c0 < c) {
                     load4(at<T>(in, pix, c0), v[u][it]);
                     s[u] += (v[u][it][0] + v[u][it][1]) + (v[u][it][2] + v[u][it][3]);
@@ -473,7 +450,7 @@ __global__ __launch_bounds__(TPB) void ln_fwd_kernel(Ref in, const float* __rest
             q[u] = 0.f;
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
-                const int c0 = (lane + 64 * it) * 4;
+                const int c0 = slice_c0(lane, it);
                 if (c0 < c) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { const float d = v[u][it][e] - mu[u]; q[u] = fmaf(d, d, q[u]); }
@@ -490,7 +467,7 @@ __global__ __launch_bounds__(TPB) void ln_fwd_kernel(Ref in, const float* __rest
             ln_out_pos(pix, h, w, s2d, cpad, opix, cbase);
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
-                const int c0 = (lane + 64 * it) * 4;
+                const int c0 = slice_c0(lane, it);
                 if (c0 < c) {
                     float g[4], b[4], o[4];
                     load4(gamma + c0, g); load4(beta + c0, b);
@@ -510,10 +487,10 @@ __global__ __launch_bounds__(TPB) void ln_fwd_kernel(Ref in, const float* __rest
 // dx (+)= rstd * (g*gamma - mean_c(g*gamma) - xhat * mean_c(g*gamma*xhat));  stats += [sum_p g*xhat | sum_p g]
 // NIT = channel slices of 256 a lane walks (registers scale with it), NT = threads: few slices leave room for 16 waves per
 // workgroup, which share one flush of the statistics (the f64 atomics bound how many workgroups a launch can afford)
-// PP = pixels a wave has in flight per trip (their loads issued together, their reductions independent).  Measured
-// (tools/diag/microbench_ln.py): PP = 2 / 4 change nothing -- what a launch pays besides its bytes is the statistics flush at the end,
-// 2c f64 atomic pairs per workgroup (10-20 us for 256-512 workgroups: PSSR_LN_DBG=1 leaves it out) -- so only PP = 1 is built
-template <typename T, int NIT, int NT, int PP>
+// A wave has one pixel in flight per trip.  Measured (tools/diag/microbench_ln.py): 2 / 4 pixels in flight change nothing -- what a launch
+// pays besides its bytes is the statistics flush at the end, 2c f64 atomic pairs per workgroup (10-20 us for 256-512 workgroups:
+// PSSR_LN_DBG=1 leaves it out)
+template <typename T, int NIT, int NT>
 __global__ __launch_bounds__(NT) void ln_bwd_kernel(Ref g, int s2d, int cpad, Ref x, const float* __restrict__ gamma, const float* __restrict__ mean,
                               const float* __restrict__ rstd, MRef dx, int accumulate, long npix, int h, int w, int c, double* stats, int dbg) {
     __shared__ float lds[(NT / 64) * 64 * 8];
@@ -529,74 +506,53 @@ __global__ __launch_bounds__(NT) void ln_bwd_kernel(Ref g, int s2d, int cpad, Re
     float gm[NIT][4];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-        const int c0 = (lane + 64 * it) * 4;
+        const int c0 = slice_c0(lane, it);
 #pragma unroll
         for (int e = 0; e < 4; ++e) gm[it][e] = 0.f;
         if (c0 < c) load4(gamma + c0, gm[it]);
     }
-    for (long pix0 = wid; pix0 < npix; pix0 += nw * PP) {
-        float xh[PP][NIT][4], gg[PP][NIT][4], gv[PP][NIT][4];
-        float mu[PP], rs[PP], s1[PP], s2[PP];
-        bool ok[PP];
+    for (long pix = wid; pix < npix; pix += nw) {
+        float xh[NIT][4], gg[NIT][4], gv[NIT][4];
+        const float mu = mean[pix], rs = rstd[pix];
+        long opix; int cbase;
+        ln_out_pos(pix, h, w, s2d, cpad, opix, cbase);
 #pragma unroll
-        for (int u = 0; u < PP; ++u) {
-            const long pix = pix0 + u * nw;
-            ok[u] = pix < npix;
-            mu[u] = ok[u] ? mean[pix] : 0.f;
-            rs[u] = ok[u] ? rstd[pix] : 0.f;
-            long opix = 0; int cbase = 0;
-            if (ok[u]) ln_out_pos(pix, h, w, s2d, cpad, opix, cbase);
+        for (int it = 0; it < NIT; ++it) {
+            const int c0 = slice_c0(lane, it);
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int c0 = (lane + 64 * it) * 4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { xh[u][it][e] = 0.f; gv[u][it][e] = 0.f; }
-                if (ok[u] && c0 < c) { load4(at<T>(x, pix, c0), xh[u][it]); load4(at<T>(g, opix, cbase + c0), gv[u][it]); }
-            }
+            for (int e = 0; e < 4; ++e) { xh[it][e] = 0.f; gv[it][e] = 0.f; }
+            if (c0 < c) { load4(at<T>(x, pix, c0), xh[it]); load4(at<T>(g, opix, cbase + c0), gv[it]); }
         }
+        float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-        for (int u = 0; u < PP; ++u) {
-            s1[u] = 0.f; s2[u] = 0.f;
+        for (int it = 0; it < NIT; ++it) {
+            if (slice_c0(lane, it) < c) {
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int c0 = (lane + 64 * it) * 4;
-                if (c0 < c) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        xh[u][it][e] = (xh[u][it][e] - mu[u]) * rs[u];
-                        gg[u][it][e] = gv[u][it][e] * gm[it][e];
-                        s1[u] += gg[u][it][e];
-                        s2[u] = fmaf(gg[u][it][e], xh[u][it][e], s2[u]);
-                        if (ok[u]) {
-                            dgam[it][e] = fmaf(gv[u][it][e], xh[u][it][e], dgam[it][e]);
-                            dbet[it][e] += gv[u][it][e];
-                        }
-                    }
+                for (int e = 0; e < 4; ++e) {
+                    xh[it][e] = (xh[it][e] - mu) * rs;
+                    gg[it][e] = gv[it][e] * gm[it][e];
+                    s1 += gg[it][e];
+                    s2 = fmaf(gg[it][e], xh[it][e], s2);
+                    dgam[it][e] = fmaf(gv[it][e], xh[it][e], dgam[it][e]);
+                    dbet[it][e] += gv[it][e];
                 }
             }
         }
-        float m1[PP], m2[PP];
+        const float m1 = wave_sum(s1) * inv_c, m2 = wave_sum(s2) * inv_c;
 #pragma unroll
-        for (int u = 0; u < PP; ++u) { m1[u] = wave_sum(s1[u]) * inv_c; m2[u] = wave_sum(s2[u]) * inv_c; }
+        for (int it = 0; it < NIT; ++it) {
+            const int c0 = slice_c0(lane, it);
+            if (c0 < c) {
+                float o[4];
 #pragma unroll
-        for (int u = 0; u < PP; ++u) {
-            const long pix = pix0 + u * nw;
-            if (!ok[u]) continue;
+                for (int e = 0; e < 4; ++e) o[e] = rs * (gg[it][e] - m1 - xh[it][e] * m2);
+                if (accumulate) {
+                    float prev[4];
+                    load4(at<T>(dx, pix, c0), prev);
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int c0 = (lane + 64 * it) * 4;
-                if (c0 < c) {
-                    float o[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = rs[u] * (gg[u][it][e] - m1[u] - xh[u][it][e] * m2[u]);
-                    if (accumulate) {
-                        float prev[4];
-                        load4(at<T>(dx, pix, c0), prev);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] += prev[e];
-                    }
-                    store4(at<T>(dx, pix, c0), o);
+                    for (int e = 0; e < 4; ++e) o[e] += prev[e];
                 }
+                store4(at<T>(dx, pix, c0), o);
             }
         }
     }
@@ -611,7 +567,7 @@ __global__ __launch_bounds__(NT) void ln_bwd_kernel(Ref g, int s2d, int cpad, Re
         for (int e = 0; e < 4; ++e) { lds[(wv * 64 + lane) * 8 + e] = dgam[it][e]; lds[(wv * 64 + lane) * 8 + 4 + e] = dbet[it][e]; }
         __syncthreads();
         if (wv == 0) {
-            const int c0 = (lane + 64 * it) * 4;
+            const int c0 = slice_c0(lane, it);
             if (c0 < c) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -704,7 +660,7 @@ __global__ __launch_bounds__(256) void ese_gate_kernel(const float* __restrict__
     const int img = i / c, co = i % c;
     float acc = 0.f;
     for (int ci = lane; ci < c; ci += 64) acc = fmaf(w[(long)co * c + ci], s[(long)img * c + ci], acc);
-    for (int o = 32; o; o >>= 1) acc += __shfl_down(acc, o, 64);
+    acc = wave_sum(acc);
     if (lane == 0) {
         acc += b[co];
         u[i] = acc;
@@ -732,8 +688,14 @@ __global__ void scale_nc_kernel(Ref t, const float* __restrict__ gate, const flo
     }
 }
 
+// du of element i = (image, channel ch) through the gate relu6(u + 3) / 6 and the layer scale: (|u| < 3) ? A*gamma/6 : 0
+__device__ __forceinline__ float ese_du(const float* u, const float* A, const float* gamma, long i, int ch) {
+    const float uv = u[i];
+    return (uv > -3.f && uv < 3.f) ? A[i] * gamma[ch] * (1.f / 6.f) : 0.f;
+}
+
 // ESE / layer-scale backward on the [N, C] side tensors.  A[n][c] = sum_p dout*t.
-//   stage 0: du[n][c] = (|u| < 3) ? A*gamma/6 : 0
+//   stage 0: du[n][c] = ese_du(u, A, gamma)
 //   stage 1: dgamma[c] = sum_n A*gate ; dbfc[c] = sum_n du
 //   stage 2: dWfc[co][ci] = sum_n du[n][co]*s[n][ci]
 //   stage 3: add[n][ci] = inv_hw * sum_co W[co][ci]*du[n][co]
@@ -744,8 +706,7 @@ __global__ void ese_bwd_kernel(int stage, const float* __restrict__ A, const flo
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (stage == 0) {
         if (i >= (long)n * c) return;
-        const float uv = u[i];
-        du[i] = (uv > -3.f && uv < 3.f) ? A[i] * gamma[i % c] * (1.f / 6.f) : 0.f;
+        du[i] = ese_du(u, A, gamma, i, i % c);
     } else if (stage == 1) {
         if (i >= c) return;
         float a = 0.f, b = 0.f;
@@ -782,10 +743,7 @@ __global__ __launch_bounds__(256) void ese_bwd_fused_kernel(const float* __restr
                                                             float* __restrict__ dbfc, float* __restrict__ dwfc, float* __restrict__ add) {
     __shared__ float dul[ESE_MAX_C];
     const int tid = threadIdx.x;
-    auto du_at = [&](int k, int co) {
-        const float uv = u[(long)k * c + co];
-        return (uv > -3.f && uv < 3.f) ? A[(long)k * c + co] * gamma[co] * (1.f / 6.f) : 0.f;
-    };
+    auto du_at = [&](int k, int co) { return ese_du(u, A, gamma, (long)k * c + co, co); };
     const int nw = (c * c + 255) / 256;
     int b = blockIdx.x;
     const int nchunk = (c + 63) / 64, nimg = n * nchunk;
@@ -872,7 +830,9 @@ int pssr_input_patchify(const float* x, void* xpatch, int n, int c, int h, int w
 
 int pssr_dwconv7_pack(const float* w, float* packed, int c, int flip, pssr_stream_t s) {
     PSSR_CHECK(w && packed && c > 0, PSSR_ERR_ARG, "dwconv7_pack: bad args");
-    hipLaunchKernelGGL(dw_pack_kernel, dim3(grid1d(49L * c, 256)), dim3(TPB), 0, (hipStream_t)s, w, packed, c, flip);
+    pssr_dwpack_batch one = {};
+    one.w[0] = w; one.packed[0] = packed; one.c[0] = c; one.flip[0] = flip;
+    hipLaunchKernelGGL(dw_pack_batch_kernel, dim3(grid1d(49L * c, 256), 1), dim3(TPB), 0, (hipStream_t)s, one);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -909,62 +869,64 @@ int pssr_dwconv7(const void* in, int in_cs, int in_co, const float* w_packed, co
     return PSSR_OK;
 }
 
-// Workgroups along the row segments for the slab version: >= 4 segments each, ~1024 workgroups in all (16 waves per CU)
-static inline long dw_slab_blocks(int n, int h, int w, int c, long* per_block_out) {
-    const int gy = (c / 4 + 31) / 32;
+// Launch geometry of dwconv7_wgrad_rows_kernel: gy workgroups of (7 kernel rows x 32 channel groups) threads along the channels times
+// `blocks` along the row segments, each a contiguous run of per_block segments: ~`target` workgroups in all, >= min_segs segments each
+struct DwRowsGrid { int gy; long blocks, per_block; };
+static DwRowsGrid dw_rows_grid(int n, int h, int w, int c, int target, int min_segs) {
+    DwRowsGrid g;
+    g.gy = (c / 4 + 31) / 32;
     const long nseg = (long)n * h * (w / 8);
-    const int target = pssr_tunables().dwwg_blocks;
-    long gs = target / gy;
-    if (gs > nseg / 4) gs = nseg / 4;
+    long gs = target / g.gy;
+    if (gs > nseg / min_segs) gs = nseg / min_segs;
     if (gs < 1) gs = 1;
-    const long per_block = (nseg + gs - 1) / gs;
-    if (per_block_out) *per_block_out = per_block;
-    return (nseg + per_block - 1) / per_block;
+    g.per_block = (nseg + gs - 1) / gs;
+    g.blocks = (nseg + g.per_block - 1) / g.per_block;
+    return g;
+}
+// the slab version: >= 4 segments per workgroup, ~1024 workgroups in all (16 waves per CU)
+static DwRowsGrid dw_slab_grid(int n, int h, int w, int c) { return dw_rows_grid(n, h, w, c, pssr_tunables().dwwg_blocks, 4); }
+
+// what both weight-gradient entry points ask of their arguments; `own` = the entry point's own conditions (pointers, w), `what` its message
+static int dw_wgrad_args_ok(const char* what, bool own, int dy_cs, int dy_co, int x_cs, int x_co, int n, int h, int w, int c) {
+    PSSR_CHECK(own && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && (long)n * h * w < (1L << 31), PSSR_ERR_ARG, "%s", what);
+    CHECK_REF("dwconv7_wgrad dy", dy_cs, dy_co, c); CHECK_REF("dwconv7_wgrad x", x_cs, x_co, c);
+    return PSSR_OK;
 }
 
 int64_t pssr_dwconv7_wgrad_workspace_bytes(int n, int h, int w, int c) {
     if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || c % 4 || w % 8) return 0;
-    return dw_slab_blocks(n, h, w, c, nullptr) * ((c / 4 + 31) / 32) * 128 * 49 * (int64_t)sizeof(float);
+    const DwRowsGrid g = dw_slab_grid(n, h, w, c);
+    return g.blocks * g.gy * 128 * 49 * (int64_t)sizeof(float);
 }
 
 int pssr_dwconv7_wgrad_ws(const void* dy, int dy_cs, int dy_co, const void* x, int x_cs, int x_co, float* dw, int n, int h, int w, int c,
                           int dtype, void* workspace, int64_t workspace_bytes, pssr_stream_t s) {
-    PSSR_CHECK(dy && x && dw && workspace && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && w % 8 == 0 && (long)n * h * w < (1L << 31), PSSR_ERR_ARG,
-               "dwconv7_wgrad_ws: bad args (w must be a multiple of 8)");
-    CHECK_REF("dwconv7_wgrad dy", dy_cs, dy_co, c); CHECK_REF("dwconv7_wgrad x", x_cs, x_co, c);
+    if (int e = dw_wgrad_args_ok("dwconv7_wgrad_ws: bad args (w must be a multiple of 8)", dy && x && dw && workspace && w % 8 == 0, dy_cs, dy_co, x_cs, x_co,
+                                 n, h, w, c)) return e;
     PSSR_CHECK(workspace_bytes >= pssr_dwconv7_wgrad_workspace_bytes(n, h, w, c), PSSR_ERR_ARG, "dwconv7_wgrad_ws: workspace of %ld bytes, %ld needed",
                (long)workspace_bytes, (long)pssr_dwconv7_wgrad_workspace_bytes(n, h, w, c));
-    long per_block;
-    const long blocks = dw_slab_blocks(n, h, w, c, &per_block);
-    const int gy = (c / 4 + 31) / 32;
-    DISPATCH_T(dtype, hipLaunchKernelGGL(dwconv7_wgrad_rows_kernel<T>, dim3((unsigned)blocks, gy), dim3(224), 0, (hipStream_t)s, Ref{dy, dy_cs, dy_co},
-                                         Ref{x, x_cs, x_co}, dw, n, h, w, c, per_block, (float*)workspace));
+    const DwRowsGrid g = dw_slab_grid(n, h, w, c);
+    DISPATCH_T(dtype, hipLaunchKernelGGL(dwconv7_wgrad_rows_kernel<T>, dim3((unsigned)g.blocks, g.gy), dim3(224), 0, (hipStream_t)s, Ref{dy, dy_cs, dy_co},
+                                         Ref{x, x_cs, x_co}, dw, n, h, w, c, g.per_block, (float*)workspace));
     PSSR_LAUNCH_CHECK();
     hipLaunchKernelGGL(dwconv7_wgrad_reduce_kernel, dim3((c * 49 + 63) / 64), dim3(1024), 0, (hipStream_t)s, (const float*)workspace, dw, c * 49,
-                       (long)gy * 128 * 49, (int)blocks);
+                       (long)g.gy * 128 * 49, (int)g.blocks);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
 
 int pssr_dwconv7_wgrad(const void* dy, int dy_cs, int dy_co, const void* x, int x_cs, int x_co, float* dw, int n, int h, int w, int c,
                        int dtype, pssr_stream_t s) {
-    PSSR_CHECK(dy && x && dw && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && (long)n * h * w < (1L << 31), PSSR_ERR_ARG, "dwconv7_wgrad: bad args");
-    CHECK_REF("dwconv7_wgrad dy", dy_cs, dy_co, c); CHECK_REF("dwconv7_wgrad x", x_cs, x_co, c);
-    const int cgc = c / 4, ppb = cgc <= TPB ? TPB / cgc : 1;
-    long gx = ((long)n * h * w + ppb - 1) / ppb / 16;       // >= 16 pixels per thread before the atomics
-    if (gx < 1) gx = 1;
-    if (gx > 96) gx = 96;
+    if (int e = dw_wgrad_args_ok("dwconv7_wgrad: bad args", dy && x && dw, dy_cs, dy_co, x_cs, x_co, n, h, w, c)) return e;
     if (w % 8 == 0) {
-        // ~512 workgroups of (7 kernel rows x 32 channel groups) threads, each a contiguous run of row segments
-        const int gy = (cgc + 31) / 32;
-        const long nseg = (long)n * h * (w / 8);
-        long gs = 512 / gy;
-        if (gs < 1) gs = 1;
-        if (gs > nseg) gs = nseg;
-        const long per_block = (nseg + gs - 1) / gs;
-        DISPATCH_T(dtype, hipLaunchKernelGGL(dwconv7_wgrad_rows_kernel<T>, dim3((unsigned)((nseg + per_block - 1) / per_block), gy), dim3(224), 0, (hipStream_t)s,
-                                             Ref{dy, dy_cs, dy_co}, Ref{x, x_cs, x_co}, dw, n, h, w, c, per_block, (float*)nullptr));
+        const DwRowsGrid g = dw_rows_grid(n, h, w, c, 512, 1);       // the atomic version: ~512 workgroups
+        DISPATCH_T(dtype, hipLaunchKernelGGL(dwconv7_wgrad_rows_kernel<T>, dim3((unsigned)g.blocks, g.gy), dim3(224), 0, (hipStream_t)s, Ref{dy, dy_cs, dy_co},
+                                             Ref{x, x_cs, x_co}, dw, n, h, w, c, g.per_block, (float*)nullptr));
     } else {
+        const int cgc = c / 4, ppb = cgc <= TPB ? TPB / cgc : 1;
+        long gx = ((long)n * h * w + ppb - 1) / ppb / 16;       // >= 16 pixels per thread before the atomics
+        if (gx < 1) gx = 1;
+        if (gx > 96) gx = 96;
         DISPATCH_T(dtype, hipLaunchKernelGGL(dwconv7_wgrad_kernel<T>, dim3((unsigned)gx, 7), dim3(TPB), 0, (hipStream_t)s, Ref{dy, dy_cs, dy_co},
                                              Ref{x, x_cs, x_co}, dw, n, h, w, c));
     }
@@ -972,11 +934,16 @@ int pssr_dwconv7_wgrad(const void* dy, int dy_cs, int dy_co, const void* x, int 
     return PSSR_OK;
 }
 
+// what both LayerNorm entry points ask of their arguments; `ptrs` = the entry point's own pointers are there
+static int ln_args_ok(const char* name, bool ptrs, int s2d, int c_pad, int n, int h, int w, int c) {
+    PSSR_CHECK(ptrs && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && c <= 256 * LN_MAXIT, PSSR_ERR_ARG, "%s: bad args (c=%d)", name, c);
+    PSSR_CHECK(c_pad >= c && c_pad % 4 == 0 && (!s2d || (h % 2 == 0 && w % 2 == 0)), PSSR_ERR_ARG, "%s: c_pad / s2d", name);
+    return PSSR_OK;
+}
+
 int pssr_layernorm2d_fwd(const void* in, int in_cs, int in_co, const float* gamma, const float* beta, float eps, void* out, int out_cs, int out_co,
                          int s2d, int c_pad, int n, int h, int w, int c, float* mean, float* rstd, int dtype, pssr_stream_t s) {
-    PSSR_CHECK(in && gamma && beta && out && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && c <= 256 * LN_MAXIT, PSSR_ERR_ARG,
-               "layernorm2d_fwd: bad args (c=%d)", c);
-    PSSR_CHECK(c_pad >= c && c_pad % 4 == 0 && (!s2d || (h % 2 == 0 && w % 2 == 0)), PSSR_ERR_ARG, "layernorm2d_fwd: c_pad / s2d");
+    if (int e = ln_args_ok("layernorm2d_fwd", in && gamma && beta && out, s2d, c_pad, n, h, w, c)) return e;
     PSSR_CHECK((mean == nullptr) == (rstd == nullptr), PSSR_ERR_ARG, "layernorm2d_fwd: mean/rstd come in pairs");
     CHECK_REF("layernorm2d_fwd in", in_cs, in_co, c); CHECK_REF("layernorm2d_fwd out", out_cs, out_co, (s2d ? 4 : 1) * c_pad);
     const long npix = (long)n * h * w;
@@ -1000,24 +967,22 @@ int pssr_layernorm2d_fwd(const void* in, int in_cs, int in_co, const float* gamm
 int pssr_layernorm2d_bwd(const void* g, int g_cs, int g_co, int s2d, int c_pad, const void* x, int x_cs, int x_co, const float* gamma,
                          const float* mean, const float* rstd, void* dx, int dx_cs, int dx_co, int accumulate, int n, int h, int w, int c,
                          double* stats, int dtype, pssr_stream_t s) {
-    PSSR_CHECK(g && x && gamma && mean && rstd && dx && stats && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && c <= 256 * LN_MAXIT,
-               PSSR_ERR_ARG, "layernorm2d_bwd: bad args (c=%d)", c);
-    PSSR_CHECK(c_pad >= c && c_pad % 4 == 0 && (!s2d || (h % 2 == 0 && w % 2 == 0)), PSSR_ERR_ARG, "layernorm2d_bwd: c_pad / s2d");
+    if (int e = ln_args_ok("layernorm2d_bwd", g && x && gamma && mean && rstd && dx && stats, s2d, c_pad, n, h, w, c)) return e;
     CHECK_REF("layernorm2d_bwd g", g_cs, g_co, (s2d ? 4 : 1) * c_pad); CHECK_REF("layernorm2d_bwd x", x_cs, x_co, c); CHECK_REF("layernorm2d_bwd dx", dx_cs, dx_co, c);
     const long npix = (long)n * h * w;
     // >= 4 pixels per wave before the statistics are flushed, <= 512 workgroups (2c f64 atomics each)
-#define PSSR_LN_BWD(NIT_, NT_, PP_)                                                                                                         \
+#define PSSR_LN_BWD(NIT_, NT_)                                                                                                              \
     do {                                                                                                                                    \
         long blocks = (npix + (NT_) / 64 - 1) / ((NT_) / 64) / 4;                                                                           \
         if (blocks < 1) blocks = 1;                                                                                                         \
         if (blocks > pssr_tunables().ln_bwd_blocks) blocks = pssr_tunables().ln_bwd_blocks;                                                 \
-        DISPATCH_T(dtype, hipLaunchKernelGGL((ln_bwd_kernel<T, NIT_, NT_, PP_>), dim3((unsigned)blocks), dim3(NT_), 0, (hipStream_t)s, Ref{g, g_cs, g_co}, s2d, \
+        DISPATCH_T(dtype, hipLaunchKernelGGL((ln_bwd_kernel<T, NIT_, NT_>), dim3((unsigned)blocks), dim3(NT_), 0, (hipStream_t)s, Ref{g, g_cs, g_co}, s2d, \
                                              c_pad, Ref{x, x_cs, x_co}, gamma, mean, rstd, MRef{dx, dx_cs, dx_co}, accumulate, npix, h, w, c, stats, pssr_tunables().ln_dbg)); \
     } while (0)
-    if (c <= 256) PSSR_LN_BWD(1, 1024, 1);
-    else if (c <= 512) PSSR_LN_BWD(2, 1024, 1);
-    else if (c <= 1024) PSSR_LN_BWD(4, 512, 1);
-    else PSSR_LN_BWD(8, 256, 1);
+    if (c <= 256) PSSR_LN_BWD(1, 1024);
+    else if (c <= 512) PSSR_LN_BWD(2, 1024);
+    else if (c <= 1024) PSSR_LN_BWD(4, 512);
+    else PSSR_LN_BWD(8, 256);
 #undef PSSR_LN_BWD
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
