@@ -59,7 +59,8 @@ struct Philox {
 };
 __device__ __forceinline__ double u01(uint32_t hi, uint32_t lo) {   // (0,1) with 53 bits
     const uint64_t v = (((uint64_t)hi << 32) | lo) >> 11;
-    return ((double)v + 0.5) * (1.0 / 9007199254740992.0);
+    // v + 0.5 is a tie from 2^52 on and rounds to even: at the last v (all bits set) that is 2^53, i.e. 1.0, so hold it below 1
+    return fmin(((double)v + 0.5) * (1.0 / 9007199254740992.0), 1.0 - 1.0 / 9007199254740992.0);
 }
 __device__ __forceinline__ double normal_from(const uint4& r) {
     const double u1 = u01(r.x, r.y), u2 = u01(r.z, r.w);
