@@ -785,6 +785,44 @@ int64_t pssr_consistency_map_workspace_bytes(int planes, int64_t pixels);
 int pssr_consistency_map_u8(const uint8_t* d, const uint8_t* l, const int32_t* lut, uint8_t* map, uint64_t* sse, int planes,
                             int64_t pixels, void* workspace, pssr_stream_t stream);
 
+/* Registration of real (HR, LR) pairs: an exhaustive search over integer shifts (pssr2_amd.util.register_pairs; csrc/register.hip).
+ * Real pairs are two acquisitions, and stage drift puts a few HR pixels between them; everything downstream (the noise-profile
+ * objective, test_metrics, train_crappifier) assumes the same field of view pixel for pixel.  After the definitions everything is
+ * integer arithmetic.
+ * Inputs, per plane pair: H uint8 [s*h][s*w] (the HR side), L uint8 [h][w] (the LR side), s an integer in 1 .. 16, a search radius R in
+ * HR pixels, 0 .. 32, giving T = (2R+1)^2 shifts t = (ty, tx), ty, tx in [-R, R]; the row index of t is (ty + R) (2R + 1) + (tx + R).
+ *   1. Interior taps.  For an integer s, Pillow's BILINEAR reduction by s uses the same 2 s fixed-point coefficients k[0 .. 2s) (22-bit,
+ *      csrc/pil_taps.h, evaluated for an interior index; not restated) for every interior output x, starting at input index
+ *      s x - floor(s / 2).  For s = 1 they are the identity.
+ *   2. Margin.  m = 1 + ceil(R / s) LR pixels; h' = h - 2m and w' = w - 2m must both be >= 1, otherwise PSSR_ERR_ARG.  With this m no
+ *      candidate ever touches a border tap or leaves H.
+ *   3. Reduced window per shift.  D_t[y][x], 0 <= y < h', 0 <= x < w', is the two-pass reduction of H sampled at HR origin
+ *      (s (y + m) + ty, s (x + m) + tx): horizontal pass first, then vertical, clip8 (the rounding to uint8) after each pass, as in
+ *      pssr_bilinear_down_u8.  Equivalently: filter H densely at every HR position and sample that map at stride s with offset t.
+ *      Consequence: D_(0,0) == pssr_bilinear_down_u8(H)[m : h - m, m : w - m], bit for bit.
+ *   4. Sums.  Lc = L[m : h - m, m : w - m].  Per plane and shift: Sd = sum D_t, Sdd = sum D_t^2, Sdl = sum D_t Lc; per plane:
+ *      Sl = sum Lc, Sll = sum Lc^2.  All exact unsigned 64-bit integers.  Limits: s h, s w < 2^30 and h w <= 2^28.
+ *   5. Choice (host, Python ints).  An item's planes pool: their sums add, and n = C h' w'.  num_t = n Sdl - Sd Sl,
+ *      den_t = n Sdd - Sd^2, denl = n Sll - Sl^2.  The score is the signed squared Pearson correlation num_t |num_t| / (den_t denl), taken
+ *      as 0 when den_t = 0 or denl = 0; scores are compared by cross-multiplying integers, never in floating point.  The chosen shift
+ *      maximises the score; ties go to the smaller ty^2 + tx^2, then the smaller ty, then the smaller tx (a constant pair therefore
+ *      chooses (0, 0)).  The reported score is the float num / sqrt(den denl) of the chosen shift.
+ *   6. Aligned pair.  lr_out = L[m : h - m, m : w - m], hr_out = H[s m + ty : s (h - m) + ty, s m + tx : s (w - m) + tx].
+ * pssr_register_shifts_u8: steps 1 - 4 in one fused pass.  hr [planes][s*h][s*w], lr [planes][h][w], sums [planes][3T + 2]: T triples
+ *   (Sd, Sdd, Sdl) in row-index order, then Sl, Sll.  Every byte of hr is read from HBM about once; the dense filtered map lives in LDS.
+ * pssr_crop_shift_u8: step 6.  out[p] = in[p][y0 : y0 + ho, x0 : x0 + wo] for in [planes][H][W], out [planes][ho][wo] and a device table
+ *   origins [planes][2] of (y0, x0), with 16-byte accesses where alignment allows.  The table's values are the caller's contract
+ *   (0 <= y0 <= H - ho, 0 <= x0 <= W - wo), as lut is for pssr_consistency_map_u8; pssr2_amd.ops.crop_shift_u8 checks them.
+ * Both validate on the host before anything is launched (null pointers, planes, sizes, s outside 1 .. 16, radius outside 0 .. 32,
+ * h' or w' < 1, the limits of step 4, a window larger than its plane): PSSR_ERR_ARG with a message.  Integer sums through per-workgroup
+ * 64-bit partials in the workspace and a second small launch: no atomics, no fence, no floating-point accumulation, the same bits on
+ * every run.  Workspace of pssr_register_shifts_workspace_bytes bytes (0 for arguments the entry point rejects). */
+int64_t pssr_register_shifts_workspace_bytes(int planes, int h, int w, int s, int radius);
+int pssr_register_shifts_u8(const uint8_t* hr, const uint8_t* lr, uint64_t* sums, int planes, int h, int w, int s, int radius,
+                            void* workspace, pssr_stream_t stream);
+int pssr_crop_shift_u8(const uint8_t* in, uint8_t* out, const int32_t* origins, int planes, int H, int W, int ho, int wo,
+                       pssr_stream_t stream);
+
 /* Several small f32 device-to-device copies in one launch (host struct passed by value to the kernel): the hand-written
  * backward pass moves side results (dbeta doubling as a bias gradient, centre taps, ...) into the flat gradient buffer the
  * all-reduce and AdamW read (the reference leaves this to autograd's .grad accumulation). */

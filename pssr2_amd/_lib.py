@@ -138,6 +138,11 @@ def lib():
         _lib.pssr_consistency_map_workspace_bytes.restype = c_i64
         _lib.pssr_consistency_map_workspace_bytes.argtypes = [c_int, c_i64]
         _lib.pssr_consistency_map_u8.argtypes = [c_void_p] * 5 + [c_int, c_i64] + [c_void_p] * 2
+        # registration of real pairs (csrc/register.hip)
+        _lib.pssr_register_shifts_workspace_bytes.restype = c_i64
+        _lib.pssr_register_shifts_workspace_bytes.argtypes = [c_int] * 5
+        _lib.pssr_register_shifts_u8.argtypes = [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
+        _lib.pssr_crop_shift_u8.argtypes = [c_void_p] * 3 + [c_int] * 5 + [c_void_p]
         # one-pass backward of a flat-K source (csrc/pre_xcol_bwd.hip)
         _lib.pssr_flatk_bwd_pair_supported.argtypes = [c_int] * 3
         _lib.pssr_flatk_bwd_pair_parts.argtypes = [c_i64]

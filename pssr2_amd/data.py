@@ -226,6 +226,16 @@ def _check_paired(hr, lr, error=ValueError):
     return hr, lr
 
 
+def _check_register(register, who):
+    """``register=None`` or a search radius for ``util.register_pairs``; a radius needs a HIP device, and says so before anything is read."""
+    if register is None:
+        return
+    from .util import _check_radius
+    _check_radius(register, f"{who}: register")
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{who}: register={register} aligns the stacks on an MI355X (HIP) device, and none is available; there is no CPU fallback")
+
+
 def _paired_stacks(hr_images, lr_images, who, keep_tensors=False):
     return _check_paired(*(_u8_stack(images, 4, f"{who} expects uint8 images [N, C, H, W]", keep_tensors) for images in (hr_images, lr_images)))
 
@@ -446,11 +456,20 @@ class PairedArrayDataset(_ItemProtocol):
     without the files -- its defaults (``val_split=1``: every item is a validation item; ``split_seed=None``: the last images), its
     attribute protocol and its item geometry (``_transform_pair``), for ``train_crappifier``, ``approximate_crappifier``,
     ``test_metrics`` and ``predict_images(norm=True)``.  Every pair is one item: with ``n_frames=[lr, hr]`` of different lengths the
-    centre frames of the two stacks are taken, as ``_transform_pair`` does."""
+    centre frames of the two stacks are taken, as ``_transform_pair`` does.
+
+    ``register=R`` (keyword-only, not in the reference; also on ``PairedImageDataset`` and ``DevicePairedTileDataset``): the two sides are
+    separate acquisitions a few HR pixels apart, so ``util.register_pairs(radius=R)`` runs once over the whole stacks at construction
+    (it needs a HIP device), the class holds the aligned stacks without their margin, and ``shifts`` [N, 2] / ``scores`` [N] say what was
+    found.  ``None``: the stacks as they came."""
 
     def __init__(self, hr_images, lr_images, hr_res=512, lr_scale=4, n_frames=-1, val_split=1, rotation=True, split_seed=None,
-                 transforms=None, names=None):
+                 transforms=None, names=None, *, register=None):
+        _check_register(register, type(self).__name__)
         self.hr_images, self.lr_images = _paired_stacks(hr_images, lr_images, type(self).__name__, self._keep_tensors)
+        self.shifts = self.scores = None
+        if register is not None:
+            self._register(register)
         self.n_frames = _get_n_frames(n_frames)
         self.slices = [1] * len(self.hr_images)
         self.val_idx = _get_val_idx(self.slices, val_split, split_seed)
@@ -459,6 +478,12 @@ class PairedArrayDataset(_ItemProtocol):
         self._set_protocol(hr_res, lr_scale, rotation, transforms, names, "image", len(self.hr_images))
 
     __len__ = ArrayDataset.__len__
+
+    def _register(self, radius):
+        """``register=radius``: the stacks become the aligned, cropped stacks of one ``util.register_pairs`` call over all of them."""
+        from .util import register_pairs
+        reg = register_pairs(self.hr_images, self.lr_images, radius=radius, to_numpy=not self._keep_tensors)
+        self.hr_images, self.lr_images, self.shifts, self.scores = reg.hr, reg.lr, reg.shift, reg.score
 
     def _item(self, idx, rot):
         return _transform_pair(self.hr_images[idx], self.lr_images[idx], self.hr_res, self.hr_res // self.lr_scale, rot, self.transforms,
@@ -477,7 +502,8 @@ class PairedImageDataset(PairedArrayDataset):
     sliced into several items per file and sheets are outside this build's scope."""
 
     def __init__(self, hr_path, lr_path, hr_res=512, lr_scale=4, n_frames=-1, extension="tif", val_split=1, rotation=True,
-                 split_seed=None, transforms=None):
+                 split_seed=None, transforms=None, *, register=None):
+        _check_register(register, type(self).__name__)
         (self.hr_path, self.hr_files), (self.lr_path, self.lr_files) = _find_paired_files(hr_path, lr_path, extension, "ImageDataset")
         sides = []
         for path, files in ((self.hr_path, self.hr_files), (self.lr_path, self.lr_files)):
@@ -485,7 +511,8 @@ class PairedImageDataset(PairedArrayDataset):
             if len({st.shape for st in stacks}) != 1:
                 raise ValueError(f'pssr2_amd.PairedImageDataset needs equally sized images in "{path}"')
             sides.append(np.stack(stacks))
-        super().__init__(*sides, hr_res, lr_scale, n_frames, val_split, rotation, split_seed, transforms, _file_names(self.lr_files))
+        super().__init__(*sides, hr_res, lr_scale, n_frames, val_split, rotation, split_seed, transforms, _file_names(self.lr_files),
+                         register=register)
         self.mode = "L"
 
     def _summary(self):
@@ -963,14 +990,19 @@ class DevicePairedTileDataset(_DevicePairs, PairedArrayDataset):
     ``draw_items`` / ``device_batch``: the hipGraph replay of ``train_paired`` (pssr2_amd/fastpath.py) does not cover real pairs."""
 
     def __init__(self, hr_images, lr_images, hr_res=512, lr_scale=4, n_frames=-1, val_split=1, rotation=True, split_seed=None,
-                 transforms=None, names=None, device="cuda"):
+                 transforms=None, names=None, device="cuda", *, register=None):
         self._no_transforms(transforms)
-        super().__init__(hr_images, lr_images, hr_res, lr_scale, n_frames, val_split, rotation, split_seed, None, names)
+        self._device = device           # where ``register=`` aligns the stacks, before the class holds them
+        super().__init__(hr_images, lr_images, hr_res, lr_scale, n_frames, val_split, rotation, split_seed, None, names, register=register)
         self.hr_images = torch.as_tensor(self.hr_images).to(device).contiguous()
         self.lr_images = torch.as_tensor(self.lr_images).to(device).contiguous()
         if not self.hr_images.is_cuda:
             raise RuntimeError("DevicePairedTileDataset keeps its images on an MI355X (HIP) device; there is no CPU fallback")
         self.depths = (self.hr_images.shape[1], self.lr_images.shape[1])
+
+    def _register(self, radius):
+        self.hr_images, self.lr_images = (torch.as_tensor(x).to(self._device) for x in (self.hr_images, self.lr_images))
+        super()._register(radius)
 
     def draw_pair_items(self, indices, pp=False):
         """(HR table, LR table) for these dataset indices: the training rotations are drawn exactly as ``__getitem__`` would draw them

@@ -1128,3 +1128,68 @@ def consistency_map_u8(d, l, lut):
     L.check(lib.pssr_consistency_map_u8(L.ptr(d), L.ptr(l), L.ptr(lut), L.ptr(out), L.ptr(sse), planes, pixels, L.ptr(ws), L.stream_ptr()),
             "pssr_consistency_map_u8")
     return out, sse
+
+
+# ----------------------------------------------------------------------------------------------
+# registration of real (HR, LR) pairs (csrc/register.hip; definitions in include/pssr_mi355.h)
+MAX_REGISTER_RADIUS = 32
+
+
+def register_margin(s, radius):
+    """LR pixels a registration at scale ``s`` and ``radius`` HR pixels drops on every side: ``1 + ceil(radius / s)``."""
+    return 1 + -(-radius // s)
+
+
+def register_shifts_u8(hr, lr, radius):
+    """uint8 device tensors ``hr`` [..., s*h, s*w] and ``lr`` [..., h, w], the same leading dimensions, ``s`` an integer in 1 .. 16, and a
+    search radius of 0 .. 32 HR pixels -> int64 [planes, 3 T + 2], ``T = (2 radius + 1)**2``: per plane and shift ``(ty, tx)`` (row
+    ``(ty + radius) (2 radius + 1) + tx + radius``) the exact ``sum D, sum D*D, sum D*Lc`` of the Pillow-bilinear reduction ``D`` of ``hr``
+    sampled at that shift against ``Lc = lr[m:h-m, m:w-m]``, ``m = register_margin(s, radius)``, then ``sum Lc, sum Lc*Lc``.  One fused
+    pass over ``hr``."""
+    if hr.dtype != torch.uint8 or lr.dtype != torch.uint8 or not (hr.is_cuda and lr.is_cuda) or hr.dim() < 2 or hr.dim() != lr.dim() \
+            or hr.shape[:-2] != lr.shape[:-2]:
+        raise ValueError("register_shifts_u8 needs two uint8 device tensors [..., s*h, s*w] and [..., h, w] with the same leading dimensions")
+    (H, W), (h, w) = hr.shape[-2:], lr.shape[-2:]
+    s = H // h if h else 0
+    if h < 1 or w < 1 or not 1 <= s <= 16 or H != s * h or W != s * w:
+        raise ValueError(f"register_shifts_u8: a {H}x{W} HR image is no integer multiple (1 .. 16) of the {h}x{w} LR image")
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= MAX_REGISTER_RADIUS:
+        raise ValueError(f"register_shifts_u8: the radius must be an int in 0 .. {MAX_REGISTER_RADIUS} HR pixels. Given {radius!r}.")
+    m = register_margin(s, radius)
+    if h - 2 * m < 1 or w - 2 * m < 1:
+        raise ValueError(f"register_shifts_u8: a {h}x{w} LR image leaves nothing inside the margin of {m} pixels on every side")
+    if h * w > 1 << 28:
+        raise ValueError(f"register_shifts_u8: {h * w} pixels per LR plane (at most 2**28)")
+    hr, lr = hr.contiguous(), lr.contiguous()
+    planes = lr.numel() // (h * w)
+    if planes < 1:
+        raise ValueError("register_shifts_u8: no planes")
+    lib = L.lib()
+    ws = torch.empty(lib.pssr_register_shifts_workspace_bytes(planes, h, w, s, radius), dtype=torch.uint8, device=hr.device)
+    sums = torch.empty(planes, 3 * (2 * radius + 1) ** 2 + 2, dtype=torch.int64, device=hr.device)
+    L.check(lib.pssr_register_shifts_u8(L.ptr(hr), L.ptr(lr), L.ptr(sums), planes, h, w, s, radius, L.ptr(ws), L.stream_ptr()),
+            "pssr_register_shifts_u8")
+    return sums
+
+
+def crop_shift_u8(x, origins, ho, wo, *, table=None):
+    """uint8 device tensor ``x`` [..., H, W] and one origin ``(y0, x0)`` per plane (``origins``: host ints [planes, 2], checked here:
+    a window must lie inside its plane) -> uint8 [..., ho, wo], ``x[p][y0:y0+ho, x0:x0+wo]``.  ``table``: an int32 device tensor
+    [planes, 2] that already holds ``origins`` (a caller that crops several tensors uploads one table and passes its rows)."""
+    if x.dtype != torch.uint8 or not x.is_cuda or x.dim() < 2:
+        raise ValueError("crop_shift_u8 needs a uint8 device tensor [..., H, W]")
+    H, W = x.shape[-2:]
+    planes = x.numel() // (H * W) if H * W else 0
+    if planes < 1 or not (1 <= ho <= H and 1 <= wo <= W):
+        raise ValueError(f"crop_shift_u8: {planes} planes, a {ho}x{wo} window of a {H}x{W} plane")
+    rows = [(int(y0), int(x0)) for y0, x0 in (origins.tolist() if hasattr(origins, "tolist") else origins)]
+    if len(rows) != planes or any(not (0 <= y0 <= H - ho and 0 <= x0 <= W - wo) for y0, x0 in rows):
+        raise ValueError(f"crop_shift_u8 needs {planes} origins (y0, x0) with 0 <= y0 <= {H - ho} and 0 <= x0 <= {W - wo}")
+    if table is None:
+        table = torch.tensor(rows, dtype=torch.int32).to(x.device)
+    elif table.dtype != torch.int32 or not table.is_cuda or tuple(table.shape) != (planes, 2) or not table.is_contiguous():
+        raise ValueError(f"crop_shift_u8: table must be a contiguous int32 device tensor [{planes}, 2]")
+    x = x.contiguous()
+    out = torch.empty(*x.shape[:-2], ho, wo, dtype=torch.uint8, device=x.device)
+    L.check(L.lib().pssr_crop_shift_u8(L.ptr(x), L.ptr(out), L.ptr(table), planes, H, W, ho, wo, L.stream_ptr()), "pssr_crop_shift_u8")
+    return out

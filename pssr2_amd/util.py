@@ -366,6 +366,112 @@ def consistency_map(lr, hr_hat, *, fit: str = "affine", to_numpy: bool = True):
     return Consistency(cmap.cpu().numpy() if to_numpy else cmap, stats[0], stats[1], rse, stats[2])
 
 
+Registration = namedtuple("Registration", "hr lr shift score margin")
+
+
+def _check_radius(radius, what="radius"):
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= ops.MAX_REGISTER_RADIUS:
+        raise ValueError(f"{what} must be an int from 0 to {ops.MAX_REGISTER_RADIUS} (the search radius in HR pixels). Given {radius!r}.")
+    return int(radius)
+
+
+def _register_choose(n: int, rows, radius: int):
+    """``((ty, tx), score)`` of one item from the exact sums of its matched planes (``rows``: one list of ``3 T + 2`` ints per plane, the
+    layout of ``pssr_register_shifts_u8``) over ``n`` pixels in all, in exactly the expressions of include/pssr_mi355.h: the planes' sums
+    add, the score of a shift is the signed squared Pearson correlation ``num |num| / (den denl)`` (0 when ``den`` or ``denl`` is 0),
+    compared by cross-multiplying Python ints; ties go to the smaller ``ty**2 + tx**2``, then ``ty``, then ``tx``."""
+    side = 2 * radius + 1
+    pooled = [sum(int(v) for v in col) for col in zip(*rows)]
+    sl, sll = pooled[3 * side * side], pooled[3 * side * side + 1]
+    denl = n * sll - sl * sl
+    best = None                                         # (p, q): the score p / (q denl), q > 0; then the tie key, num and den
+    for t in range(side * side):
+        sd, sdd, sdl = pooled[3 * t:3 * t + 3]
+        ty, tx = t // side - radius, t % side - radius
+        num, den = n * sdl - sd * sl, n * sdd - sd * sd
+        p, q = (num * abs(num), den) if den > 0 and denl > 0 else (0, 1)
+        key = (ty * ty + tx * tx, ty, tx)
+        if best is None or p * best[1] > best[0] * q or (p * best[1] == best[0] * q and key < best[2]):
+            best = (p, q, key, num, den)
+    _, _, key, num, den = best
+    return (key[1], key[2]), (num / math.sqrt(den * denl) if den > 0 and denl > 0 else 0.0)
+
+
+def register_pairs(hr, lr, *, radius: int = 8, to_numpy: bool = True):
+    r"""Aligns real (HR, LR) pairs -- two acquisitions of one field of view, a few HR pixels apart by stage drift and scan offset -- by an
+    exhaustive search over integer shifts under this package's forward model (``_gen_pair``'s Pillow-bilinear reduction).  ``hr``: uint8
+    array or device tensor [N, C, s*h, s*w]; ``lr``: uint8 [N, c, h, w], ``s`` an integer in 1 .. 16 inferred from the sizes (or both 3-D,
+    without the batch axis).  Frame ``j`` of ``hr`` meets frame ``j`` of the ``C`` centre frames of ``lr`` (``_slice_center``, the rule of
+    ``n_frames=[lr, hr]``).  For every shift ``(ty, tx)`` of at most ``radius`` HR pixels (0 .. 32) the HR item, moved by the shift and
+    reduced to the LR grid, is correlated with the LR item inside a margin of ``m = 1 + ceil(radius / s)`` LR pixels; the shift with the
+    largest signed squared Pearson correlation wins, one shift per item (its planes pool their sums; include/pssr_mi355.h has the
+    definitions, exact integers throughout).  Returns ``Registration(hr, lr, shift, score, margin)``:
+
+    * ``lr``: uint8 [N, c, h - 2m, w - 2m], every LR frame without the margin; ``hr``: uint8 [N, C, s (h - 2m), s (w - 2m)], the window of
+      the HR item that shows the same field of view;
+    * ``shift``: int [N, 2], ``(ty, tx)`` in HR pixels: ``hr_out = hr[..., s m + ty : s (h - m) + ty, s m + tx : s (w - m) + tx]``;
+    * ``score``: float [N], the Pearson correlation at the chosen shift; ``margin``: ``m``.
+
+    One sums launch (``pssr_register_shifts_u8``), one copy of the sums to the host, the choice in Python ints, one origin upload and two
+    crop launches (``pssr_crop_shift_u8``).  A chosen ``|ty|`` or ``|tx|`` equal to ``radius > 0`` emits a ``UserWarning`` naming the
+    items: the optimum may then lie outside the window.  ``to_numpy=False`` leaves ``hr`` and ``lr`` in HBM.  ``s = 1`` is taken, so a
+    prediction can be aligned to its ground truth."""
+    import warnings
+    radius = _check_radius(radius)
+    tensors = []
+    for name, t in (("hr", hr), ("lr", lr)):
+        if not torch.is_tensor(t):
+            t = torch.as_tensor(np.ascontiguousarray(t))
+        elif not t.is_cuda:
+            raise RuntimeError("pssr2_amd.util.register_pairs runs on an MI355X (HIP) device only; there is no CPU fallback")
+        if t.dtype != torch.uint8:
+            raise TypeError(f"register_pairs takes uint8 images; {name} is {t.dtype}")
+        tensors.append(t)
+    hr, lr = tensors
+    if hr.dim() != lr.dim() or hr.dim() not in (3, 4):
+        raise ValueError(f"hr and lr must both be [N, C, H, W] / [N, c, h, w] or both 3-D without the batch axis. Shapes are "
+                         f"{tuple(hr.shape)} and {tuple(lr.shape)} respectively.")
+    batched = hr.dim() == 4
+    if not batched:
+        hr, lr = hr[None], lr[None]
+    (n_img, C, H, W), (n_lr, c, h, w) = hr.shape, lr.shape
+    if n_img != n_lr:
+        raise ValueError(f"hr and lr must have the same number of images. Received {n_img} and {n_lr} images respectively.")
+    if C > c:
+        raise ValueError(f"An HR item of {C} frames cannot be matched with an LR item of {c} frames.")
+    scale = H // h if h else 0
+    if min(n_img, C, h, w) < 1 or not 1 <= scale <= 16 or H != scale * h or W != scale * w:
+        raise ValueError(f"The HR size must be one integer multiple (1 to 16) of the LR size along both axes. Sizes are {H}x{W} and {h}x{w} respectively.")
+    m = ops.register_margin(scale, radius)
+    hc, wc = h - 2 * m, w - 2 * m
+    if hc < 1 or wc < 1:
+        raise ValueError(f"An LR image of {h}x{w} leaves nothing inside the margin of {m} pixels that radius={radius} at scale {scale} needs on every side.")
+    if h * w > 1 << 28:
+        raise ValueError(f"An LR plane of {h * w} pixels is above the 2**28 up to which the sums are exact.")
+    if not (hr.is_cuda or lr.is_cuda or torch.cuda.is_available()):
+        raise RuntimeError("pssr2_amd.util.register_pairs needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
+    from .data import _slice_center
+    dev = hr.device if hr.is_cuda else (lr.device if lr.is_cuda else "cuda")
+    hr, lr = hr.to(dev).contiguous(), lr.to(dev).contiguous()
+    sums = ops.register_shifts_u8(hr, _slice_center(lr, C).contiguous(), radius).cpu().tolist()
+    chosen = [_register_choose(C * hc * wc, sums[i * C:(i + 1) * C], radius) for i in range(n_img)]
+    edge = [i for i, ((ty, tx), _) in enumerate(chosen) if radius > 0 and max(abs(ty), abs(tx)) == radius]
+    if edge:
+        warnings.warn(f"register_pairs: the chosen shift of item(s) {edge} lies on the edge of the search window (radius={radius}); the optimum "
+                      "may lie outside it", UserWarning, stacklevel=2)
+    origins = [(scale * m + ty, scale * m + tx) for (ty, tx), _ in chosen for _ in range(C)] + [(m, m)] * (n_img * c)
+    table = torch.tensor(origins, dtype=torch.int32).to(dev)
+    hr_out = ops.crop_shift_u8(hr, origins[:n_img * C], scale * hc, scale * wc, table=table[:n_img * C])
+    lr_out = ops.crop_shift_u8(lr, origins[n_img * C:], hc, wc, table=table[n_img * C:])
+    shift = np.array([sh for sh, _ in chosen], dtype=np.int64).reshape(n_img, 2)
+    score = np.array([sc for _, sc in chosen], dtype=np.float64)
+    if not batched:
+        hr_out, lr_out, shift, score = hr_out[0], lr_out[0], shift[0], score[0]
+    if to_numpy:
+        hr_out, lr_out = hr_out.cpu().numpy(), lr_out.cpu().numpy()
+    return Registration(hr_out, lr_out, shift, score, m)
+
+
 def _sort_tiles(name: str):
     """Sort key of tile names ``{sheet}_{tile}_{slice}[.ext]`` (pssr/util.py:110-114): slice first, then tile."""
     if "." not in name:
