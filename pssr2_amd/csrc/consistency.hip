@@ -12,9 +12,10 @@
 // outputs at a time.  For an integer ratio the window of output i is [i s - s/2, i s - s/2 + 2 s) clipped to the image, so a block
 // reads at most 33 s rows x 33 s columns of Y: its own 32 s and a halo of s.  It
 //   1. takes its column's taps into registers (thread t: column t & 31) and the 32 rows' taps into LDS,
-//   2. stages Y in strips of raw rows -- about 22 KB of LDS: all 33 s rows of the block for s <= 4 -- as whole aligned 16-byte pieces
-//      where the buffer has them (else bytes); a thread issues all its loads of a strip (and of its four L bytes) before it waits,
-//      so that a workgroup has ~20 KB in flight (with one dword per lane and 16 rows per step the kernel was latency-bound),
+//   2. stages Y in strips of raw rows -- about 22 KB of LDS: all 33 s rows of the block for s <= 4 -- with stage_rows_u8 of
+//      u8_planes.h: whole aligned 16-byte pieces where the buffer has them (else bytes); a thread issues all its loads of a strip (and
+//      of its four L bytes) before it waits, so that a workgroup has ~20 KB in flight (with one dword per lane and 16 rows per step
+//      the kernel was latency-bound),
 //   3. reduces every staged row horizontally into an LDS array [33 s][32] of bytes (clip8 between the passes, as Pillow),
 //   4. runs the vertical pass on that array: a thread's four outputs (rows t >> 5, + 8, + 16, + 24) are stored to D, paired with
 //      L and fed to 32-bit partial sums, which 64-bit accumulators take over after every block of outputs.
@@ -22,25 +23,23 @@
 // reduction never leaves LDS.  Windows are never assumed: the block's raw range is read from the tap table and clamped to the LDS
 // arrays, taps beyond a window are zero.
 //
-// Determinism: integers only.  A wave's shuffle tree and the four waves' LDS sums give one row of 64-bit partials per workgroup
-// and plane in the workspace; fold_u64_kernel (a second launch) adds them.  No atomics, no fence, no floating-point sum: the same
-// bits on every run, whatever the order.
+// Determinism: integers only.  A wave's shuffle tree and the four waves' LDS sums (block_sum_u64) give one row of 64-bit partials per
+// workgroup and plane in the workspace; fold_u64_kernel<1> (a second launch, one workgroup per value and plane) adds them.  No atomics,
+// no fence, no floating-point sum: the same bits on every run, whatever the order.
+//
+// The argument checks of a plane pair, the workgroups per plane and their runs of blocks, the staging, the workgroup sum and the fold are
+// u8_planes.h's, shared with register.hip.
 //
 // consistency_map_kernel: grid (blocks, planes), block 256, the plane's 256-entry table in LDS; 16 pixels per lane and step with
 // 16-byte loads / stores where size and pointers allow, else one.  e < 2^18, so e^2 needs the 64-bit accumulator from the start.
-#include "common.h"
-#include "pil_taps.h"
+#include "u8_planes.h"
 
 namespace {
 
 constexpr int RM_TILE = 32;                 // outputs per block and axis
 constexpr int RM_RAW_BYTES = 22 * 1024;     // LDS for the raw rows staged per step
 constexpr int RM_TAP_STRIDE = 2 + 32;       // ints per tap-table entry: xmin, n, k[32]
-constexpr int RM_PLANES_CAP = 1024;         // grid.y of both kernels (planes beyond it: stride loop)
-constexpr int RM_BLOCKS = 4096;             // workgroups a launch aims at (about two waves of 8 per CU)
 constexpr int CM_VEC = 16;
-
-typedef unsigned long long u64;
 
 // entry i of `tab`: the taps of output i of an axis of `out_size` outputs reduced from `in_size` inputs
 __global__ void reduce_taps_kernel(int* __restrict__ tab_x, int* __restrict__ tab_y, int W, int w, int H, int h) {
@@ -52,16 +51,6 @@ __global__ void reduce_taps_kernel(int* __restrict__ tab_x, int* __restrict__ ta
     const int n = t.n < 32 ? t.n : 32;
     e[0] = t.xmin; e[1] = n;
     for (int k = 0; k < 32; ++k) e[2 + k] = k < n ? t.k[k] : 0;
-}
-
-// sum of v over the workgroup's 256 threads, valid in thread 0: fixed shuffle tree per wave, waves in order
-__device__ __forceinline__ u64 block_sum_u64(u64 v, u64* red4) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const u64 r = (red4[0] + red4[1]) + (red4[2] + red4[3]);
-    __syncthreads();
-    return r;
 }
 
 template <int MAXT>
@@ -86,12 +75,8 @@ __global__ __launch_bounds__(256) void reduce_moments_kernel(const uint8_t* __re
     const uintptr_t ybase = (uintptr_t)y;
     for (int pl = blockIdx.y; pl < planes; pl += gridDim.y) {
         u64 acc[5] = {0, 0, 0, 0, 0};
-        // a workgroup walks a run of neighbouring blocks of outputs along x: the raw window of a block starts s/2 bytes before a
-        // 32 s-byte boundary, so its rows touch a cache line of each neighbour, which a run can find in this XCD's L2 (against blocks
-        // dealt out with a grid stride it measured the same at s = 4, where the kernel is not bound by HBM; the order costs nothing)
-        const int run = (tiles + (int)gridDim.x - 1) / (int)gridDim.x;
-        const int tile_end = (int)(blockIdx.x + 1) * run < tiles ? (int)(blockIdx.x + 1) * run : tiles;
-        for (int tile = blockIdx.x * run; tile < tile_end; ++tile) {
+        const TileRun mine = my_tile_run(tiles);
+        for (int tile = mine.begin; tile < mine.end; ++tile) {
             const int ty0 = tile / tiles_x * RM_TILE, tx0 = tile % tiles_x * RM_TILE;
             const int ncol = w - tx0 < RM_TILE ? w - tx0 : RM_TILE, nrow = h - ty0 < RM_TILE ? h - ty0 : RM_TILE;
             // the raw range of this block, from the table (never assumed), clamped to what the LDS arrays hold
@@ -123,48 +108,21 @@ __global__ __launch_bounds__(256) void reduce_moments_kernel(const uint8_t* __re
                 lv[q] = ry < nrow && c < ncol ? l[((long)pl * h + ty0 + ry) * w + tx0 + c] : 0;
             }
             for (int y0 = 0; y0 < yspan; y0 += STRIP) {
-                // every 16-byte piece of the strip this thread stages: all loads first, then the LDS stores
-                uint4 v[ITERS];
-#pragma unroll
-                for (int it = 0; it < ITERS; ++it) {
-                    const int idx = tid + 256 * it, r = idx / ROWQ, j = idx % ROWQ;
-                    v[it] = make_uint4(0, 0, 0, 0);
-                    if (idx < STRIP * ROWQ && y0 + r < yspan) {
-                        const long row = rowbase + (long)(y0 + r) * W;
-                        const int shift = (base15 + (y0 + r) * w15) & 15;
-                        const long g = row - shift + 16 * j;              // an aligned piece; whole inside the buffer?
-                        if (16 * j < shift + xspan && g >= 0 && g + 16 <= total) v[it] = *reinterpret_cast<const uint4*>(y + g);
-                    }
-                }
-                if (y0 == 0 && tid < RM_TILE) {
-                    int yoff = 0, yn = 0;
-                    const int* e = tab_y + (long)(ty0 + (tid < nrow ? tid : 0)) * RM_TAP_STRIDE;
-                    if (tid < nrow) {
-                        yoff = e[0] - ylo; yn = e[1] < MAXT ? e[1] : MAXT;
-                        if (yoff < 0 || yoff > yspan) { yoff = 0; yn = 0; }
-                        if (yoff + yn > yspan) yn = yspan - yoff;
-                    }
-                    yoff_s[tid] = yoff;
-                    for (int k = 0; k < MAXT; ++k) ky[tid][k] = k < yn ? e[2 + k] : 0;
-                }
-#pragma unroll
-                for (int it = 0; it < ITERS; ++it) {
-                    const int idx = tid + 256 * it, r = idx / ROWQ, j = idx % ROWQ;
-                    if (idx < STRIP * ROWQ && y0 + r < yspan) {
-                        const long row = rowbase + (long)(y0 + r) * W;
-                        const int shift = (base15 + (y0 + r) * w15) & 15;
-                        const long g = row - shift + 16 * j;
-                        if (16 * j < shift + xspan) {
-                            if (!(g >= 0 && g + 16 <= total)) {           // the buffer's first or last piece: byte by byte
-                                uint32_t p[4] = {0, 0, 0, 0};
-                                for (int b = 0; b < 16; ++b)
-                                    if (g + b >= 0 && g + b < total) p[b >> 2] |= (uint32_t)y[g + b] << (8 * (b & 3));
-                                v[it] = make_uint4(p[0], p[1], p[2], p[3]);
-                            }
-                            *reinterpret_cast<uint4*>(&raw[r][16 * j]) = v[it];
+                // the strip's raw rows, every piece of them in one round; the rows' taps go to LDS while the loads are in flight
+                const int nstrip = yspan - y0 < STRIP ? yspan - y0 : STRIP;
+                stage_rows_u8<ITERS>(y, total, rowbase, W, base15, w15, y0, nstrip, xspan, &raw[0][0], ROWB, 0, [&] {
+                    if (y0 == 0 && tid < RM_TILE) {
+                        int yoff = 0, yn = 0;
+                        const int* e = tab_y + (long)(ty0 + (tid < nrow ? tid : 0)) * RM_TAP_STRIDE;
+                        if (tid < nrow) {
+                            yoff = e[0] - ylo; yn = e[1] < MAXT ? e[1] : MAXT;
+                            if (yoff < 0 || yoff > yspan) { yoff = 0; yn = 0; }
+                            if (yoff + yn > yspan) yn = yspan - yoff;
                         }
+                        yoff_s[tid] = yoff;
+                        for (int k = 0; k < MAXT; ++k) ky[tid][k] = k < yn ? e[2 + k] : 0;
                     }
-                }
+                });
                 __syncthreads();
                 // read and multiply without a branch (a row beyond the strip's end is inside `raw`, its result is dropped), so that
                 // several rows' LDS reads are in flight; 24-bit multiplies: a tap is at most 2^22, a byte 255
@@ -218,18 +176,6 @@ __global__ __launch_bounds__(256) void reduce_moments_kernel(const uint8_t* __re
     }
 }
 
-// out[pl][q] = sum_g partial[pl][g][q]: one workgroup per plane (stride loop), k values per row
-__global__ __launch_bounds__(256) void fold_u64_kernel(const u64* __restrict__ partial, u64* __restrict__ out, int planes, int rows, int k) {
-    __shared__ u64 red4[4];
-    for (int pl = blockIdx.x; pl < planes; pl += gridDim.x)
-        for (int q = 0; q < k; ++q) {
-            u64 s = 0;
-            for (int g = threadIdx.x; g < rows; g += 256) s += partial[((long)pl * rows + g) * k + q];
-            s = block_sum_u64(s, red4);
-            if (threadIdx.x == 0) out[(long)pl * k + q] = s;
-        }
-}
-
 __device__ __forceinline__ uint32_t map_pixel(const int* P, uint32_t dv, uint32_t lv, u64& acc) {
     const int v = (int)(lv << 8) - P[dv];
     const uint32_t e = (uint32_t)(v < 0 ? -v : v);
@@ -273,23 +219,13 @@ __global__ __launch_bounds__(256) void consistency_map_kernel(const uint8_t* __r
     }
 }
 
-// workgroups per plane: enough to fill the part when there are few planes, never more than the plane has pieces of work
-int blocks_per_plane(int planes, long pieces) {
-    const int gy = planes < RM_PLANES_CAP ? planes : RM_PLANES_CAP;
-    long want = (RM_BLOCKS + gy - 1) / gy;
-    if (want > pieces) want = pieces;
-    return (int)(want < 1 ? 1 : want);
-}
 long rm_tiles(int h, int w) { return (long)cdiv(h, RM_TILE) * cdiv(w, RM_TILE); }
-bool rm_args_ok(int planes, int h, int w, int s) {
-    return planes > 0 && h > 0 && w > 0 && s >= 1 && s <= 16 && (long)h * s < (1L << 30) && (long)w * s < (1L << 30) && (long)h * w <= (1L << 28);
-}
 long cm_pieces(long pixels) { return (pixels + 256 * CM_VEC - 1) / (256 * CM_VEC); }
 
 }  // namespace
 
 extern "C" int64_t pssr_reduce_moments_workspace_bytes(int planes, int h, int w, int s) {
-    if (!rm_args_ok(planes, h, w, s)) return 0;
+    if (!u8_pair_ok(planes, h, w, s)) return 0;
     const int64_t part = (int64_t)planes * blocks_per_plane(planes, rm_tiles(h, w)) * 5 * (int64_t)sizeof(u64);
     return part + ((int64_t)w + h) * RM_TAP_STRIDE * (int64_t)sizeof(int);
 }
@@ -297,14 +233,10 @@ extern "C" int64_t pssr_reduce_moments_workspace_bytes(int planes, int h, int w,
 extern "C" int pssr_reduce_moments_u8(const uint8_t* y, const uint8_t* l, uint8_t* d, uint64_t* sums, int planes, int h, int w, int s,
                                       void* workspace, pssr_stream_t stream) {
     PSSR_CHECK(y && l && d && sums && workspace, PSSR_ERR_ARG, "reduce_moments_u8: null pointer");
-    PSSR_CHECK(planes > 0 && h > 0 && w > 0, PSSR_ERR_ARG, "reduce_moments_u8: planes, h and w must be positive (%d, %d, %d)", planes, h, w);
-    PSSR_CHECK(s >= 1 && s <= 16, PSSR_ERR_ARG, "reduce_moments_u8: the scale must be an integer in 1 .. 16, given %d", s);
-    PSSR_CHECK((long)h * w <= (1L << 28), PSSR_ERR_ARG, "reduce_moments_u8: %ld pixels per reduced plane (at most 2^28: the sums are exact up to there)",
-               (long)h * w);
-    PSSR_CHECK(rm_args_ok(planes, h, w, s), PSSR_ERR_ARG, "reduce_moments_u8: a %d x %d plane at scale %d has an axis of 2^30 or more", h, w, s);
+    if (const int status = u8_pair_check("reduce_moments_u8", planes, h, w, s)) return status;
     const int H = h * s, W = w * s;
     const long tiles = rm_tiles(h, w);
-    const int gx = blocks_per_plane(planes, tiles), gy = planes < RM_PLANES_CAP ? planes : RM_PLANES_CAP;
+    const int gx = blocks_per_plane(planes, tiles), gy = planes_grid_y(planes);
     u64* partial = (u64*)workspace;
     int* tab_x = (int*)(partial + (long)planes * gx * 5);
     int* tab_y = tab_x + (long)w * RM_TAP_STRIDE;
@@ -322,7 +254,7 @@ extern "C" int pssr_reduce_moments_u8(const uint8_t* y, const uint8_t* l, uint8_
     else RM_LAUNCH(32);
 #undef RM_LAUNCH
     PSSR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fold_u64_kernel, dim3(planes < 4096 ? planes : 4096), dim3(256), 0, st, (const u64*)partial, (u64*)sums, planes, gx, 5);
+    launch_fold_u64<1>(partial, (u64*)sums, planes, gx, 5, st);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -338,7 +270,7 @@ extern "C" int pssr_consistency_map_u8(const uint8_t* d, const uint8_t* l, const
     PSSR_CHECK(planes > 0 && pixels > 0, PSSR_ERR_ARG, "consistency_map_u8: planes and pixels must be positive (%d, %ld)", planes, (long)pixels);
     PSSR_CHECK(pixels <= (1L << 28), PSSR_ERR_ARG, "consistency_map_u8: %ld pixels per plane (at most 2^28: the squared-error sum is exact up to there)",
                (long)pixels);
-    const int gx = blocks_per_plane(planes, cm_pieces((long)pixels)), gy = planes < RM_PLANES_CAP ? planes : RM_PLANES_CAP;
+    const int gx = blocks_per_plane(planes, cm_pieces((long)pixels)), gy = planes_grid_y(planes);
     const bool vec = pixels % CM_VEC == 0 && (uintptr_t)d % 16 == 0 && (uintptr_t)l % 16 == 0 && (uintptr_t)map % 16 == 0;
     hipStream_t st = (hipStream_t)stream;
     if (vec)
@@ -346,7 +278,7 @@ extern "C" int pssr_consistency_map_u8(const uint8_t* d, const uint8_t* l, const
     else
         hipLaunchKernelGGL(consistency_map_kernel<false>, dim3(gx, gy), dim3(256), 0, st, d, l, (const int*)lut, map, (u64*)workspace, planes, (long)pixels);
     PSSR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fold_u64_kernel, dim3(planes < 4096 ? planes : 4096), dim3(256), 0, st, (const u64*)workspace, (u64*)sse, planes, gx, 1);
+    launch_fold_u64<1>((const u64*)workspace, (u64*)sse, planes, gx, 1, st);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }

@@ -1,5 +1,6 @@
 // Pillow's 8-bit-per-channel resampling taps (ImagingResample, BILINEAR), the one copy shared by the two-launch reduction of
-// crappify.hip (pssr_bilinear_down_u8) and the fused reduction + moments of consistency.hip (pssr_reduce_moments_u8).
+// crappify.hip (pssr_bilinear_down_u8), the fused reduction + moments of consistency.hip (pssr_reduce_moments_u8) and the shift search of
+// register.hip (pssr_register_shifts_u8); the last two take it through u8_planes.h, which holds the steps they share beyond the taps.
 #pragma once
 #include "common.h"
 

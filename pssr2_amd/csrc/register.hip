@@ -11,11 +11,11 @@
 // register_shifts_kernel, grid (workgroups, planes), block 256, dynamic LDS.  "Filter H densely at every HR position, then sample that map
 // at stride s with offset t": a workgroup owns B x B outputs of the cropped LR grid at a time (B = 32 .. 4, the largest whose arrays
 // fit 60 KB of LDS, so that two or more workgroups share a CU).  It
-//   1. stages the raw HR bytes of the block -- (B-1) s + 2R + 2s rows and columns: the block, R on every side, the tap window -- as
-//      whole aligned 16-byte pieces where the buffer has them (else bytes), four pieces per thread in flight before the LDS stores,
-//      and the block's Lc bytes,
+//   1. stages the raw HR bytes of the block -- (B-1) s + 2R + 2s rows and columns: the block, R on every side, the tap window -- with
+//      stage_rows_u8 of u8_planes.h: whole aligned 16-byte pieces where the buffer has them (else bytes), four pieces per thread in
+//      flight before the LDS stores, and the block's Lc bytes,
 //   2. filters every staged row horizontally at every column position into `hbuf` (clip8), then `hbuf` vertically at every row position
-//      into the dense image (clip8), which takes the place of the raw bytes: (B-1) s + 2R + 1 positions a side,
+//      into the dense image (clip8), which takes the place of the raw bytes: (B-1) s + 2R + 1 positions a side (filter_pass, twice),
 //   3. gives each thread its own shifts (work item = shift; item T is "D = Lc" and yields sum Lc, sum Lc^2).  A thread walks the
 //      block's outputs, four of a row per step with all their LDS reads issued together (one read per step was bound by the LDS
 //      latency), reads dense[s y + ty + R][s x + tx + R] -- neighbouring lanes have neighbouring tx, so neighbouring bytes -- and
@@ -27,25 +27,24 @@
 //      thread does that itself).  No shuffle and no atomic anywhere.
 // H comes from HBM about once (the halo is shared with the neighbours through L2); neither intermediate leaves LDS.
 //
-// Determinism: integers only.  A slot of the partial rows is written by one thread only, in program order; register_fold_kernel (a
-// second small launch) adds the rows in a fixed order.  No atomics, no fence, no floating-point sum: the same bits on every run.
+// Determinism: integers only.  A slot of the partial rows is written by one thread only, in program order (slots_update);
+// fold_u64_kernel<16> (a second small launch: 16 values per workgroup, 16 threads share the rows of each) adds the rows.  No atomics, no
+// fence, no floating-point sum: the same bits on every run.
+//
+// The argument checks of a plane pair, the workgroups per plane and their runs of blocks, the staging and the fold are u8_planes.h's,
+// shared with consistency.hip.
 //
 // crop_shift_kernel: out[p] = in[p][y0 : y0 + ho, x0 : x0 + wo] with a per-plane origin table; 16 bytes per thread and step where the
 // output rows are whole 16-byte pieces (the input piece as one, four or sixteen loads, by its address), else one byte.
-#include "common.h"
-#include "pil_taps.h"
+#include "u8_planes.h"
 
 namespace {
 
 constexpr int RS_MAX_S = 16, RS_MAX_R = 32;
 constexpr int RS_LDS_BYTES = 60 * 1024;     // dynamic LDS a workgroup may take
-constexpr int RS_PLANES_CAP = 1024;         // grid.y (planes beyond it: stride loop)
-constexpr int RS_BLOCKS = 4096;             // workgroups a launch aims at
 constexpr long RS_PARTIAL_BYTES = 64L << 20; // partial rows a launch aims to stay below (fewer workgroups at large radii)
 constexpr int RS_MAX_SPLIT = 32;            // threads an item is split over at most (a block has at most 32 rows)
 constexpr int RS_STAGE = 4;                 // 16-byte pieces a thread has in flight
-
-typedef unsigned long long u64;
 
 // the LDS arrays of a block of B x B outputs (bytes; all offsets multiples of 16)
 struct RsLayout { int rn, rp, dp, off_hbuf, off_lc, bytes; };
@@ -87,12 +86,40 @@ __global__ void register_taps_kernel(int* __restrict__ ks, int s) {
     for (int k = 0; k < 2 * RS_MAX_S; ++k) ks[k] = k < t.n && k < 2 * s ? t.k[k] : 0;
 }
 
+// One pass of the `nt` taps `ks` at every position, a wave per row and a lane per column: dst[r][x] = clip8 of the taps on
+// src[r][x + k * kstride], k < nt, for r < ny and x < nx.  Row r of `src` starts at column (base15 + r * w15) & 15 of its pitch: the raw
+// rows as stage_rows_u8 leaves them, or 0, 0 for rows that start at column 0.
+__device__ __forceinline__ void filter_pass(const uint8_t* src, int spitch, int base15, int w15, int kstride, uint8_t* dst, int dpitch, int ny, int nx,
+                                            const int* ks, int nt) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = wave; r < ny; r += 4) {
+        const uint8_t* row = src + r * spitch + ((base15 + r * w15) & 15);
+        for (int x = lane; x < nx; x += 64) {
+            int a = 1 << (PRECISION_BITS - 1);
+            for (int k = 0; k < nt; ++k) a += __mul24((int)row[x + k * kstride], ks[k]);
+            dst[r * dpitch + x] = clip8(a);
+        }
+    }
+}
+
+// An item's sums of one block of outputs into its three slots of the workgroup's partial row: the first block of a run writes them, the
+// later ones add (a slot is written by one thread only, in program order).  The item "D = Lc" has no third slot.
+__device__ __forceinline__ void slots_update(u64* slot, bool first, bool third, u64 sd, u64 sdd, u64 sdl) {
+    if (first) {
+        slot[0] = sd; slot[1] = sdd;
+        if (third) slot[2] = sdl;
+    } else {
+        slot[0] += sd; slot[1] += sdd;
+        if (third) slot[2] += sdl;
+    }
+}
+
 __global__ __launch_bounds__(256) void register_shifts_kernel(const uint8_t* __restrict__ hr, const uint8_t* __restrict__ lr, u64* __restrict__ partial,
                                                               const int* __restrict__ taps, int planes, int h, int w, int s, int R, int B,
                                                               int G, int tiles_x, int tiles) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ int ks[2 * RS_MAX_S];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int m = 1 + (R + s - 1) / s, hc = h - 2 * m, wc = w - 2 * m;
     const int side = 2 * R + 1, T = side * side, nitems = T + 1, k3 = 3 * T + 2, nt = 2 * s;
     const int work = G * nitems;
@@ -106,13 +133,12 @@ __global__ __launch_bounds__(256) void register_shifts_kernel(const uint8_t* __r
     const long plane_in = (long)H * W, total = (long)planes * plane_in;
     const uintptr_t hbase = (uintptr_t)hr;
     if (tid < 2 * RS_MAX_S) ks[tid] = taps[tid];
-    const int run = (tiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int tile_begin = blockIdx.x * run, tile_end = tile_begin + run < tiles ? tile_begin + run : tiles;
+    const TileRun mine = my_tile_run(tiles);
     for (int pl = blockIdx.y; pl < planes; pl += gridDim.y) {
         u64* const prow = partial + ((long)pl * gridDim.x + blockIdx.x) * k3;
-        if (tile_begin >= tile_end)                 // a workgroup without a block of outputs: its row is zero
+        if (mine.begin >= mine.end)                 // a workgroup without a block of outputs: its row is zero
             for (int i = tid; i < k3; i += 256) prow[i] = 0;
-        for (int tile = tile_begin; tile < tile_end; ++tile) {
+        for (int tile = mine.begin; tile < mine.end; ++tile) {
             const int y0 = tile / tiles_x * B, x0 = tile % tiles_x * B;
             const int nrow = hc - y0 < B ? hc - y0 : B, ncol = wc - x0 < B ? wc - x0 : B;
             const int dny = (nrow - 1) * s + side, dnx = (ncol - 1) * s + side;          // dense positions
@@ -126,58 +152,17 @@ __global__ __launch_bounds__(256) void register_shifts_kernel(const uint8_t* __r
             // 1. the raw bytes, as aligned 16-byte pieces: row r lands at raw[r][0 ..] with its first byte at raw[r][shift_r]
             const long rowbase = (long)pl * plane_in + (long)yr * W + xr;
             const int base15 = (int)((hbase + (uintptr_t)rowbase) & 15), w15 = W & 15;
-            const int RQ = RP / 16, npieces = rny * RQ;
-            for (int p0 = 0; p0 < npieces; p0 += 256 * RS_STAGE) {
-                uint4 v[RS_STAGE];
-#pragma unroll
-                for (int it = 0; it < RS_STAGE; ++it) {
-                    const int idx = p0 + tid + 256 * it, r = idx / RQ, j = idx - r * RQ;
-                    v[it] = make_uint4(0, 0, 0, 0);
-                    if (idx < npieces) {
-                        const int shift = (base15 + r * w15) & 15;
-                        const long g = rowbase + (long)r * W - shift + 16 * j;          // an aligned piece; whole inside the buffer?
-                        if (16 * j < shift + rnx && g >= 0 && g + 16 <= total) v[it] = *reinterpret_cast<const uint4*>(hr + g);
-                    }
-                }
-#pragma unroll
-                for (int it = 0; it < RS_STAGE; ++it) {
-                    const int idx = p0 + tid + 256 * it, r = idx / RQ, j = idx - r * RQ;
-                    if (idx < npieces) {
-                        const int shift = (base15 + r * w15) & 15;
-                        const long g = rowbase + (long)r * W - shift + 16 * j;
-                        if (16 * j < shift + rnx) {
-                            if (!(g >= 0 && g + 16 <= total)) {           // the buffer's first or last piece: byte by byte
-                                uint32_t p[4] = {0, 0, 0, 0};
-                                for (int b = 0; b < 16; ++b)
-                                    if (g + b >= 0 && g + b < total) p[b >> 2] |= (uint32_t)hr[g + b] << (8 * (b & 3));
-                                v[it] = make_uint4(p[0], p[1], p[2], p[3]);
-                            }
-                            *reinterpret_cast<uint4*>(raw + r * RP + 16 * j) = v[it];
-                        }
-                    }
-                }
-            }
+            for (int p0 = 0; p0 < rny * (RP / 16); p0 += 256 * RS_STAGE)
+                stage_rows_u8<RS_STAGE>(hr, total, rowbase, W, base15, w15, 0, rny, rnx, raw, RP, p0, [] {});
             __syncthreads();
             // 2a. horizontal pass at every column position: hbuf[r][X] = the taps on raw[r][X .. X + 2s)
-            for (int r = wave; r < rny; r += 4) {
-                const uint8_t* src = raw + r * RP + ((base15 + r * w15) & 15);
-                for (int X = lane; X < dnx; X += 64) {
-                    int a = 1 << (PRECISION_BITS - 1);
-                    for (int k = 0; k < nt; ++k) a += __mul24((int)src[X + k], ks[k]);
-                    hbuf[r * DP + X] = clip8(a);
-                }
-            }
+            filter_pass(raw, RP, base15, w15, 1, hbuf, DP, rny, dnx, ks, nt);
             __syncthreads();
             // 2b. vertical pass at every row position: dense[Y][X] = the taps on hbuf[Y .. Y + 2s)[X] (the raw bytes are dead)
-            for (int Y = wave; Y < dny; Y += 4)
-                for (int X = lane; X < dnx; X += 64) {
-                    int a = 1 << (PRECISION_BITS - 1);
-                    for (int k = 0; k < nt; ++k) a += __mul24((int)hbuf[(Y + k) * DP + X], ks[k]);
-                    raw[Y * DP + X] = clip8(a);
-                }
+            filter_pass(hbuf, DP, 0, 0, DP, raw, DP, dny, dnx, ks, nt);
             __syncthreads();
             // 3. the search: one work item per shift (and one for Lc itself), G threads per item with every G-th row each
-            const bool first = tile == tile_begin;
+            const bool first = tile == mine.begin;
             for (int wi = tid; wi < work; wi += 256) {
                 const int g = wi / nitems, item = wi - g * nitems;
                 const uint8_t* src = lc;
@@ -205,15 +190,8 @@ __global__ __launch_bounds__(256) void register_shifts_kernel(const uint8_t* __r
                         sd += d; sdd += d * d; sdl += d * l;
                     }
                 }
-                if (G == 1) {                                   // the item's only thread: straight into its slots (see below)
-                    u64* slot = prow + 3 * item;
-                    if (first) {
-                        slot[0] = sd; slot[1] = sdd;
-                        if (item < T) slot[2] = sdl;
-                    } else {
-                        slot[0] += sd; slot[1] += sdd;
-                        if (item < T) slot[2] += sdl;
-                    }
+                if (G == 1) {                                   // the item's only thread: straight into its slots
+                    slots_update(prow + 3 * item, first, item < T, sd, sdd, sdl);
                 } else {
                     parts[3 * wi] = sd; parts[3 * wi + 1] = sdd; parts[3 * wi + 2] = sdl;
                 }
@@ -227,38 +205,11 @@ __global__ __launch_bounds__(256) void register_shifts_kernel(const uint8_t* __r
                         const uint32_t* part = parts + 3 * (g * nitems + item);
                         a += part[0]; b += part[1]; c += part[2];
                     }
-                    u64* slot = prow + 3 * item;
-                    if (first) {
-                        slot[0] = a; slot[1] = b;
-                        if (item < T) slot[2] = c;
-                    } else {
-                        slot[0] += a; slot[1] += b;
-                        if (item < T) slot[2] += c;
-                    }
+                    slots_update(prow + 3 * item, first, item < T, a, b, c);
                 }
             }
             __syncthreads();      // the LDS arrays are rewritten by the next block of outputs (`parts` by its horizontal pass)
         }
-    }
-}
-
-// out[pl][q] = sum_row partial[pl][row][q]: a workgroup takes 16 values q of a plane, 16 threads per value share the rows, fixed order
-__global__ __launch_bounds__(256) void register_fold_kernel(const u64* __restrict__ partial, u64* __restrict__ out, int planes, int rows, int k) {
-    __shared__ u64 part[16][16];
-    const int ql = threadIdx.x & 15, rg = threadIdx.x >> 4, q = blockIdx.x * 16 + ql;
-    for (int pl = blockIdx.y; pl < planes; pl += gridDim.y) {
-        u64 sum = 0;
-        if (q < k)
-#pragma unroll 8
-            for (int row = rg; row < rows; row += 16) sum += partial[((long)pl * rows + row) * k + q];
-        part[rg][ql] = sum;
-        __syncthreads();
-        if (rg == 0 && q < k) {
-            u64 total = 0;
-            for (int i = 0; i < 16; ++i) total += part[i][ql];
-            out[(long)pl * k + q] = total;
-        }
-        __syncthreads();
     }
 }
 
@@ -303,8 +254,7 @@ __global__ __launch_bounds__(256) void crop_shift_kernel(const uint8_t* __restri
 }
 
 bool rs_args_ok(int planes, int h, int w, int s, int R) {
-    if (!(planes > 0 && h > 0 && w > 0 && s >= 1 && s <= RS_MAX_S && R >= 0 && R <= RS_MAX_R)) return false;
-    if (!((long)h * s < (1L << 30) && (long)w * s < (1L << 30) && (long)h * w <= (1L << 28))) return false;
+    if (!(u8_pair_ok(planes, h, w, s) && R >= 0 && R <= RS_MAX_R)) return false;
     const int m = rs_margin(s, R);
     return h - 2 * m >= 1 && w - 2 * m >= 1;
 }
@@ -318,15 +268,10 @@ RsGrid rs_grid(int planes, int h, int w, int s, int R) {
     g.G = rs_split(T, g.B, rs_layout(g.B, s, R));
     g.tiles_x = cdiv(w - 2 * m, g.B);
     g.tiles = cdiv(h - 2 * m, g.B) * g.tiles_x;
-    g.gy = planes < RS_PLANES_CAP ? planes : RS_PLANES_CAP;
-    long want = (RS_BLOCKS + g.gy - 1) / g.gy;
+    g.gy = planes_grid_y(planes);
     const long row_bytes = (3L * T + 2) * (long)sizeof(u64);
-    const long fit = RS_PARTIAL_BYTES / row_bytes / planes;
-    if (want > fit) want = fit;
-    if (want > g.tiles) want = g.tiles;
-    if (want < 1) want = 1;
-    const int run = (int)((g.tiles + want - 1) / want);
-    g.gx = (g.tiles + run - 1) / run;                // every workgroup has a block of outputs
+    const int want = blocks_per_plane(planes, g.tiles, RS_PARTIAL_BYTES / row_bytes / planes);
+    g.gx = cdiv(g.tiles, tile_run(g.tiles, want));   // every workgroup has a block of outputs
     return g;
 }
 constexpr int64_t RS_TAP_BYTES = 2 * RS_MAX_S * (int64_t)sizeof(int);
@@ -343,13 +288,8 @@ extern "C" int64_t pssr_register_shifts_workspace_bytes(int planes, int h, int w
 extern "C" int pssr_register_shifts_u8(const uint8_t* hr, const uint8_t* lr, uint64_t* sums, int planes, int h, int w, int s, int radius,
                                        void* workspace, pssr_stream_t stream) {
     PSSR_CHECK(hr && lr && sums && workspace, PSSR_ERR_ARG, "register_shifts_u8: null pointer");
-    PSSR_CHECK(planes > 0 && h > 0 && w > 0, PSSR_ERR_ARG, "register_shifts_u8: planes, h and w must be positive (%d, %d, %d)", planes, h, w);
-    PSSR_CHECK(s >= 1 && s <= RS_MAX_S, PSSR_ERR_ARG, "register_shifts_u8: the scale must be an integer in 1 .. 16, given %d", s);
+    if (const int status = u8_pair_check("register_shifts_u8", planes, h, w, s)) return status;
     PSSR_CHECK(radius >= 0 && radius <= RS_MAX_R, PSSR_ERR_ARG, "register_shifts_u8: the radius must be 0 .. 32 HR pixels, given %d", radius);
-    PSSR_CHECK((long)h * w <= (1L << 28), PSSR_ERR_ARG, "register_shifts_u8: %ld pixels per LR plane (at most 2^28: the sums are exact up to there)",
-               (long)h * w);
-    PSSR_CHECK((long)h * s < (1L << 30) && (long)w * s < (1L << 30), PSSR_ERR_ARG,
-               "register_shifts_u8: a %d x %d plane at scale %d has an axis of 2^30 or more", h, w, s);
     PSSR_CHECK(rs_args_ok(planes, h, w, s, radius), PSSR_ERR_ARG,
                "register_shifts_u8: a %d x %d LR plane leaves nothing inside the margin of %d pixels (1 + ceil(radius / scale)) on every side", h, w,
                rs_margin(s, radius));
@@ -363,7 +303,7 @@ extern "C" int pssr_register_shifts_u8(const uint8_t* hr, const uint8_t* lr, uin
     hipLaunchKernelGGL(register_shifts_kernel, dim3(g.gx, g.gy), dim3(256), (size_t)rs_layout(g.B, s, radius).bytes, st, hr, lr, partial, (const int*)taps,
                        planes, h, w, s, radius, g.B, g.G, g.tiles_x, g.tiles);
     PSSR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(register_fold_kernel, dim3(cdiv(k3, 16), g.gy), dim3(256), 0, st, (const u64*)partial, (u64*)sums, planes, g.gx, k3);
+    launch_fold_u64<16>(partial, (u64*)sums, planes, g.gx, k3, st);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }
@@ -376,8 +316,7 @@ extern "C" int pssr_crop_shift_u8(const uint8_t* in, uint8_t* out, const int32_t
     PSSR_CHECK(ho <= H && wo <= W, PSSR_ERR_ARG, "crop_shift_u8: a %d x %d window does not fit a %d x %d plane", ho, wo, H, W);
     const bool vec = wo % 16 == 0 && (uintptr_t)out % 16 == 0;
     const long pieces = vec ? (long)ho * (wo / 16) : (long)ho * wo;
-    const int gy = planes < RS_PLANES_CAP ? planes : RS_PLANES_CAP;
-    const dim3 grid(grid1d(pieces, (RS_BLOCKS + gy - 1) / gy), gy);
+    const dim3 grid(blocks_per_plane(planes, (pieces + 255) / 256), planes_grid_y(planes));
     hipStream_t st = (hipStream_t)stream;
     if (vec)
         hipLaunchKernelGGL(crop_shift_kernel<true>, grid, dim3(256), 0, st, in, out, (const int*)origins, planes, H, W, ho, wo);

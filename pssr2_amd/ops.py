@@ -1085,21 +1085,30 @@ def noise_profile_loss(pred_hist, pred_sum, target_hist, target_sum, per_image, 
 FITS = ("affine", "identity")        # consistency_map's ``fit``
 
 
+def _u8_plane_pair(who, hi, lo, hi_name):
+    """The checks of the ops that score an HR-side plane against an LR-side plane: uint8 device tensors ``hi`` [..., s*h, s*w] and ``lo``
+    [..., h, w], the same leading dimensions, ``s`` an integer in 1 .. 16, at most 2**28 pixels per LR plane.  ``who`` and ``hi_name``
+    name the op and its HR side in the messages.  -> ``(hi, lo, planes, h, w, s)`` with both tensors contiguous."""
+    if hi.dtype != torch.uint8 or lo.dtype != torch.uint8 or not (hi.is_cuda and lo.is_cuda) or hi.dim() < 2 or hi.dim() != lo.dim() \
+            or hi.shape[:-2] != lo.shape[:-2]:
+        raise ValueError(f"{who} needs two uint8 device tensors [..., s*h, s*w] and [..., h, w] with the same leading dimensions")
+    (H, W), (h, w) = hi.shape[-2:], lo.shape[-2:]
+    s = H // h if h else 0
+    if h < 1 or w < 1 or not 1 <= s <= 16 or H != s * h or W != s * w:
+        raise ValueError(f"{who}: a {H}x{W} {hi_name} is no integer multiple (1 .. 16) of the {h}x{w} LR image")
+    if h * w > 1 << 28:
+        raise ValueError(f"{who}: {h * w} pixels per LR plane (at most 2**28)")
+    planes = lo.numel() // (h * w)
+    if planes < 1:
+        raise ValueError(f"{who}: no planes")
+    return hi.contiguous(), lo.contiguous(), planes, h, w, s
+
+
 def reduce_moments_u8(y, l):
     """uint8 device tensors ``y`` [..., s*h, s*w] (the prediction) and ``l`` [..., h, w] (the LR input), the same leading dimensions, ``s`` an
     integer in 1 .. 16 -> ``(d, sums)``: ``d`` uint8 like ``l``, ``bilinear_down_u8(y, h, w)`` bit for bit, and ``sums`` int64 [planes, 5],
     the exact ``sum d, sum l, sum d*d, sum d*l, sum l*l`` of each plane (all below 2**63).  One fused pass over ``y``."""
-    if y.dtype != torch.uint8 or l.dtype != torch.uint8 or not (y.is_cuda and l.is_cuda) or y.dim() < 2 or y.dim() != l.dim() \
-            or y.shape[:-2] != l.shape[:-2]:
-        raise ValueError("reduce_moments_u8 needs two uint8 device tensors [..., s*h, s*w] and [..., h, w] with the same leading dimensions")
-    (H, W), (h, w) = y.shape[-2:], l.shape[-2:]
-    s = H // h if h else 0
-    if h < 1 or w < 1 or not 1 <= s <= 16 or H != s * h or W != s * w:
-        raise ValueError(f"reduce_moments_u8: a {H}x{W} prediction is no integer multiple (1 .. 16) of the {h}x{w} LR image")
-    if h * w > 1 << 28:
-        raise ValueError(f"reduce_moments_u8: {h * w} pixels per reduced plane (at most 2**28)")
-    y, l = y.contiguous(), l.contiguous()
-    planes = l.numel() // (h * w)
+    y, l, planes, h, w, s = _u8_plane_pair("reduce_moments_u8", y, l, "prediction")
     lib = L.lib()
     ws = torch.empty(lib.pssr_reduce_moments_workspace_bytes(planes, h, w, s), dtype=torch.uint8, device=y.device)
     d = torch.empty_like(l)
@@ -1146,24 +1155,12 @@ def register_shifts_u8(hr, lr, radius):
     ``(ty + radius) (2 radius + 1) + tx + radius``) the exact ``sum D, sum D*D, sum D*Lc`` of the Pillow-bilinear reduction ``D`` of ``hr``
     sampled at that shift against ``Lc = lr[m:h-m, m:w-m]``, ``m = register_margin(s, radius)``, then ``sum Lc, sum Lc*Lc``.  One fused
     pass over ``hr``."""
-    if hr.dtype != torch.uint8 or lr.dtype != torch.uint8 or not (hr.is_cuda and lr.is_cuda) or hr.dim() < 2 or hr.dim() != lr.dim() \
-            or hr.shape[:-2] != lr.shape[:-2]:
-        raise ValueError("register_shifts_u8 needs two uint8 device tensors [..., s*h, s*w] and [..., h, w] with the same leading dimensions")
-    (H, W), (h, w) = hr.shape[-2:], lr.shape[-2:]
-    s = H // h if h else 0
-    if h < 1 or w < 1 or not 1 <= s <= 16 or H != s * h or W != s * w:
-        raise ValueError(f"register_shifts_u8: a {H}x{W} HR image is no integer multiple (1 .. 16) of the {h}x{w} LR image")
+    hr, lr, planes, h, w, s = _u8_plane_pair("register_shifts_u8", hr, lr, "HR image")
     if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= MAX_REGISTER_RADIUS:
         raise ValueError(f"register_shifts_u8: the radius must be an int in 0 .. {MAX_REGISTER_RADIUS} HR pixels. Given {radius!r}.")
     m = register_margin(s, radius)
     if h - 2 * m < 1 or w - 2 * m < 1:
         raise ValueError(f"register_shifts_u8: a {h}x{w} LR image leaves nothing inside the margin of {m} pixels on every side")
-    if h * w > 1 << 28:
-        raise ValueError(f"register_shifts_u8: {h * w} pixels per LR plane (at most 2**28)")
-    hr, lr = hr.contiguous(), lr.contiguous()
-    planes = lr.numel() // (h * w)
-    if planes < 1:
-        raise ValueError("register_shifts_u8: no planes")
     lib = L.lib()
     ws = torch.empty(lib.pssr_register_shifts_workspace_bytes(planes, h, w, s, radius), dtype=torch.uint8, device=hr.device)
     sums = torch.empty(planes, 3 * (2 * radius + 1) ** 2 + 2, dtype=torch.int64, device=hr.device)

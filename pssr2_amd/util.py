@@ -290,12 +290,55 @@ def _check_fit(fit):
         raise ValueError(f"fit must be one of {ops.FITS}. Given {fit!r}.")
 
 
+def _pearson_terms(n: int, sd: int, sl: int, sdd: int, sdl: int, sll: int):
+    """``(num, den, denl, r)`` from the exact sums of ``D``, ``L``, ``D D``, ``D L`` and ``L L`` over ``n`` pixels (Python ints), in exactly
+    the expressions of include/pssr_mi355.h: ``n`` times the covariance and the two variances, and the Pearson correlation
+    ``num / sqrt(den denl)`` (0 when ``den`` or ``denl`` is 0)."""
+    num, den, denl = n * sdl - sd * sl, n * sdd - sd * sd, n * sll - sl * sl
+    return num, den, denl, (num / math.sqrt(den * denl) if den > 0 and denl > 0 else 0.0)
+
+
+def _u8_image_pair(who, hi, lo, names, roles):
+    """The front half of the entry points that score an HR-side stack ``hi`` [N, C, s*h, s*w] against an LR-side stack ``lo`` [N, m, h, w]
+    (or both 3-D, without the batch axis): uint8 arrays become tensors, host tensors are refused, ``C <= m``, ``s`` an integer in 1 .. 16,
+    at most 2**28 pixels per LR plane.  ``names``: the two arguments' names, ``roles``: what an item of each is, with a gap for its frame
+    count.  -> ``(hi, lo, batched, scale, device)``, both tensors 4-D and where they were."""
+    tensors = []
+    for name, t in zip(names, (hi, lo)):
+        if not torch.is_tensor(t):
+            t = torch.as_tensor(np.ascontiguousarray(t))
+        elif not t.is_cuda:
+            raise RuntimeError(f"pssr2_amd.util.{who} runs on an MI355X (HIP) device only; there is no CPU fallback")
+        if t.dtype != torch.uint8:
+            raise TypeError(f"{who} takes uint8 images; {name} is {t.dtype}")
+        tensors.append(t)
+    hi, lo = tensors
+    if hi.dim() != lo.dim() or hi.dim() not in (3, 4):
+        raise ValueError(f"{names[0]} and {names[1]} must both be 4-D, [images, frames, height, width], or both 3-D without the batch axis. "
+                         f"Shapes are {tuple(hi.shape)} and {tuple(lo.shape)} respectively.")
+    batched = hi.dim() == 4
+    if not batched:
+        hi, lo = hi[None], lo[None]
+    (n_img, c, H, W), (n_lo, m, h, w) = hi.shape, lo.shape
+    if n_img != n_lo:
+        raise ValueError(f"{names[0]} and {names[1]} must have the same number of images. Received {n_img} and {n_lo} images respectively.")
+    if c > m:
+        raise ValueError(f"{roles[0].format(c)} cannot be matched with {roles[1].format(m)}.")
+    scale = H // h if h else 0
+    if min(n_img, c, h, w) < 1 or not 1 <= scale <= 16 or H != scale * h or W != scale * w:
+        raise ValueError(f"The size of {names[0]} must be one integer multiple (1 to 16) of the size of {names[1]} along both axes. "
+                         f"Sizes are {H}x{W} and {h}x{w} respectively.")
+    if h * w > 1 << 28:
+        raise ValueError(f"A plane of {names[1]} of {h * w} pixels is above the 2**28 up to which the sums are exact.")
+    return hi, lo, batched, scale, hi.device if hi.is_cuda else (lo.device if lo.is_cuda else "cuda")
+
+
 def _consistency_fit(n: int, sums, fit: str):
     """``(alpha, beta, rsp, table)`` of one plane from its five exact sums ``Sd, Sl, Sdd, Sdl, Sll`` over ``n`` pixels (Python ints), in
     exactly the expressions of include/pssr_mi355.h: the least-squares line ``L ~ alpha D + beta`` (or the identity), the Pearson
     correlation of D and L, and the int32 table ``P[d]`` of the expected LR value in 1/256 grey levels (``round`` is half-to-even)."""
     sd, sl, sdd, sdl, sll = (int(v) for v in sums)
-    num, den, denl = n * sdl - sd * sl, n * sdd - sd * sd, n * sll - sl * sl
+    num, den, _, rsp = _pearson_terms(n, sd, sl, sdd, sdl, sll)
     if fit == "identity":
         alpha, beta = 1.0, 0.0
     elif den == 0:
@@ -303,7 +346,6 @@ def _consistency_fit(n: int, sums, fit: str):
     else:
         alpha = num / den
         beta = (sl - alpha * sd) / n
-    rsp = num / math.sqrt(den * denl) if den > 0 and denl > 0 else 0.0
     table = [min(max(round(256.0 * (alpha * d + beta)), -65536), 131071) for d in range(256)]
     return alpha, beta, rsp, table
 
@@ -326,34 +368,9 @@ def consistency_map(lr, hr_hat, *, fit: str = "affine", to_numpy: bool = True):
     (``pssr_consistency_map_u8``).  Everything after the fit is integer arithmetic: the result is a pure function of the bytes.
     ``to_numpy=False`` leaves ``map`` in HBM."""
     _check_fit(fit)
-    tensors = []
-    for name, t in (("lr", lr), ("hr_hat", hr_hat)):
-        if not torch.is_tensor(t):
-            t = torch.as_tensor(np.ascontiguousarray(t))
-        elif not t.is_cuda:
-            raise RuntimeError("pssr2_amd.util.consistency_map runs on an MI355X (HIP) device only; there is no CPU fallback")
-        if t.dtype != torch.uint8:
-            raise TypeError(f"consistency_map takes uint8 images (the LR acquisition and the output of _pred_array); {name} is {t.dtype}")
-        tensors.append(t)
-    lr, hr_hat = tensors
-    if lr.dim() != hr_hat.dim() or lr.dim() not in (3, 4):
-        raise ValueError(f"lr and hr_hat must both be [N, m, h, w] / [N, C, H, W] or both 3-D without the batch axis. Shapes are "
-                         f"{tuple(lr.shape)} and {tuple(hr_hat.shape)} respectively.")
-    batched = lr.dim() == 4
-    if not batched:
-        lr, hr_hat = lr[None], hr_hat[None]
-    (n_img, m, h, w), (n_hat, c, H, W) = lr.shape, hr_hat.shape
-    if n_img != n_hat:
-        raise ValueError(f"lr and hr_hat must have the same number of images. Received {n_img} and {n_hat} images respectively.")
-    if c > m:
-        raise ValueError(f"A prediction of {c} planes cannot be compared with an input of {m} frames.")
-    scale = H // h if h else 0
-    if min(n_img, c, h, w) < 1 or not 1 <= scale <= 16 or H != scale * h or W != scale * w:
-        raise ValueError(f"The prediction's size must be an integer multiple (1 to 16) of the input's. Sizes are {H}x{W} and {h}x{w} respectively.")
-    if h * w > 1 << 28:
-        raise ValueError(f"An input plane of {h * w} pixels is above the 2**28 up to which the squared-error sum is exact.")
+    hr_hat, lr, batched, _, dev = _u8_image_pair("consistency_map", hr_hat, lr, ("hr_hat", "lr"), ("A prediction of {} planes", "an input of {} frames"))
+    (n_img, c), (h, w) = hr_hat.shape[:2], lr.shape[-2:]
     from .data import _slice_center
-    dev = hr_hat.device if hr_hat.is_cuda else (lr.device if lr.is_cuda else "cuda")
     frames = _slice_center(lr.to(dev), c).contiguous()
     d, sums = ops.reduce_moments_u8(hr_hat.to(dev).contiguous(), frames)
     fits = [_consistency_fit(h * w, row, fit) for row in sums.cpu().tolist()]
@@ -383,18 +400,16 @@ def _register_choose(n: int, rows, radius: int):
     side = 2 * radius + 1
     pooled = [sum(int(v) for v in col) for col in zip(*rows)]
     sl, sll = pooled[3 * side * side], pooled[3 * side * side + 1]
-    denl = n * sll - sl * sl
-    best = None                                         # (p, q): the score p / (q denl), q > 0; then the tie key, num and den
+    best = None                                         # (p, q): the score p / (q denl), q > 0; then the tie key and the correlation
     for t in range(side * side):
         sd, sdd, sdl = pooled[3 * t:3 * t + 3]
         ty, tx = t // side - radius, t % side - radius
-        num, den = n * sdl - sd * sl, n * sdd - sd * sd
+        num, den, denl, r = _pearson_terms(n, sd, sl, sdd, sdl, sll)
         p, q = (num * abs(num), den) if den > 0 and denl > 0 else (0, 1)
         key = (ty * ty + tx * tx, ty, tx)
         if best is None or p * best[1] > best[0] * q or (p * best[1] == best[0] * q and key < best[2]):
-            best = (p, q, key, num, den)
-    _, _, key, num, den = best
-    return (key[1], key[2]), (num / math.sqrt(den * denl) if den > 0 and denl > 0 else 0.0)
+            best = (p, q, key, r)
+    return (best[2][1], best[2][2]), best[3]
 
 
 def register_pairs(hr, lr, *, radius: int = 8, to_numpy: bool = True):
@@ -418,40 +433,15 @@ def register_pairs(hr, lr, *, radius: int = 8, to_numpy: bool = True):
     prediction can be aligned to its ground truth."""
     import warnings
     radius = _check_radius(radius)
-    tensors = []
-    for name, t in (("hr", hr), ("lr", lr)):
-        if not torch.is_tensor(t):
-            t = torch.as_tensor(np.ascontiguousarray(t))
-        elif not t.is_cuda:
-            raise RuntimeError("pssr2_amd.util.register_pairs runs on an MI355X (HIP) device only; there is no CPU fallback")
-        if t.dtype != torch.uint8:
-            raise TypeError(f"register_pairs takes uint8 images; {name} is {t.dtype}")
-        tensors.append(t)
-    hr, lr = tensors
-    if hr.dim() != lr.dim() or hr.dim() not in (3, 4):
-        raise ValueError(f"hr and lr must both be [N, C, H, W] / [N, c, h, w] or both 3-D without the batch axis. Shapes are "
-                         f"{tuple(hr.shape)} and {tuple(lr.shape)} respectively.")
-    batched = hr.dim() == 4
-    if not batched:
-        hr, lr = hr[None], lr[None]
-    (n_img, C, H, W), (n_lr, c, h, w) = hr.shape, lr.shape
-    if n_img != n_lr:
-        raise ValueError(f"hr and lr must have the same number of images. Received {n_img} and {n_lr} images respectively.")
-    if C > c:
-        raise ValueError(f"An HR item of {C} frames cannot be matched with an LR item of {c} frames.")
-    scale = H // h if h else 0
-    if min(n_img, C, h, w) < 1 or not 1 <= scale <= 16 or H != scale * h or W != scale * w:
-        raise ValueError(f"The HR size must be one integer multiple (1 to 16) of the LR size along both axes. Sizes are {H}x{W} and {h}x{w} respectively.")
+    hr, lr, batched, scale, dev = _u8_image_pair("register_pairs", hr, lr, ("hr", "lr"), ("An HR item of {} frames", "an LR item of {} frames"))
+    (n_img, C), (c, h, w) = hr.shape[:2], lr.shape[1:]
     m = ops.register_margin(scale, radius)
     hc, wc = h - 2 * m, w - 2 * m
     if hc < 1 or wc < 1:
         raise ValueError(f"An LR image of {h}x{w} leaves nothing inside the margin of {m} pixels that radius={radius} at scale {scale} needs on every side.")
-    if h * w > 1 << 28:
-        raise ValueError(f"An LR plane of {h * w} pixels is above the 2**28 up to which the sums are exact.")
     if not (hr.is_cuda or lr.is_cuda or torch.cuda.is_available()):
         raise RuntimeError("pssr2_amd.util.register_pairs needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
     from .data import _slice_center
-    dev = hr.device if hr.is_cuda else (lr.device if lr.is_cuda else "cuda")
     hr, lr = hr.to(dev).contiguous(), lr.to(dev).contiguous()
     sums = ops.register_shifts_u8(hr, _slice_center(lr, C).contiguous(), radius).cpu().tolist()
     chosen = [_register_choose(C * hc * wc, sums[i * C:(i + 1) * C], radius) for i in range(n_img)]

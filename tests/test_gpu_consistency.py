@@ -141,6 +141,22 @@ def test_consistency_map_more_planes_than_the_grid_and_a_large_sse():
     assert int(sse[0]) == 90000 * 131071 ** 2 and bool((got == 255).all())
 
 
+@pytest.mark.parametrize("pixels", [258 * 4096, 257 * 4096 + 1])
+def test_consistency_map_more_partial_rows_than_the_fold_has_threads(pixels):
+    """One plane of more than 256 workgroups, on the 16-byte path and on the scalar path: the fold's 256 threads take more than one
+    partial row each.  The workspace is one 64-bit partial sum per workgroup and plane."""
+    from pssr2_amd import _lib, ops
+    rows = _lib.lib().pssr_consistency_map_workspace_bytes(1, pixels) // 8
+    assert rows > 256
+    rng = np.random.default_rng(pixels)
+    d, l = rng.integers(0, 256, size=(1, 1, pixels), dtype=np.uint8), rng.integers(0, 256, size=(1, 1, pixels), dtype=np.uint8)
+    lut = rng.integers(-65536, 131072, size=(1, 256)).astype(np.int32)
+    got, sse = ops.consistency_map_u8(torch.tensor(d).cuda(), torch.tensor(l).cuda(), torch.tensor(lut).cuda())
+    want, want_sse = R.map_ref(d[0], l[0], lut[0])
+    np.testing.assert_array_equal(got[0].cpu().numpy(), want)
+    assert sse.cpu().tolist() == [want_sse]
+
+
 # ------------------------------------------------------------------------------------------------ util.consistency_map
 @pytest.mark.parametrize("fit", R.FITS)
 @pytest.mark.parametrize("m,c", [(3, 1), (3, 3), (4, 2)])

@@ -65,6 +65,16 @@ def test_sums_when_a_workgroup_walks_several_blocks():
     _sums_case(rng.integers(0, 256, size=(planes, s * h, s * w), dtype=np.uint8), rng.integers(0, 256, size=(planes, h, w), dtype=np.uint8), radius)
 
 
+def test_sums_with_more_partial_rows_than_the_fold_has_threads():
+    """One plane, s = 1, radius 0 (m = 1): a 544 x 544 window is 17 x 17 blocks of 32 x 32 outputs, one per workgroup, so the fold adds
+    289 partial rows of 3 T + 2 = 5 sums.  The workspace is the tap table (128 bytes) and one such row per workgroup and plane."""
+    from pssr2_amd import _lib
+    rows = (_lib.lib().pssr_register_shifts_workspace_bytes(1, 546, 546, 1, 0) - 128) // (8 * 5)
+    assert rows > 256
+    rng = np.random.default_rng(5)
+    _sums_case(rng.integers(0, 256, size=(1, 546, 546), dtype=np.uint8), rng.integers(0, 256, size=(1, 546, 546), dtype=np.uint8), 0)
+
+
 def test_sums_leading_dimensions_and_odd_addresses():
     """[N, C, ...] inputs, and an HR buffer that starts at every address modulo 4 (the 16-byte staging must fall back to bytes at the
     buffer's ends and shift inside it)."""
