@@ -848,7 +848,9 @@ int pssr_f64_to_f32_batch(const pssr_fold_batch* items, int n_items, int stripes
  * GradHist soft histogram (pssr/models/_blocks.py:94-112) and the crappifier loss around it (pssr/train.py:388-402), for
  * train_crappifier (pssr/train.py:168-322).  Per image over its n = C*H*W f32 values: bins centred at
  * c_k = lo + (hi - lo) / bins * (k + 1/2), s_k(x) = sigmoid(sigma (x - c_k)), s_{-1} = 1.  Reproducible bit for bit (no atomics);
- * the work skipped and what it can drop are bounded in csrc/hist.hip's header comment.
+ * the work skipped and what it can drop are bounded in csrc/hist.hip's header comment.  Non-finite values follow torch: a NaN x
+ * makes its image's histogram row NaN and its dx NaN (0 where PSSR_HIST_CLAMP cut a NaN xa); x = -inf adds 1 to bin 0, x = +inf
+ * adds nothing, both have dx = 0.
  */
 #define PSSR_HIST_CLAMP 1          /* clamp the first operand to [0, 255] on load (and mask its gradient: torch.clamp, inclusive) */
 #define PSSR_HIST_ACCUMULATE 2     /* pssr_gradhist_bwd adds into dx */

@@ -9,17 +9,21 @@
 //
 // Forward: one thread per bin, the image's pixels staged through LDS in tiles of HIST_TILE (256: many short
 // workgroups, so the few waves whose bins hold the mass do not serialise the launch); a workgroup covers 256 bins of one image and a
-// fixed strided subset of its tiles and writes one partial row (no atomics); hist_reduce_kernel adds the partial rows in workgroup order in
-// double.  Workspace: pairs * batch * HIST_MAX_WG * bins floats, independent of N.  Two runs give the same bits.
+// fixed strided subset of its tiles, adds its f32 terms in double and writes one partial row rounded to f32 (no atomics);
+// hist_reduce_kernel adds the partial rows in workgroup order in double.  Workspace: pairs * batch * HIST_MAX_WG * bins floats,
+// independent of N.  Two runs give the same bits.
 // Skipped work (per wave of 64 bins [j0, j1), decided for each pixel, uniform over the wave):
 //   * x >= c_{j1-1} + 19 / sigma: every s_k of the wave (k = j0-1 .. j1-1) is exactly 1.0f (sigma (x - c) >= 18 > 17.4, where
 //     exp(-z) is below half an ulp of 1), so every term is exactly 0 -- nothing is lost;
 //   * j0 > 0 and x <= c_{j0-1} - 31 / sigma: every term is at most s_{j0-1}(x) <= e^-30, and the terms of ALL skipped bins above x add up
 //     (telescoping) to at most e^-30 ~ 9.4e-14 per pixel, i.e. at most 9.4e-14 * N absolute per image summed over every bin.
+//     The wave that holds bin 0 has no lower window: s_{-1} = 1 does not decay, so x = -inf adds its 1 to bin 0 as in the reference.
 // The window is set in x by 1 / sigma, so a small sigma (wide sigmoids) keeps every bin of the range active.
+// Non-finite pixels follow torch: NaN passes both window tests and makes its image's row NaN; +inf adds 0, -inf adds 1 to bin 0.
 // Backward: one thread per pixel, the combined gradient G_k = g[k+1] [k+1 < bins] - g[k] in LDS, k restricted to
 // sigma (x - c_k) in [-31, 19]: above, s_k(1 - s_k) is exactly 0; below, the dropped sum is at most
-// sigma * max|G| * e^-30 / (1 - e^-(sigma delta)) per pixel.
+// sigma * max|G| * e^-30 / (1 - e^-(sigma delta)) per pixel.  A NaN x gives dx = NaN (0 under PSSR_HIST_CLAMP when xa itself is NaN:
+// torch.clamp's gradient); x = +-inf gives 0.
 #include "common.h"
 
 #define HIST_TILE 256
@@ -30,8 +34,12 @@
 namespace {
 
 __device__ __forceinline__ float hist_center(int k, float lo, float delta) {
-    // torch: float(lo) + delta * (arange(bins).float() + 0.5): an fp32 multiply then an fp32 add, never contracted
-    return __fadd_rn(lo, __fmul_rn(delta, (float)k + 0.5f));
+#pragma clang fp contract(off)
+    // torch: float(lo) + delta * (arange(bins).float() + 0.5): an fp32 multiply then an fp32 add.  The pragma keeps them apart:
+    // __fmul_rn / __fadd_rn are plain operators to the compiler, and fused into one FMA (one rounding) they give another centre
+    // wherever delta * (k + 1/2) is inexact (1000 bins over 512: off by up to 3e-5, 1e-4 in sigma (x - c))
+    const float p = delta * ((float)k + 0.5f);
+    return lo + p;
 }
 
 __device__ __forceinline__ float hist_sig(float x, float c, float sigma) {
@@ -72,7 +80,8 @@ __global__ __launch_bounds__(256) void hist_fwd_kernel(HistPairs in, float* __re
     const float x_hi = j0 < bins ? hist_center(j1 - 1, lo, delta) + HIST_HI_Z / sigma : -INFINITY;
     const float x_lo = j0 > 0 ? hist_center(j0 - 1, lo, delta) - HIST_LO_Z / sigma : -INFINITY;
     const float c_j = hist_center(j, lo, delta), c_jm = hist_center(j - 1, lo, delta);
-    float acc = 0.f;
+    double acc = 0.0;       // not float: a run of equal pixels (clamped or integer profiles) adds one term again and again, and the
+                            // roundings of a growing f32 sum then share a sign (8e-5 of 210 for 226 pixels at 255)
     const long ntiles = (n + HIST_TILE - 1) / HIST_TILE;
     for (long t = wg; t < ntiles; t += nwg) {
         const long base = t * HIST_TILE;
@@ -83,13 +92,13 @@ __global__ __launch_bounds__(256) void hist_fwd_kernel(HistPairs in, float* __re
         if (j0 >= bins) continue;
         for (int i = 0; i < cnt; ++i) {
             const float x = xs[i];
-            if (x >= x_hi || x <= x_lo) continue;       // wave-uniform
+            if (x >= x_hi || (j0 > 0 && x <= x_lo)) continue;       // wave-uniform; the wave of bin 0 has no lower window (x = -inf counts)
             const float sj = hist_sig(x, c_j, sigma);
             const float sm = j == 0 ? 1.f : hist_sig(x, c_jm, sigma);
-            acc += sm - sj;
+            acc += (double)(sm - sj);
         }
     }
-    if (j < bins) work[(((long)pair * gridDim.y + b) * nwg + wg) * bins + j] = acc;
+    if (j < bins) work[(((long)pair * gridDim.y + b) * nwg + wg) * bins + j] = (float)acc;
 }
 
 // h[pair][b][j] = sum over workgroups, in workgroup order, in double
@@ -140,6 +149,7 @@ __global__ __launch_bounds__(256) void hist_bwd_kernel(const float* __restrict__
         const float sk = hist_sig(x, hist_center(k, lo, delta), sigma);
         s += sk * (1.f - sk) * G[k];
     }
+    if (x != x) s = x;                                  // the k window of a NaN is empty; torch's sum is NaN
     float d = sigma * s;
     if (flags & PSSR_HIST_ACCUMULATE) d += dx[gi];
     if (clamp_a && !(a_raw >= 0.f && a_raw <= 255.f)) d = 0.f;        // torch.clamp's gradient: min <= x <= max, inclusive
