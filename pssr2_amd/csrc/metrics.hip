@@ -6,6 +6,9 @@
 //     elements accumulated in order, each summed PAIRWISE (blocks of <= 128 elements with 8 accumulators, halves rounded down
 //     to a multiple of 8),
 // while the float64 parts (np.cov, the prediction's rescaling) are insensitive to summation order at uint8 resolution.
+// Degenerate images: where the reference's value is NaN (0/0 from a constant ground truth or prediction, or from a ground truth so
+// sparse that its `pmax` percentile is 0) numpy's cast of NaN to uint8 is undefined and gives 0 on x86-64; here that side comes
+// out as byte 0 by construction -- NaN is mapped to 0 before the cast, on both tables.
 // One workgroup per image.
 #include "common.h"
 
@@ -195,11 +198,12 @@ __global__ __launch_bounds__(NT) void normalize_preds_kernel(const uint8_t* __re
     const float a_div = __fdiv_rn(a_mean, base_mean);
     const double b_div = b_mean / (double)base_mean;
     {
+        // `v > 0 ? ... : 0` sends NaN to 0 with the negatives, so no NaN reaches the cast (see the header: degenerate images)
         float a = __fdiv_rn(a_tab[tid], a_div);
-        a = a < 0.f ? 0.f : (a > 255.f ? 255.f : a);
+        a = a > 0.f ? (a > 255.f ? 255.f : a) : 0.f;
         out_a[tid] = (unsigned char)a;
         double b = b_tab[tid] / b_div;
-        b = b < 0.0 ? 0.0 : (b > 255.0 ? 255.0 : b);
+        b = b > 0.0 ? (b > 255.0 ? 255.0 : b) : 0.0;
         out_b[tid] = (unsigned char)b;
     }
     __syncthreads();

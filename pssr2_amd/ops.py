@@ -847,7 +847,9 @@ def window_attn_bwd(qkv, bias_table, lse, dout, heads, ws, shift, scale):
 
 
 def normalize_preds_u8(hr, hr_hat, pmin=0.1, pmax=99.9):
-    """uint8 device tensors [..., H, W] of equal shape -> (hr_norm, hr_hat_norm) uint8, as pssr.util.normalize_preds (bit-exact)."""
+    """uint8 device tensors [..., H, W] of equal shape -> (hr_norm, hr_hat_norm) uint8, as pssr.util.normalize_preds (bit-exact).
+    Degenerate images: a side whose reference value is NaN (a constant ground truth or prediction, or a ground truth so sparse that its
+    ``pmax`` percentile is 0) comes out as byte 0 -- what numpy's undefined NaN -> uint8 cast happens to give on x86-64, fixed here."""
     if hr.dtype != torch.uint8 or hr_hat.dtype != torch.uint8 or hr.shape != hr_hat.shape or not hr.is_cuda:
         raise ValueError("normalize_preds_u8 needs two uint8 device tensors of the same shape")
     hr, hr_hat = hr.contiguous(), hr_hat.contiguous()

@@ -1,10 +1,97 @@
 """normalize_preds on the device (csrc/metrics.hip) vs the reference's own outputs (tests/golden/metrics.npz) and,
-at sizes the fixtures do not hold, vs the pinned numpy restatement (oracle/metrics_ref.py): bit-exact uint8."""
+at sizes the fixtures do not hold, vs the pinned numpy restatement (oracle/metrics_ref.py): bit-exact uint8.  The image metrics
+against exact values (tests/_metrics_ref.py, whose statements tests/test_metrics_ref.py pins on the host).
+
+Pixel counts of the chunk-tail test (numpy sums float32 in pieces of 8192 elements; "tail" is the last piece, "+" means full pieces
+come before it), each with three contents (correlated, anti-correlated = 255 - hr, saturated) at percentiles (0.1, 99.9) and (2, 98):
+    one piece     2, 7 (left to right, n < 8); 9 (8 accumulators + 1); 128 (one full leaf); 129 = 64 + 65, 130 = 64 + 66, 136 = 64 + 72
+                  (first split); 8191 (uneven splits all the way down); 8192 (exactly one piece)
+    tail < 8      8193 = 8192 + 1, 8199 = 8192 + 7
+    tail 8..128   8281 = 8192 + 89 (89 % 8 = 1), 8320 = 8192 + 128
+    tail > 128    8327 = 8192 + 135 (135 % 8 = 7), 10000 = 8192 + 1808, 16383 = 8192 + 8191, 32761 = 3 * 8192 + 8185 (8185 % 8 = 1),
+                  63300 = 7 * 8192 + 5956 (5956 % 8 = 4)
+The prediction of another size adds 3600 / 9000, 4500 / 7200 (single pieces) and 8281 / 32761 both ways (a tail on either reduction).
+
+Degenerate contract (header of csrc/metrics.hip, ops.normalize_preds_u8): a side whose reference value is NaN -- 0/0 from a constant
+ground truth (both sides), a constant prediction (prediction side only) or a ground truth so sparse that its upper percentile is 0
+(both sides) -- is byte 0, asserted literally; the other sides, and the other images of the same call, stay bit-exact.  Every
+non-degenerate case asserts that the oracle ran without a warning.
+
+SSIM errors against the exact value, measured on an MI355X over the 8 shapes x 7 contents of test_image_metrics_vs_exact_values:
+    kernel        max 1.6e-14 (200x7, the diagonal ramp against its mirror image); at most 2.0e-15 off the ramp
+    scipy oracle  max 6.7e-13 (7x200, the same content); 2.0e-13 at 45x71, 2.7e-14 on the saturated field
+The kernel's maximum is 40 times below the oracle's, and inside what its arithmetic allows (the cancellation in uxx - ux * ux is at
+most about 65025 * 2^-52 = 1.4e-11 against c2 = 58.5: a few 1e-13).  Its window sums are exact, so its error does not depend on the
+image size; scipy's running float64 sums drift along a row, hence 6.7e-13 over 200 columns.  On single cases the oracle is the closer
+one (200x7 ramp: 4.4e-16 against the kernel's 1.6e-14; zeros against 255: 0 against 1.6e-17): scipy's first pass then runs over
+integers and is exact too, while the kernel still rounds s / 49 (as s * (1 / 49)) and the products in the SSIM expression.  That is
+the rounding the kernel's header names, not a loss in the sums.
+
+test_metrics' `psnr = inf` for a prediction equal to its ground truth is not asserted here: reaching that guard needs a model whose
+output equals the ground truth, i.e. a fake model."""
 import numpy as np
 import pytest
 import torch
 
+import _metrics_ref as R
+
 pytestmark = pytest.mark.gpu
+
+
+def _dev(x):
+    return torch.tensor(x).cuda()
+
+
+def _normalize(hr, hat, pmin=0.1, pmax=99.9):
+    from pssr2_amd import ops
+    a, b = ops.normalize_preds_u8(_dev(hr), _dev(hat), pmin=pmin, pmax=pmax)
+    return a.cpu().numpy(), b.cpu().numpy()
+
+
+def _assert_bit_exact_vs_clean_oracle(hr, hat, pcts, what):
+    want_a, want_b, caught = R.oracle_normalize(hr, hat, *pcts)
+    assert caught == [], (what, pcts, caught)                 # a degenerate input must not slip into the bit-exact set
+    a, b = _normalize(hr, hat, *pcts)
+    np.testing.assert_array_equal(a, want_a, err_msg=f"{what} {pcts} hr side")
+    np.testing.assert_array_equal(b, want_b, err_msg=f"{what} {pcts} prediction side")
+
+
+@pytest.mark.parametrize("shape", R.NORM_SHAPES)
+def test_normalize_preds_bit_exact_on_chunk_tails(shape):
+    for content in R.NORM_CONTENTS:
+        hr, hat = R.norm_pair(shape, content)
+        for pcts in R.NORM_PERCENTILES:
+            _assert_bit_exact_vs_clean_oracle(hr, hat, pcts, (shape, content))
+
+
+@pytest.mark.parametrize("pcts", R.EDGE_PERCENTILES)
+def test_normalize_preds_bit_exact_on_percentile_edges(pcts):
+    hr, hat = R.edge_pair()
+    _assert_bit_exact_vs_clean_oracle(hr, hat, pcts, "edge")
+
+
+@pytest.mark.parametrize("name", ["two_level", "narrow", "sparse50"])
+def test_normalize_preds_bit_exact_on_narrow_distributions(name):
+    hr, hat, percentiles = R.distribution_pairs()[name]
+    for pcts in percentiles:
+        _assert_bit_exact_vs_clean_oracle(hr, hat, pcts, name)
+
+
+@pytest.mark.parametrize("name", ["constant_hr", "constant_hat", "both_zero", "sparse4", "mixed"])
+def test_normalize_preds_degenerate_sides_are_zero_bytes(name):
+    """The contract of csrc/metrics.hip's header: a side whose reference value is NaN is byte 0, literally; every other side is still
+    bit-exact with the oracle (tests/test_metrics_ref.py documents that the oracle's own cast gives 0 on the same sides on x86-64)."""
+    hr, hat, zero_hr, zero_hat = R.degenerate_cases()[name]
+    want_a, want_b, _ = R.oracle_normalize(hr, hat)
+    a, b = _normalize(hr, hat)
+    for i in range(hr.shape[0]):
+        np.testing.assert_array_equal(a[i], np.zeros_like(a[i]) if zero_hr[i] else want_a[i], err_msg=f"{name} image {i} hr side")
+        np.testing.assert_array_equal(b[i], np.zeros_like(b[i]) if zero_hat[i] else want_b[i], err_msg=f"{name} image {i} prediction side")
+        assert zero_hr[i] or a[i].std() > 10
+    if name == "sparse4":                                      # the sparse image of the distribution test, at the percentiles that empty it
+        hr, hat, _ = R.distribution_pairs()["sparse50"]
+        a, b = _normalize(hr, hat, 2.0, 98.0)
+        assert not a.any() and not b.any()
 
 
 def test_normalize_preds_bit_exact_vs_reference_fixture(golden):
@@ -161,3 +248,49 @@ def test_normalize_preds_with_a_prediction_of_another_size_vs_oracle(hr_shape, h
     assert want_b.std() > 10                                           # a real image came out, not a constant
     a3, b3 = normalize_preds(hr, hat)                                  # the reference-shaped entry point routes here
     assert np.array_equal(a3, a) and np.array_equal(b3, b) and b3.shape == hat_shape
+
+
+@pytest.mark.parametrize("hr_shape,hat_shape", R.RESIZED_SHAPES)
+def test_normalize_preds_of_another_size_on_the_remaining_branches(hr_shape, hat_shape):
+    """Shrinking along y only (the Gaussian pre-filter on axis 0 alone), shrinking y while enlarging x, and both ways between 91x91
+    and 181x181, where the n and n_hat reductions both end in a tail piece.  The bound is the one of the test above;
+    tests/test_metrics_ref.py shows that the device's covariance formula, restated on the host, stays inside it on these inputs."""
+    from pssr2_amd import ops
+    hr, hat = R.resized_pair(hr_shape, hat_shape)
+    want_a, want_b, caught = R.oracle_normalize(hr, hat)
+    assert caught == [] and want_b.std() > 10
+    a, b = ops.normalize_preds_resized_u8(_dev(hr), _dev(hat))
+    a, b = a.cpu().numpy(), b.cpu().numpy()
+    np.testing.assert_array_equal(a, want_a)
+    ok, figures = R.within_resized_cap(b, want_b)
+    print(f"resized {hr_shape} / {hat_shape}: max diff {figures[0]}, fraction {figures[1]:.2e}")
+    assert ok and b.shape == hat_shape, figures
+
+
+def _image_metrics(a, b):
+    from pssr2_amd import ops
+    return ops.image_metrics_u8(_dev(a), _dev(b)).cpu().numpy()
+
+
+@pytest.mark.parametrize("shape", R.METRIC_SHAPES)
+def test_image_metrics_vs_exact_values(shape):
+    """Squared-difference sum equal to the Python-int sum; SSIM within 1e-10 of the exact value (tests/_metrics_ref.py:ssim_exact);
+    two calls bit-identical; a batch row equal, bit for bit, to the same image evaluated alone (the img * tiles + tile indexing)."""
+    from oracle import metrics_ref as M
+    for content in R.METRIC_CONTENTS:
+        a, b = R.metric_pair(shape, content)
+        got = _image_metrics(a, b)
+        assert got.shape == (shape[0], 2) and np.array_equal(got, _image_metrics(a, b))
+        exact = [R.ssim_exact(a[i], b[i]) for i in range(shape[0])]
+        err_kernel = max(abs(got[i, 1] - exact[i]) for i in range(shape[0]))
+        err_oracle = max(abs(M.ssim(a[i], b[i]) - exact[i]) for i in range(shape[0]))
+        print(f"ssim {shape} {content}: kernel error {err_kernel:.3e}, scipy oracle error {err_oracle:.3e}")
+        for i in range(shape[0]):
+            assert got[i, 0] == R.ssd_exact(a[i], b[i]), (content, i)
+            assert abs(got[i, 1] - exact[i]) <= 1e-10, (content, i, got[i, 1], exact[i])
+        if shape[0] > 1:
+            for i in range(shape[0]):
+                assert np.array_equal(_image_metrics(a[i:i + 1], b[i:i + 1])[0], got[i]), (content, i)
+    x = R.flat(shape, 200)                                                         # identical constant images: every variance cancels
+    got = _image_metrics(x, x)
+    assert np.array_equal(got[:, 0], np.zeros(shape[0])) and np.abs(got[:, 1] - 1.0).max() <= 1e-15, got
