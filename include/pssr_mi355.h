@@ -823,6 +823,42 @@ int pssr_register_shifts_u8(const uint8_t* hr, const uint8_t* lr, uint64_t* sums
 int pssr_crop_shift_u8(const uint8_t* in, uint8_t* out, const int32_t* origins, int planes, int H, int W, int ho, int wo,
                        pssr_stream_t stream);
 
+/* Fourier ring correlation (FRC): down to which detail size two images of one field agree (pssr2_amd.util.frc; csrc/frc.hip) -- a
+ * prediction against its ground truth, or two predictions of independent acquisitions.  The correlation of the two spectra, ring by ring
+ * in spatial frequency, read off where it falls through a threshold (1/7 by convention).
+ * Inputs: two uint8 plane stacks A, B [planes][H][W] and an even block side n, 16 <= n <= 1024, n <= min(H, W).  Each plane is tiled into
+ * nby x nbx = (H / n) x (W / n) blocks at stride n (integer division); the grid of blocks is centred: its origin is
+ * ((H - nby n) / 2, (W - nbx n) / 2), integer division again.  R = n / 2.
+ *   1. Tables.  w[x] = sin^2(pi (x + 1/2) / n) (window "hann") or 1 (window "none").  Ct[x][k] = w[x] cos(2 pi ((x k) mod n) / n),
+ *      St[x][k] = - w[x] sin(2 pi ((x k) mod n) / n), x, k = 0 .. n - 1, the product reduced mod n in integers before the angle is formed;
+ *      evaluated in float64 on the host, rounded once to float32, row-major [n][n].  The tables are the caller's contract, as lut is for
+ *      pssr_consistency_map_u8 (pssr2_amd.ops.frc_tables makes them); the kernels never evaluate a sine.
+ *   2. Transform.  For a block a: Fa[ky][kx] = sum_y sum_x (Ct + i St)[y][ky] a[y][x] (Ct + i St)[x][kx], the DFT of the block times the
+ *      separable window, in float32 (sum over x first, then over y, each an ascending chain of fused multiply-adds: the order is fixed).
+ *      Fb likewise.
+ *   3. Rings.  fy = ky if ky <= n / 2 else ky - n; q = fy^2 + kx^2; r = (isqrt(4 q) + 1) / 2 in integers, that is floor(sqrt(q) + 1/2).
+ *      Rings 0 .. R are kept, r > R is dropped.
+ *   4. Sums.  Per plane, block and ring three float64 sums over the full spectrum, kx in [0, n) with fx signed like fy:
+ *      Sab = sum Re(Fa conj Fb), Saa = sum |Fa|^2, Sbb = sum |Fb|^2.  The kernel visits kx <= n / 2 and doubles the columns 0 < kx < n / 2,
+ *      which is the same sum (the blocks are real).  The products are formed in float32, the sums across coefficients in float64.
+ *   5. Curve and resolution (host, Python floats, from the sums).  An item's planes and blocks pool their sums ring by ring.  With
+ *      smooth = k >= 0, ring r >= 1 takes the sums of rings max(1, r - k) .. min(R, r + k); ring 0 is never pooled into another ring.
+ *      frc[r] = Sab / sqrt(Saa Sbb), or 0 where Saa Sbb <= 0.  The crossing is the first r >= 1 with frc[r] < threshold:
+ *      r* = (r - 1) + (frc[r-1] - threshold) / (frc[r-1] - frc[r]) (r* = 1 where ring 0 itself lies below the threshold),
+ *      resolution = pixel_size n / r* (infinite for r* = 0), crossed = true.  No ring below the threshold: resolution = 2 pixel_size,
+ *      the sampling limit, crossed = false.
+ * pssr_frc_rings_u8: steps 2 - 4.  a, b [planes][H][W], ct, st [n][n] (step 1), sums [planes][nby nbx][n / 2 + 1][3] in the order
+ *   Sab, Saa, Sbb.  Any even n in range (500 as well as 512): the transform is two matrix products against the tables on the f32-input
+ *   MFMA.  A row pass leaves T = a (Ct + i St)[:, 0 .. n/2] of both images in the workspace; a column pass forms 64 x 64 tiles of Fa and Fb
+ *   in registers and reduces them to ring sums; F never leaves the compute unit.  A third small launch adds the tiles' partial sums in
+ *   tile order.  No atomics, no fence: the same bits on every run.
+ * Both validate on the host before anything is launched (null pointers, planes, sizes, n odd or outside 16 .. 1024 or larger than
+ * the plane, more than 2^24 blocks): PSSR_ERR_ARG with a message.  Workspace of pssr_frc_workspace_bytes bytes (0 for arguments the entry
+ * point rejects; at most about 256 MB: blocks are worked off in chunks). */
+int64_t pssr_frc_workspace_bytes(int planes, int H, int W, int n);
+int pssr_frc_rings_u8(const uint8_t* a, const uint8_t* b, const float* ct, const float* st, double* sums, int planes, int H, int W, int n,
+                      void* workspace, pssr_stream_t stream);
+
 /* Several small f32 device-to-device copies in one launch (host struct passed by value to the kernel): the hand-written
  * backward pass moves side results (dbeta doubling as a bias gradient, centre taps, ...) into the flat gradient buffer the
  * all-reduce and AdamW read (the reference leaves this to autograd's .grad accumulation). */

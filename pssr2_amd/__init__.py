@@ -52,6 +52,9 @@ def __getattr__(name):
     if name in ("preprocess_dataset",):
         from .data import preprocess_dataset
         return preprocess_dataset
+    if name in ("frc",):
+        from .util import frc
+        return frc
     if name in ("FusedAdamW",):
         from .optim import FusedAdamW
         return FusedAdamW

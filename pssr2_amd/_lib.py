@@ -143,6 +143,10 @@ def lib():
         _lib.pssr_register_shifts_workspace_bytes.argtypes = [c_int] * 5
         _lib.pssr_register_shifts_u8.argtypes = [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
         _lib.pssr_crop_shift_u8.argtypes = [c_void_p] * 3 + [c_int] * 5 + [c_void_p]
+        # Fourier ring correlation (csrc/frc.hip)
+        _lib.pssr_frc_workspace_bytes.restype = c_i64
+        _lib.pssr_frc_workspace_bytes.argtypes = [c_int] * 4
+        _lib.pssr_frc_rings_u8.argtypes = [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 2
         # one-pass backward of a flat-K source (csrc/pre_xcol_bwd.hip)
         _lib.pssr_flatk_bwd_pair_supported.argtypes = [c_int] * 3
         _lib.pssr_flatk_bwd_pair_parts.argtypes = [c_i64]

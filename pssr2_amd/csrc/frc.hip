@@ -1,0 +1,257 @@
+// Fourier ring correlation of two uint8 plane stacks (pssr2_amd.util.frc; include/pssr_mi355.h has the definitions).  Per plane the
+// centred grid of n x n blocks (n even, 16 .. 1024, any such n: the transform is two matrix products against the caller's tables
+// Ct, St [n][n] -- window times cosine / minus sine -- on the f32-input MFMA, not a radix-2 FFT), K = n / 2 + 1 kept spectrum columns,
+// R = n / 2 rings.  Per block, three launches' worth of work:
+//
+// frc_rows_kernel, grid (tiles, blocks of the chunk), block 256 = 2 x 2 waves, each wave a 32 x 32 tile of the 64 (y) x 64 (kx) outputs:
+//   T = a (Ct + i St)[:, 0 .. n/2] for both images, four real products  a Ct, a St, b Ct, b St  that share their operands.  Per stage of
+//   32 x: the 64 x 32 bytes of both images go to LDS as floats (converted on the way; pitch 33 words, the A operand reads down a
+//   column of it), the 32 x 64 pieces of both tables beside them (the B operand reads along a row).  The bytes are loaded one per
+//   lane: a stage's row is 32 bytes at an arbitrary address, so stage_rows_u8's aligned 16-byte pieces would need a second, shifting
+//   pass through LDS (a stage is 4 KB of bytes against 64 MFMAs per wave; what the byte loads cost was not measured).  16 k-steps
+//   of v_mfma_f32_32x32x2_f32 x 4 accumulators per stage.  T goes to the workspace, [4][n][K] floats per block (a Ct, a St, b Ct, b St).
+// frc_cols_kernel, the same grid shape over 64 (ky) x 64 (kx) tiles of the spectrum: F = (Ct + i St)^T T, with the tables as the A
+//   operand (read along a row of the staged piece) and the four planes of T as B; eight MFMAs per k-step into the four accumulators
+//   Re Fa, Im Fa, Re Fb, Im Fb (- St as an operand gives the minus of the real part).  The tile of F stays in registers: each lane
+//   forms Re(Fa conj Fb), |Fa|^2, |Fb|^2 of its 16 coefficients in float32, doubled for the columns 0 < kx < n/2 that stand for
+//   their mirror images too, and puts the three products into LDS (in place of the stages).  Then thread r owns ring r: in a spectrum row
+//   the ring index is non-decreasing in kx, so the ring's coefficients of a row are one run kx in [lo, hi] that follows from
+//   integer square roots, and the thread adds the runs of the tile's rows, in row order and kx order, in float64.  It writes the
+//   three sums (zeros for a ring that misses the tile) into the tile's row of partial sums.
+// frc_fold_kernel: sums[block][r][3] = the partial rows of the block's tiles added in tile order, one thread per value.
+//
+// Padding: tiles and stages past n or K are zeros in LDS (tables and images both), never reads past a block, a table or T.
+// Determinism: every float32 product and every float64 sum has one fixed order; no atomics, no fence between workgroups.
+// Blocks are worked off in chunks that keep T and the partial rows inside FRC_WS_BYTES of workspace.
+#include "common.h"
+
+namespace {
+
+constexpr int FRC_MIN_N = 16, FRC_MAX_N = 1024;
+constexpr int FRC_TILE = 64;                    // outputs a side per workgroup (2 x 2 waves of 32 x 32)
+constexpr int FRC_KT = 32;                      // summation indices per LDS stage
+constexpr int FRC_APITCH = FRC_KT + 1;          // words per staged image row: the A operand reads down a column
+constexpr long FRC_WS_BYTES = 256L << 20;       // workspace a chunk of blocks aims to stay below
+constexpr int FRC_MAX_CHUNK = 32768;            // grid.y
+constexpr long FRC_MAX_BLOCKS = 1L << 24;       // blocks per call
+
+struct FrcGeom {
+    int n, K, R, nby, nbx, oy, ox, ty, tk, tiles;     // ty, tk: 64-tiles along y (or ky) and along kx; both passes have ty * tk tiles
+    long nblocks, per_block_bytes;
+    int chunk;
+};
+
+inline bool frc_args_ok(int planes, int H, int W, int n) {
+    if (!(planes > 0 && H > 0 && W > 0 && n >= FRC_MIN_N && n <= FRC_MAX_N && n % 2 == 0 && n <= H && n <= W)) return false;
+    return (long)planes * (H / n) * (W / n) <= FRC_MAX_BLOCKS;
+}
+
+inline FrcGeom frc_geom(int planes, int H, int W, int n) {
+    FrcGeom g;
+    g.n = n; g.K = n / 2 + 1; g.R = n / 2;
+    g.nby = H / n; g.nbx = W / n;
+    g.oy = (H - g.nby * n) / 2; g.ox = (W - g.nbx * n) / 2;
+    g.ty = cdiv(n, FRC_TILE); g.tk = cdiv(g.K, FRC_TILE);
+    g.tiles = g.ty * g.tk;
+    g.nblocks = (long)planes * g.nby * g.nbx;
+    g.per_block_bytes = (long)g.tiles * (g.R + 1) * 3 * (long)sizeof(double) + 4L * n * g.K * (long)sizeof(float);
+    long chunk = FRC_WS_BYTES / g.per_block_bytes;
+    if (chunk < 1) chunk = 1;
+    if (chunk > FRC_MAX_CHUNK) chunk = FRC_MAX_CHUNK;
+    if (chunk > g.nblocks) chunk = g.nblocks;
+    g.chunk = (int)chunk;
+    return g;
+}
+
+// floor(sqrt(v)), v >= 0 and below 2^24 (exact as a float); the two loops mend the last place of the float root
+__device__ __forceinline__ int isqrt_i(int v) {
+    int k = (int)__builtin_sqrtf((float)v);
+    while (k * k > v) --k;
+    while ((k + 1) * (k + 1) <= v) ++k;
+    return k;
+}
+
+__device__ __forceinline__ f32x16 mma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+// row of element `reg` of a lane's 32 x 32 accumulator (its column is lane & 31)
+__device__ __forceinline__ int acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+
+// A 32 x 64 piece of a row-major float matrix [rows][pitch] into lds[32][64]: rows row0 .., columns col0 .., zeros past rows / cols.
+__device__ __forceinline__ void stage_f32_32x64(const float* __restrict__ src, long pitch, int row0, int rows, int col0, int cols, float* lds) {
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+        const int idx = (int)threadIdx.x + 256 * it, r = idx >> 6, c = idx & 63;
+        float v = 0.f;
+        if (row0 + r < rows && col0 + c < cols) v = src[(long)(row0 + r) * pitch + col0 + c];
+        lds[idx] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void frc_rows_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, const float* __restrict__ ct,
+                                                       const float* __restrict__ st, float* __restrict__ T, long block0, int H, int W, int n, int nby,
+                                                       int nbx, int oy, int ox, int tk) {
+    __shared__ float la[FRC_TILE * FRC_APITCH], lb[FRC_TILE * FRC_APITCH], lc[FRC_KT * FRC_TILE], ls[FRC_KT * FRC_TILE];
+    const int K = n / 2 + 1;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wy = wave >> 1, wx = wave & 1;
+    const int y0 = (int)blockIdx.x / tk * FRC_TILE, k0 = (int)blockIdx.x % tk * FRC_TILE;
+    const long g = block0 + blockIdx.y;                         // block of the call: plane, then row and column of the grid of blocks
+    const int nb = nby * nbx, blk = (int)(g % nb);
+    const long origin = (g / nb * H + oy + blk / nbx * n) * (long)W + ox + blk % nbx * n;
+    f32x16 acc[4] = {};                                         // a Ct, a St, b Ct, b St
+    for (int x0 = 0; x0 < n; x0 += FRC_KT) {
+        uint8_t va[8], vb[8];
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int idx = tid + 256 * it, r = idx >> 5, c = idx & 31;
+            va[it] = vb[it] = 0;
+            if (y0 + r < n && x0 + c < n) {
+                const long at = origin + (long)(y0 + r) * W + x0 + c;
+                va[it] = a[at]; vb[it] = b[at];
+            }
+        }
+        stage_f32_32x64(ct, n, x0, n, k0, K, lc);
+        stage_f32_32x64(st, n, x0, n, k0, K, ls);
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int idx = tid + 256 * it, r = idx >> 5, c = idx & 31;
+            la[r * FRC_APITCH + c] = (float)va[it];
+            lb[r * FRC_APITCH + c] = (float)vb[it];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < FRC_KT / 2; ++kk) {
+            const int k = 2 * kk + (lane >> 5);
+            const float pa = la[(32 * wy + (lane & 31)) * FRC_APITCH + k], pb = lb[(32 * wy + (lane & 31)) * FRC_APITCH + k];
+            const float c = lc[k * FRC_TILE + 32 * wx + (lane & 31)], s = ls[k * FRC_TILE + 32 * wx + (lane & 31)];
+            acc[0] = mma(pa, c, acc[0]);
+            acc[1] = mma(pa, s, acc[1]);
+            acc[2] = mma(pb, c, acc[2]);
+            acc[3] = mma(pb, s, acc[3]);
+        }
+        __syncthreads();
+    }
+    float* const out = T + (long)blockIdx.y * 4 * n * K;
+    const int kx = k0 + 32 * wx + (lane & 31);
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int y = y0 + 32 * wy + acc_row(reg, lane);
+        if (y < n && kx < K)
+#pragma unroll
+            for (int m = 0; m < 4; ++m) out[((long)m * n + y) * K + kx] = acc[m][reg];
+    }
+}
+
+__global__ __launch_bounds__(256) void frc_cols_kernel(const float* __restrict__ T, const float* __restrict__ ct, const float* __restrict__ st,
+                                                       double* __restrict__ partial, int n, int tk) {
+    // stages: the tables' pieces [2][32][64] and T's four [32][64]; afterwards the three products [3][64][64]
+    __shared__ float lds[6 * FRC_KT * FRC_TILE];
+    static_assert(6 * FRC_KT * FRC_TILE >= 3 * FRC_TILE * FRC_TILE, "the products take the place of the stages");
+    const int K = n / 2 + 1, R = n / 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wy = wave >> 1, wx = wave & 1;
+    const int ky0 = (int)blockIdx.x / tk * FRC_TILE, k0 = (int)blockIdx.x % tk * FRC_TILE;
+    const float* const Tb = T + (long)blockIdx.y * 4 * n * K;
+    float* const lc = lds, * const ls = lds + FRC_KT * FRC_TILE, * const lt = lds + 2 * FRC_KT * FRC_TILE;
+    f32x16 acc[4] = {};                                         // Re Fa, Im Fa, Re Fb, Im Fb
+    for (int yy = 0; yy < n; yy += FRC_KT) {
+        stage_f32_32x64(ct, n, yy, n, ky0, n, lc);
+        stage_f32_32x64(st, n, yy, n, ky0, n, ls);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) stage_f32_32x64(Tb + (long)m * n * K, K, yy, n, k0, K, lt + m * FRC_KT * FRC_TILE);
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < FRC_KT / 2; ++kk) {
+            const int k = 2 * kk + (lane >> 5);
+            const float c = lc[k * FRC_TILE + 32 * wy + (lane & 31)], s = ls[k * FRC_TILE + 32 * wy + (lane & 31)];
+            const float* t = lt + k * FRC_TILE + 32 * wx + (lane & 31);
+            const float ar = t[0], ai = t[FRC_KT * FRC_TILE], br = t[2 * FRC_KT * FRC_TILE], bi = t[3 * FRC_KT * FRC_TILE];
+            acc[0] = mma(c, ar, acc[0]);
+            acc[1] = mma(c, ai, acc[1]);
+            acc[2] = mma(c, br, acc[2]);
+            acc[3] = mma(c, bi, acc[3]);
+            acc[0] = mma(-s, ai, acc[0]);
+            acc[1] = mma(s, ar, acc[1]);
+            acc[2] = mma(-s, bi, acc[2]);
+            acc[3] = mma(s, br, acc[3]);
+        }
+        __syncthreads();
+    }
+    // the three products of every coefficient of the tile, weighted, into LDS [3][64][64]
+    {
+        const int col = 32 * wx + (lane & 31), kx = k0 + col;
+        const float wgt = kx > 0 && kx < R ? 2.f : 1.f;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int row = 32 * wy + acc_row(reg, lane);
+            const float far = acc[0][reg], fai = acc[1][reg], fbr = acc[2][reg], fbi = acc[3][reg];
+            lds[row * FRC_TILE + col] = wgt * (far * fbr + fai * fbi);
+            lds[(FRC_TILE + row) * FRC_TILE + col] = wgt * (far * far + fai * fai);
+            lds[(2 * FRC_TILE + row) * FRC_TILE + col] = wgt * (fbr * fbr + fbi * fbi);
+        }
+    }
+    __syncthreads();
+    // ring r of the tile: per spectrum row the run of kx with floor(sqrt(fy^2 + kx^2) + 1/2) == r, that is
+    // r^2 - r + 1 <= fy^2 + kx^2 <= r^2 + r (ring 0: the origin alone), cut to the tile's valid columns
+    double* const prow = partial + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (R + 1) * 3;
+    const int klast = k0 + FRC_TILE - 1 < K - 1 ? k0 + FRC_TILE - 1 : K - 1;
+    for (int r = tid; r <= R; r += 256) {
+        double sab = 0., saa = 0., sbb = 0.;
+        for (int row = 0; row < FRC_TILE && ky0 + row < n; ++row) {
+            const int ky = ky0 + row, fy = ky <= R ? ky : ky - n, f2 = fy * fy;
+            const int hi2 = r * r + r - f2, lo2 = (r > 0 ? r * r - r + 1 : 0) - f2;
+            if (hi2 < 0) continue;
+            int lo = lo2 <= 0 ? 0 : isqrt_i(lo2 - 1) + 1, hi = isqrt_i(hi2);
+            if (lo < k0) lo = k0;
+            if (hi > klast) hi = klast;
+            for (int at = row * FRC_TILE + lo - k0; at <= row * FRC_TILE + hi - k0; ++at) {
+                sab += (double)lds[at];
+                saa += (double)lds[FRC_TILE * FRC_TILE + at];
+                sbb += (double)lds[2 * FRC_TILE * FRC_TILE + at];
+            }
+        }
+        prow[3 * r] = sab; prow[3 * r + 1] = saa; prow[3 * r + 2] = sbb;
+    }
+}
+
+// sums[block][q] = the partial rows [block][tile][q] added in tile order, q < k
+__global__ __launch_bounds__(256) void frc_fold_kernel(const double* __restrict__ partial, double* __restrict__ sums, long values, int tiles, int k) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < values; i += (long)gridDim.x * 256) {
+        const long blk = i / k;
+        const int q = (int)(i - blk * k);
+        double s = 0.;
+        for (int t = 0; t < tiles; ++t) s += partial[(blk * tiles + t) * k + q];
+        sums[i] = s;
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t pssr_frc_workspace_bytes(int planes, int H, int W, int n) {
+    if (!frc_args_ok(planes, H, W, n)) return 0;
+    const FrcGeom g = frc_geom(planes, H, W, n);
+    return (int64_t)g.chunk * g.per_block_bytes;
+}
+
+extern "C" int pssr_frc_rings_u8(const uint8_t* a, const uint8_t* b, const float* ct, const float* st, double* sums, int planes, int H, int W, int n,
+                                 void* workspace, pssr_stream_t stream) {
+    PSSR_CHECK(a && b && ct && st && sums && workspace, PSSR_ERR_ARG, "frc_rings_u8: null pointer");
+    PSSR_CHECK(planes > 0 && H > 0 && W > 0, PSSR_ERR_ARG, "frc_rings_u8: planes, H and W must be positive (%d, %d, %d)", planes, H, W);
+    PSSR_CHECK(n >= FRC_MIN_N && n <= FRC_MAX_N && n % 2 == 0, PSSR_ERR_ARG, "frc_rings_u8: the block side must be even and in %d .. %d, given %d",
+               FRC_MIN_N, FRC_MAX_N, n);
+    PSSR_CHECK(n <= H && n <= W, PSSR_ERR_ARG, "frc_rings_u8: a block of %d does not fit a %d x %d plane", n, H, W);
+    PSSR_CHECK(frc_args_ok(planes, H, W, n), PSSR_ERR_ARG, "frc_rings_u8: %ld blocks in all (at most 2^24 per call)", (long)planes * (H / n) * (W / n));
+    const FrcGeom g = frc_geom(planes, H, W, n);
+    const int k = (g.R + 1) * 3;
+    double* const partial = (double*)workspace;
+    float* const T = (float*)((char*)workspace + (long)g.chunk * g.tiles * k * (long)sizeof(double));
+    hipStream_t s = (hipStream_t)stream;
+    for (long block0 = 0; block0 < g.nblocks; block0 += g.chunk) {
+        const int count = (int)(g.nblocks - block0 < g.chunk ? g.nblocks - block0 : g.chunk);
+        hipLaunchKernelGGL(frc_rows_kernel, dim3(g.tiles, count), dim3(256), 0, s, a, b, ct, st, T, block0, H, W, n, g.nby, g.nbx, g.oy, g.ox, g.tk);
+        PSSR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(frc_cols_kernel, dim3(g.tiles, count), dim3(256), 0, s, (const float*)T, ct, st, partial, n, g.tk);
+        PSSR_LAUNCH_CHECK();
+        const long values = (long)count * k;
+        hipLaunchKernelGGL(frc_fold_kernel, dim3(grid1d(values, 4096)), dim3(256), 0, s, (const double*)partial, sums + block0 * k, values, g.tiles, k);
+        PSSR_LAUNCH_CHECK();
+    }
+    return PSSR_OK;
+}

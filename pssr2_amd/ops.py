@@ -1192,3 +1192,70 @@ def crop_shift_u8(x, origins, ho, wo, *, table=None):
     out = torch.empty(*x.shape[:-2], ho, wo, dtype=torch.uint8, device=x.device)
     L.check(L.lib().pssr_crop_shift_u8(L.ptr(x), L.ptr(out), L.ptr(table), planes, H, W, ho, wo, L.stream_ptr()), "pssr_crop_shift_u8")
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# Fourier ring correlation (csrc/frc.hip; definitions in include/pssr_mi355.h)
+FRC_WINDOWS = ("hann", "none")       # frc's ``window``
+FRC_MIN_BLOCK, FRC_MAX_BLOCK = 16, 1024
+
+_FRC_TABLES = {}                     # (n, window) -> (ct, st) float32 numpy
+_FRC_DEVICE_TABLES = {}              # (n, window, device) -> their device copies, kept for the life of the process (8 MB a pair at n = 1024)
+
+
+def _check_frc_block(who, block):
+    if isinstance(block, bool) or not isinstance(block, int) or block % 2 or not FRC_MIN_BLOCK <= block <= FRC_MAX_BLOCK:
+        raise ValueError(f"{who}: block must be an even int in {FRC_MIN_BLOCK} .. {FRC_MAX_BLOCK}. Given {block!r}.")
+
+
+def frc_tables(n, window="hann"):
+    """The tables of ``pssr_frc_rings_u8`` (step 1 of include/pssr_mi355.h) -> ``(ct, st)``, float32 numpy [n, n]:
+    ``ct[x, k] = w[x] cos(2 pi ((x k) mod n) / n)``, ``st[x, k] = -w[x] sin(2 pi ((x k) mod n) / n)`` with ``w[x] = sin(pi (x + 1/2) / n)**2``
+    (``"hann"``) or 1 (``"none"``); float64 on the host, rounded once."""
+    import numpy as np
+    _check_frc_block("frc_tables", n)
+    if window not in FRC_WINDOWS:
+        raise ValueError(f"window must be one of {FRC_WINDOWS}. Given {window!r}.")
+    if (n, window) not in _FRC_TABLES:
+        x = np.arange(n, dtype=np.int64)
+        w = np.sin(np.pi * (x + 0.5) / n) ** 2 if window == "hann" else np.ones(n)
+        angle = 2.0 * np.pi * ((x[:, None] * x[None, :]) % n) / n
+        _FRC_TABLES[n, window] = ((w[:, None] * np.cos(angle)).astype(np.float32), (-w[:, None] * np.sin(angle)).astype(np.float32))
+    return _FRC_TABLES[n, window]
+
+
+def _frc_device_tables(n, window, device):
+    key = (n, window, torch.device(device))
+    if key not in _FRC_DEVICE_TABLES:
+        _FRC_DEVICE_TABLES[key] = tuple(torch.from_numpy(t).to(device) for t in frc_tables(n, window))
+        torch.cuda.current_stream(key[2]).synchronize()        # uploaded once: whichever stream uses them later finds them written
+    return _FRC_DEVICE_TABLES[key]
+
+
+def frc_rings_u8(a, b, block, window="hann"):
+    """uint8 device tensors ``a`` and ``b`` of the same shape [..., H, W], an even block side ``block`` in 16 .. 1024 (at most
+    ``min(H, W)``) -> float64 device tensor [planes, nby * nbx, block // 2 + 1, 3]: per plane, per block of the centred grid of
+    ``(H // block) x (W // block)`` blocks and per ring of spatial frequency the sums ``Re(Fa conj Fb), |Fa|**2, |Fb|**2`` over the
+    windowed spectra of the two blocks.  Two matrix products per block on the f32-input MFMA and a fixed-order reduction: the same bits on
+    every call."""
+    if not (torch.is_tensor(a) and torch.is_tensor(b)) or a.dtype != torch.uint8 or b.dtype != torch.uint8 or not (a.is_cuda and b.is_cuda) \
+            or a.dim() < 2 or a.shape != b.shape:
+        raise ValueError("frc_rings_u8 needs two uint8 device tensors of the same shape [..., H, W]")
+    _check_frc_block("frc_rings_u8", block)
+    if window not in FRC_WINDOWS:
+        raise ValueError(f"window must be one of {FRC_WINDOWS}. Given {window!r}.")
+    H, W = a.shape[-2:]
+    if block > min(H, W):
+        raise ValueError(f"frc_rings_u8: a block of {block} does not fit a {H}x{W} plane")
+    planes = a.numel() // (H * W)
+    nb = (H // block) * (W // block)
+    if planes < 1 or planes * nb > 1 << 24:
+        raise ValueError(f"frc_rings_u8: {planes} planes of {nb} blocks (at least one plane, at most 2**24 blocks in all)")
+    a, b = a.contiguous(), b.contiguous()
+    ct, st = _frc_device_tables(block, window, a.device)
+    lib = L.lib()
+    ws = torch.empty(lib.pssr_frc_workspace_bytes(planes, H, W, block), dtype=torch.uint8, device=a.device)
+    sums = torch.empty(planes, nb, block // 2 + 1, 3, dtype=torch.float64, device=a.device)
+    L.check(lib.pssr_frc_rings_u8(L.ptr(a), L.ptr(b), L.ptr(ct), L.ptr(st), L.ptr(sums), planes, H, W, block, L.ptr(ws), L.stream_ptr()),
+            "pssr_frc_rings_u8")
+    return sums

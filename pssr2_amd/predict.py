@@ -484,7 +484,11 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
 
     ``metrics`` may also name ``"rse"`` and ``"rsp"`` (not in the default tuple): the two summary numbers of ``util.consistency_map``
     (with ``fit``) of the cropped prediction, before ``norm``, against the item's own LR side -- the resolution-scaled error in grey
-    levels and the Pearson correlation, which need no ground truth -- per image the mean over its planes."""
+    levels and the Pearson correlation, which need no ground truth -- per image the mean over its planes.
+
+    ``metrics`` may name ``"frc"`` too (not in the default tuple either): the resolution that the prediction reached, in HR pixels --
+    ``util.frc`` with its defaults (one block per plane, Hann window, the 1/7 threshold) of the cropped uint8 prediction, before ``norm``,
+    against the cropped ground truth, the image's planes pooled.  A call that does not name it launches what it launched before."""
     import math
     from .util import pixel_metric
     _check_ensemble(ensemble, device)
@@ -493,6 +497,8 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
     image_range = 255
     metrics = [metrics] if type(metrics) is str else list(metrics)
     out = {m: [] for m in metrics}
+    if "frc" in out and torch.device(device).type != "cuda":                   # as _check_ensemble: before model, dataset or device are touched
+        raise RuntimeError("pssr2_amd.predict runs on an MI355X (HIP) device only; there is no CPU fallback")
     model.to(device)
     model.eval()
 
@@ -513,6 +519,9 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
                 for name in ("rse", "rsp"):
                     if name in out:
                         out[name].extend(sum(v.tolist()) / len(v) for v in getattr(cons, name))
+            if "frc" in out:
+                from .util import frc
+                out["frc"].extend(frc(hat_dev, hr_dev).resolution.tolist())
             if norm:
                 hr_dev, hat_dev = ops.normalize_preds_u8(hr_dev, hat_dev)
             n, c, h, w = hr_dev.shape

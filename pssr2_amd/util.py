@@ -462,6 +462,98 @@ def register_pairs(hr, lr, *, radius: int = 8, to_numpy: bool = True):
     return Registration(hr_out, lr_out, shift, score, m)
 
 
+FRC = namedtuple("FRC", "curve freq resolution crossed block")
+
+
+def _frc_resolve(sums, n: int, threshold: float, smooth: int, pixel_size: float):
+    """``(curve, resolution, crossed)`` of one item from the ring sums of its planes and blocks (``sums``: float64 [..., n // 2 + 1, 3],
+    the layout of ``pssr_frc_rings_u8``; every leading axis pools), in exactly the expressions of step 5 of include/pssr_mi355.h: the
+    sums add ring by ring, ``smooth = k`` gives ring ``r >= 1`` the sums of rings ``max(1, r - k) .. min(R, r + k)`` (ring 0 stays alone),
+    ``frc[r] = Sab / sqrt(Saa Sbb)`` (0 where ``Saa Sbb <= 0``), the first ``r >= 1`` below ``threshold`` is crossed at
+    ``r* = (r - 1) + (frc[r-1] - threshold) / (frc[r-1] - frc[r])`` (``r* = 1`` where ring 0 lies below the threshold too) and
+    ``resolution = pixel_size n / r*``; without a crossing the resolution is the sampling limit ``2 pixel_size``.  No device involved."""
+    R = n // 2
+    pooled = np.asarray(sums, dtype=np.float64).reshape(-1, R + 1, 3).sum(axis=0)
+    rings = pooled.copy()
+    for r in range(1, R + 1):
+        rings[r] = pooled[max(1, r - smooth):min(R, r + smooth) + 1].sum(axis=0)
+    curve = np.zeros(R + 1, dtype=np.float64)
+    for r in range(R + 1):
+        sab, saa, sbb = (float(v) for v in rings[r])
+        if saa * sbb > 0:
+            curve[r] = sab / math.sqrt(saa * sbb)
+    for r in range(1, R + 1):
+        if curve[r] < threshold:
+            before, here = float(curve[r - 1]), float(curve[r])
+            r_star = (r - 1) + (before - threshold) / (before - here) if before >= threshold else 1.0
+            return curve, (pixel_size * n / r_star if r_star > 0 else math.inf), True
+    return curve, 2.0 * pixel_size, False
+
+
+def frc(a, b, *, block=None, window: str = "hann", threshold: float = 1 / 7, smooth: int = 0, pixel_size: float = 1.0, to_numpy: bool = True):
+    r"""Fourier ring correlation of two images of one field: down to which detail size they agree -- a prediction against its ground truth,
+    or two predictions of independent acquisitions.  ``a``, ``b``: uint8 arrays or device tensors of the same shape [N, C, H, W] (or one
+    [C, H, W] or [H, W] pair).  Each plane is cut into the centred grid of ``block x block`` blocks (``block`` even, 16 .. 1024;
+    ``None``: the largest even side that fits, one block per plane up to 1024 pixels), each block is windowed (``"hann"``, or ``"none"``)
+    and transformed, and the two spectra are correlated ring by ring of spatial frequency; an item's planes and blocks pool their sums
+    (include/pssr_mi355.h has the definitions).  Returns ``FRC(curve, freq, resolution, crossed, block)``:
+
+    * ``curve``: float64 [N, block // 2 + 1], the correlation of ring ``r``; ``freq``: float64 [block // 2 + 1], ``r / block`` in cycles per
+      pixel; ``smooth=k`` pools rings ``r - k .. r + k`` first (never ring 0);
+    * ``resolution``: float64 [N], ``pixel_size * block / r*`` at the first crossing ``r*`` of ``threshold`` (1/7 by convention), linearly
+      interpolated between rings; ``crossed``: bool [N], ``False`` where the curve never falls below the threshold, and the resolution is
+      then the sampling limit ``2 * pixel_size``.
+
+    One sums launch for the whole batch (``pssr_frc_rings_u8``: two matrix products per block on the f32-input MFMA, ring sums in float64 in
+    a fixed order) and one copy of the sums to the host; the curve and the crossing are Python floats.  A pair without the batch axis gets
+    ``curve`` [block // 2 + 1] and scalars.  ``to_numpy=False`` leaves ``curve`` on the device."""
+    if window not in ops.FRC_WINDOWS:
+        raise ValueError(f"window must be one of {ops.FRC_WINDOWS}. Given {window!r}.")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or not 0 < threshold < 1:
+        raise ValueError(f"threshold must be a number inside (0, 1). Given {threshold!r}.")
+    if isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)) or smooth < 0:
+        raise ValueError(f"smooth must be a non-negative int (rings pooled on either side). Given {smooth!r}.")
+    if isinstance(pixel_size, bool) or not isinstance(pixel_size, (int, float, np.integer, np.floating)) or not pixel_size > 0:
+        raise ValueError(f"pixel_size must be a positive number. Given {pixel_size!r}.")
+    tensors = []
+    for name, t in (("a", a), ("b", b)):
+        host = torch.is_tensor(t) and not t.is_cuda
+        if not torch.is_tensor(t):
+            t = torch.as_tensor(np.ascontiguousarray(t))
+        if t.dtype != torch.uint8:
+            raise TypeError(f"frc takes uint8 images; {name} is {t.dtype}")
+        if host:
+            raise RuntimeError("pssr2_amd.util.frc runs on an MI355X (HIP) device only; there is no CPU fallback")
+        tensors.append(t)
+    a, b = tensors
+    if a.shape != b.shape or a.dim() not in (2, 3, 4):
+        raise ValueError("a and b must have the same shape, [images, planes, height, width] or one [planes, height, width] or [height, width] "
+                         f"pair. Shapes are {tuple(a.shape)} and {tuple(b.shape)} respectively.")
+    batched = a.dim() == 4
+    a, b = a.reshape((1,) * (4 - a.dim()) + tuple(a.shape)), b.reshape((1,) * (4 - b.dim()) + tuple(b.shape))
+    n_img, c, H, W = a.shape
+    if min(n_img, c) < 1 or min(H, W) < ops.FRC_MIN_BLOCK:
+        raise ValueError(f"frc needs at least one plane of at least {ops.FRC_MIN_BLOCK}x{ops.FRC_MIN_BLOCK} pixels. The shape is {tuple(a.shape)}.")
+    if block is None:
+        block = min(H, W, ops.FRC_MAX_BLOCK) // 2 * 2
+    elif isinstance(block, bool) or not isinstance(block, (int, np.integer)) or block % 2 or not ops.FRC_MIN_BLOCK <= block <= min(H, W, ops.FRC_MAX_BLOCK):
+        raise ValueError(f"block must be an even int from {ops.FRC_MIN_BLOCK} to {min(H, W, ops.FRC_MAX_BLOCK)} (the smaller side, at most "
+                         f"{ops.FRC_MAX_BLOCK}). Given {block!r}.")
+    block, smooth = int(block), int(smooth)
+    if not (a.is_cuda or b.is_cuda or torch.cuda.is_available()):
+        raise RuntimeError("pssr2_amd.util.frc needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
+    dev = a.device if a.is_cuda else (b.device if b.is_cuda else "cuda")
+    sums = ops.frc_rings_u8(a.to(dev), b.to(dev), block, window).cpu().numpy().reshape(n_img, -1, block // 2 + 1, 3)
+    items = [_frc_resolve(sums[i], block, float(threshold), smooth, float(pixel_size)) for i in range(n_img)]
+    curve = np.stack([it[0] for it in items])
+    resolution = np.array([it[1] for it in items], dtype=np.float64)
+    crossed = np.array([it[2] for it in items], dtype=bool)
+    freq = np.arange(block // 2 + 1, dtype=np.float64) / block
+    if not batched:
+        curve, resolution, crossed = curve[0], float(resolution[0]), bool(crossed[0])
+    return FRC(curve if to_numpy else torch.from_numpy(curve).to(dev), freq, resolution, crossed, block)
+
+
 def _sort_tiles(name: str):
     """Sort key of tile names ``{sheet}_{tile}_{slice}[.ext]`` (pssr/util.py:110-114): slice first, then tile."""
     if "." not in name:
