@@ -823,6 +823,53 @@ int pssr_register_shifts_u8(const uint8_t* hr, const uint8_t* lr, uint64_t* sums
 int pssr_crop_shift_u8(const uint8_t* in, uint8_t* out, const int32_t* origins, int planes, int H, int W, int ho, int wo,
                        pssr_stream_t stream);
 
+/* Estimate of the resolution-scaling function (RSF): an exhaustive search over candidate blurs (pssr2_amd.util.estimate_rsf,
+ * consistency_map(rsf=...); csrc/rsf.hip).  The resolution-scaled error of the literature is defined after a Gaussian has been fitted
+ * between the sharp image and the measured one; the consistency block above stops at Pillow's bilinear reduction.  For every candidate
+ * sigma the best intensity fit L ~ alpha D_sigma + beta has the residual denl (1 - rho^2) / n, so the best sigma has the largest signed
+ * squared Pearson correlation: the score of the registration block, over blurs instead of shifts.  After the tap table everything is
+ * integer arithmetic.
+ * Inputs, per plane pair: Y uint8 [s*h][s*w] (the sharp side), L uint8 [h][w] (the measured side), s an integer in 1 .. 16, a radius R in
+ * HR pixels, 0 .. 32, K candidates, 1 .. 64.
+ *   1. Tap table.  taps int32 [K][NT], NT = 2 s + 2 R, made on the host; it is the caller's contract, as the FRC tables and lut are
+ *      (pssr2_amd.ops.rsf_taps makes it, ops.rsf_moments_u8 checks it).  Every row is non-negative; a row of sigma > 0 sums to exactly 2^22, the row of
+ *      sigma = 0 to whatever Pillow's interior taps sum to (2^22 + e, |e| <= 6: e = 1 at s = 3, 0 at s = 1, 2, 4, 8, 16; Pillow rounds
+ *      each tap on its own, and this row must stay Pillow's bit for bit).  For the candidates sigma_k: rad_k = 0 for sigma_k = 0, else ceil(3 sigma_k); R = max rad_k unless a larger one is given.  The row of
+ *      sigma_k = 0 is the 2 s interior taps of the registration block (step 1 there) at columns R .. R + 2 s, zeros elsewhere.  For
+ *      sigma_k > 0: the float64 Gaussian g[i] = exp(-i^2 / (2 sigma^2)), |i| <= rad_k, normalised to sum 1; convolved with the interior
+ *      taps divided by 2^22 (2 s + 2 rad_k values c[n] = sum_i g[i] t[n - i]); rounded as floor(c 2^22 + 1/2); the difference of their
+ *      sum to 2^22 added to the first largest tap; placed at columns R - rad_k .. R + rad_k + 2 s, zeros elsewhere.  The Gaussian's
+ *      sum and every c[n] are correctly rounded sums of float64 terms (math.fsum), so the table does not depend on an order of addition.
+ *   2. Margin.  m = 1 + ceil(R / s) LR pixels; h' = h - 2m and w' = w - 2m must both be >= 1, otherwise PSSR_ERR_ARG.  No candidate
+ *      touches a border tap or leaves Y.
+ *   3. Blurred reduction per candidate.  Horizontal pass first: T_k[r][x] = clip8(2^21 + sum_j taps[k][j] Y[r][s (x + m) - floor(s/2) - R + j]),
+ *      0 <= x < w', j < NT; then the vertical pass, the same on the columns of T_k: D_k[y][x] = clip8(2^21 + sum_j taps[k][j]
+ *      T_k[s (y + m) - floor(s/2) - R + j][x]), 0 <= y < h'.  clip8(v) = min(max(v >> 22, 0), 255), as in pssr_bilinear_down_u8.
+ *      Consequence: with the row of sigma = 0, D == pssr_bilinear_down_u8(Y)[m : h - m, m : w - m] bit for bit, whatever R.
+ *   4. Sums.  Lc = L[m : h - m, m : w - m].  Per plane and candidate: Sd = sum D_k, Sdd = sum D_k^2, Sdl = sum D_k Lc; per plane:
+ *      Sl = sum Lc, Sll = sum Lc^2.  All exact unsigned 64-bit integers.  Limits: s h, s w < 2^30 and h w <= 2^28.
+ *   5. Choice (host, Python ints).  The pooled planes add their sums, n = their pixels.  num_k = n Sdl - Sd Sl, den_k = n Sdd - Sd^2,
+ *      denl = n Sll - Sl^2.  The score is num_k |num_k| / (den_k denl), taken as 0 when den_k = 0 or denl = 0; scores are compared by
+ *      cross-multiplying integers.  The largest wins, ties go to the smaller k (a constant pair therefore chooses candidate 0).  The
+ *      reported correlation is the float num / sqrt(den denl).
+ * pssr_rsf_moments_u8: steps 2 - 4 in one fused pass.  y [planes][s*h][s*w], l [planes][h][w], taps [K][NT] (device), sums
+ *   [planes][3K + 2]: K triples (Sd, Sdd, Sdl), then Sl, Sll -- the layout of pssr_register_shifts_u8 with T = K.  Every byte of y is read
+ *   from HBM about once for all K candidates; T_k and D_k never leave LDS; a row of the table costs the taps between its first and last
+ *   non-zero column only.
+ * pssr_rsf_reduce_u8: d[p] = D_sel[p], uint8 [planes][h'][w'], for a device table sel [planes] of candidate indices.  Its values are the
+ *   caller's contract (0 <= sel[p] < K; pssr2_amd.ops.rsf_reduce_u8 checks them); no row outside the table is read either way.
+ * pssr_rsf_block: the side B of the square blocks of outputs a workgroup owns at (s, radius), 0 for an s or a radius out of range.
+ * Both kernels' entry points validate on the host before anything is launched (null pointers, planes, sizes, s outside 1 .. 16, K outside
+ * 1 .. 64, radius outside 0 .. 32, h' or w' < 1, the limits of step 4): PSSR_ERR_ARG with a message.  Integer sums through per-workgroup
+ * 64-bit partials in the workspace and a second small launch: no atomics, no fence, no floating point, the same bits on every run.
+ * Workspace of pssr_rsf_moments_workspace_bytes bytes (0 for arguments the entry point rejects). */
+int pssr_rsf_block(int s, int radius);
+int64_t pssr_rsf_moments_workspace_bytes(int planes, int h, int w, int s, int K, int radius);
+int pssr_rsf_moments_u8(const uint8_t* y, const uint8_t* l, const int32_t* taps, uint64_t* sums, int planes, int h, int w, int s, int K,
+                        int radius, void* workspace, pssr_stream_t stream);
+int pssr_rsf_reduce_u8(const uint8_t* y, const int32_t* taps, const int32_t* sel, uint8_t* d, int planes, int h, int w, int s, int K,
+                       int radius, pssr_stream_t stream);
+
 /* Fourier ring correlation (FRC): down to which detail size two images of one field agree (pssr2_amd.util.frc; csrc/frc.hip) -- a
  * prediction against its ground truth, or two predictions of independent acquisitions.  The correlation of the two spectra, ring by ring
  * in spatial frequency, read off where it falls through a threshold (1/7 by convention).

@@ -55,6 +55,9 @@ def __getattr__(name):
     if name in ("frc",):
         from .util import frc
         return frc
+    if name in ("estimate_rsf",):
+        from .util import estimate_rsf
+        return estimate_rsf
     if name in ("FusedAdamW",):
         from .optim import FusedAdamW
         return FusedAdamW

@@ -143,6 +143,12 @@ def lib():
         _lib.pssr_register_shifts_workspace_bytes.argtypes = [c_int] * 5
         _lib.pssr_register_shifts_u8.argtypes = [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 2
         _lib.pssr_crop_shift_u8.argtypes = [c_void_p] * 3 + [c_int] * 5 + [c_void_p]
+        # estimate of the resolution-scaling function (csrc/rsf.hip)
+        _lib.pssr_rsf_block.argtypes = [c_int] * 2
+        _lib.pssr_rsf_moments_workspace_bytes.restype = c_i64
+        _lib.pssr_rsf_moments_workspace_bytes.argtypes = [c_int] * 6
+        _lib.pssr_rsf_moments_u8.argtypes = [c_void_p] * 4 + [c_int] * 6 + [c_void_p] * 2
+        _lib.pssr_rsf_reduce_u8.argtypes = [c_void_p] * 4 + [c_int] * 6 + [c_void_p]
         # Fourier ring correlation (csrc/frc.hip)
         _lib.pssr_frc_workspace_bytes.restype = c_i64
         _lib.pssr_frc_workspace_bytes.argtypes = [c_int] * 4

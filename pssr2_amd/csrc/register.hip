@@ -102,18 +102,6 @@ __device__ __forceinline__ void filter_pass(const uint8_t* src, int spitch, int 
     }
 }
 
-// An item's sums of one block of outputs into its three slots of the workgroup's partial row: the first block of a run writes them, the
-// later ones add (a slot is written by one thread only, in program order).  The item "D = Lc" has no third slot.
-__device__ __forceinline__ void slots_update(u64* slot, bool first, bool third, u64 sd, u64 sdd, u64 sdl) {
-    if (first) {
-        slot[0] = sd; slot[1] = sdd;
-        if (third) slot[2] = sdl;
-    } else {
-        slot[0] += sd; slot[1] += sdd;
-        if (third) slot[2] += sdl;
-    }
-}
-
 __global__ __launch_bounds__(256) void register_shifts_kernel(const uint8_t* __restrict__ hr, const uint8_t* __restrict__ lr, u64* __restrict__ partial,
                                                               const int* __restrict__ taps, int planes, int h, int w, int s, int R, int B,
                                                               int G, int tiles_x, int tiles) {

@@ -1,5 +1,6 @@
 // The steps shared by the kernels that score a uint8 HR-side plane [s*h][s*w] against a uint8 LR-side plane [h][w] through Pillow's
-// bilinear forward model: the fused reduction + moments and the map of consistency.hip, the shift search of register.hip.  The one
+// bilinear forward model: the fused reduction + moments and the map of consistency.hip, the shift search of register.hip, the blur search
+// of rsf.hip.  The one
 // copy of the argument checks of such a pair, of the grid sizing (workgroups per plane, a run of blocks of outputs per workgroup), of
 // the staging of raw rows into LDS, of the workgroup sum and of the fold of the workgroups' partial rows.
 #pragma once
@@ -103,6 +104,19 @@ __device__ __forceinline__ u64 block_sum_u64(u64 v, u64* red4) {
     const u64 r = (red4[0] + red4[1]) + (red4[2] + red4[3]);
     __syncthreads();
     return r;
+}
+
+// An item's sums of one block of outputs into its three slots of the workgroup's partial row (the search kernels of register.hip and
+// rsf.hip: an item is a shift or a candidate): the first block of a run writes them, the later ones add (a slot is written by one thread
+// only, in program order).  The item "D = Lc" has no third slot.
+__device__ __forceinline__ void slots_update(u64* slot, bool first, bool third, u64 sd, u64 sdd, u64 sdl) {
+    if (first) {
+        slot[0] = sd; slot[1] = sdd;
+        if (third) slot[2] = sdl;
+    } else {
+        slot[0] += sd; slot[1] += sdd;
+        if (third) slot[2] += sdl;
+    }
 }
 
 // out[pl][q] = sum_row partial[pl][row][q], q < k: the second launch behind every kernel that leaves one row of 64-bit partial sums per

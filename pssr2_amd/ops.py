@@ -1195,6 +1195,162 @@ def crop_shift_u8(x, origins, ho, wo, *, table=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# estimate of the resolution-scaling function (csrc/rsf.hip; definitions in include/pssr_mi355.h)
+MAX_RSF_CANDIDATES = 64
+RSF_PRECISION_BITS = 22              # PRECISION_BITS of csrc/pil_taps.h: a row of a tap table of sigma > 0 sums to 1 << 22
+
+
+def _interior_taps(s):
+    """The ``2 s`` fixed-point coefficients of an interior output of Pillow's BILINEAR reduction by the integer ``s`` (step 1 of the
+    registration block of include/pssr_mi355.h; the device copy is csrc/pil_taps.h): Pillow's precompute_coeffs + normalize_coeffs_8bpc
+    for output 1 of 4 reduced from ``4 s``, in Python floats (C doubles) and Pillow's order of operations."""
+    in_size, out_size = 4 * s, 4
+    scale = in_size / out_size
+    support = scale if scale > 1.0 else 1.0
+    ss = 1.0 / support
+    center = 1.5 * scale
+    xmin, xmax = max(int(center - support + 0.5), 0), min(int(center + support + 0.5), in_size)
+    ws = []
+    for x in range(xmax - xmin):
+        a = abs((x + xmin - center + 0.5) * ss)
+        ws.append(1.0 - a if a < 1.0 else 0.0)
+    ww = 0.0
+    for v in ws:
+        ww += v
+    return [int(0.5 + (v / ww if ww != 0.0 else v) * (1 << RSF_PRECISION_BITS)) for v in ws]
+
+
+def rsf_radius(sigma):
+    """HR pixels the Gaussian of ``sigma`` reaches to either side in a tap table: 0 for ``sigma = 0``, else ``ceil(3 sigma)``."""
+    import math
+    return 0 if sigma == 0 else math.ceil(3 * sigma)
+
+
+def rsf_taps(s, sigmas, radius=None):
+    """The tap table of ``pssr_rsf_moments_u8`` (step 1 of include/pssr_mi355.h) for the scale ``s`` (1 .. 16) and the candidate widths
+    ``sigmas`` (1 .. 64 finite numbers >= 0, in HR pixels, ``ceil(3 sigma) <= 32``) -> ``(taps, R)``: int32 numpy [K, 2 s + 2 R], every row
+    non-negative with the sum ``1 << 22`` (the row of ``sigma = 0``: the sum of Pillow's own taps, which is ``(1 << 22) + 1`` at ``s = 3``),
+    and ``R = max ceil(3 sigma)`` unless ``radius`` gives it.  Row ``k`` is Pillow's ``2 s`` interior
+    taps convolved with the normalised float64 Gaussian of ``sigma_k`` (every sum the correctly rounded ``math.fsum``), rounded to 22 bits, the
+    rounding's remainder added to the first largest tap; the row of ``sigma = 0`` is the interior taps themselves."""
+    import math
+    import numpy as np
+    if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 1 <= s <= 16:
+        raise ValueError(f"rsf_taps: the scale must be an int in 1 .. 16. Given {s!r}.")
+    s = int(s)
+    try:
+        sig = [float(v) for v in sigmas]
+    except (TypeError, ValueError):
+        raise ValueError(f"rsf_taps: sigmas must be a sequence of numbers. Given {sigmas!r}.") from None
+    if not 1 <= len(sig) <= MAX_RSF_CANDIDATES:
+        raise ValueError(f"rsf_taps: 1 .. {MAX_RSF_CANDIDATES} candidate sigmas. Given {len(sig)}.")
+    if any(not math.isfinite(v) or v < 0 for v in sig):
+        raise ValueError(f"rsf_taps: every sigma must be finite and >= 0. Given {sig}.")
+    rads = [rsf_radius(v) for v in sig]
+    if max(rads) > MAX_REGISTER_RADIUS:
+        raise ValueError(f"rsf_taps: ceil(3 sigma) must be at most {MAX_REGISTER_RADIUS} HR pixels. Given sigma = {max(sig)}.")
+    if radius is None:
+        radius = max(rads)
+    elif isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not max(rads) <= radius <= MAX_REGISTER_RADIUS:
+        raise ValueError(f"rsf_taps: radius must be an int from {max(rads)} (the largest ceil(3 sigma)) to {MAX_REGISTER_RADIUS}. Given {radius!r}.")
+    radius, one = int(radius), 1 << RSF_PRECISION_BITS
+    interior = _interior_taps(s)
+    t = [k / one for k in interior]
+    table = np.zeros((len(sig), 2 * s + 2 * radius), dtype=np.int32)
+    for row, sigma, rad in zip(table, sig, rads):
+        if sigma == 0:
+            row[radius:radius + 2 * s] = interior
+            continue
+        g = [math.exp(-(i * i) / (2.0 * sigma * sigma)) for i in range(-rad, rad + 1)]
+        total = math.fsum(g)
+        g = [v / total for v in g]
+        ks = []
+        for n in range(2 * s + 2 * rad):
+            c = math.fsum(g[i] * t[n - i] for i in range(max(0, n - 2 * s + 1), min(n, 2 * rad) + 1))
+            ks.append(math.floor(c * one + 0.5))
+        ks[ks.index(max(ks))] += one - sum(ks)
+        row[radius - rad:radius + rad + 2 * s] = ks
+    return table, radius
+
+
+def _rsf_table(who, taps, radius, s=None):
+    """The checks of a host tap table: int [K, 2 s + 2 radius], ``K`` in 1 .. 64, ``radius`` in 0 .. 32, rows non-negative with the sum
+    ``1 << 22`` or that of Pillow's interior taps at this scale -> ``(int32 numpy table, K, s)``."""
+    import numpy as np
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= MAX_REGISTER_RADIUS:
+        raise ValueError(f"{who}: the radius must be an int in 0 .. {MAX_REGISTER_RADIUS} HR pixels. Given {radius!r}.")
+    if torch.is_tensor(taps):
+        if taps.is_cuda:
+            raise ValueError(f"{who} takes the tap table on the host (it is checked there and uploaded)")
+        taps = taps.numpy()
+    taps = np.asarray(taps)
+    if taps.ndim != 2 or taps.dtype.kind not in "iu" or not 1 <= taps.shape[0] <= MAX_RSF_CANDIDATES:
+        raise ValueError(f"{who} needs an integer tap table [K, 2 s + 2 radius] with K in 1 .. {MAX_RSF_CANDIDATES} (ops.rsf_taps makes it)")
+    nt = taps.shape[1] - 2 * int(radius)
+    if nt < 2 or nt % 2 or nt // 2 > 16 or (s is not None and nt != 2 * s):
+        want = f"2 * {s} + 2 * {radius}" if s is not None else f"2 s + 2 * {radius}, s in 1 .. 16,"
+        raise ValueError(f"{who}: a tap table of {taps.shape[1]} columns does not have the {want} columns of radius {radius}")
+    wide = taps.astype(np.int64)
+    one, plain = 1 << RSF_PRECISION_BITS, sum(_interior_taps(nt // 2))
+    if (wide < 0).any() or ((wide.sum(axis=1) != one) & (wide.sum(axis=1) != plain)).any():
+        raise ValueError(f"{who}: every row of the tap table must be non-negative and sum to {one}"
+                         + (f" (or to {plain}, as Pillow's own taps at this scale do)" if plain != one else ""))
+    return np.ascontiguousarray(wide.astype(np.int32)), taps.shape[0], nt // 2
+
+
+def rsf_moments_u8(y, l, taps, radius):
+    """uint8 device tensors ``y`` [..., s*h, s*w] and ``l`` [..., h, w], the same leading dimensions, ``s`` an integer in 1 .. 16, the host
+    tap table ``taps`` int [K, 2 s + 2 radius] of ``rsf_taps`` (checked here: shape, sign and row sums; then uploaded) -> int64
+    [planes, 3 K + 2]: per plane and candidate ``k`` the exact ``sum D, sum D*D, sum D*Lc`` of ``D_k``, ``y`` blurred and reduced to the LR grid
+    by row ``k`` in two strided passes, against ``Lc = l[m:h-m, m:w-m]``, ``m = register_margin(s, radius)``, then ``sum Lc, sum Lc*Lc``.
+    One fused pass over ``y`` for all candidates."""
+    y, l, planes, h, w, s = _u8_plane_pair("rsf_moments_u8", y, l, "sharp image")
+    table, K, _ = _rsf_table("rsf_moments_u8", taps, radius, s)
+    radius = int(radius)
+    m = register_margin(s, radius)
+    if h - 2 * m < 1 or w - 2 * m < 1:
+        raise ValueError(f"rsf_moments_u8: a {h}x{w} LR image leaves nothing inside the margin of {m} pixels on every side")
+    lib = L.lib()
+    dev_taps = torch.from_numpy(table).to(y.device)
+    ws = torch.empty(lib.pssr_rsf_moments_workspace_bytes(planes, h, w, s, K, radius), dtype=torch.uint8, device=y.device)
+    sums = torch.empty(planes, 3 * K + 2, dtype=torch.int64, device=y.device)
+    L.check(lib.pssr_rsf_moments_u8(L.ptr(y), L.ptr(l), L.ptr(dev_taps), L.ptr(sums), planes, h, w, s, K, radius, L.ptr(ws), L.stream_ptr()),
+            "pssr_rsf_moments_u8")
+    return sums
+
+
+def rsf_reduce_u8(y, taps, radius, sel):
+    """uint8 device tensor ``y`` [..., s*h, s*w], the host tap table ``taps`` int [K, 2 s + 2 radius] of ``rsf_taps`` (it fixes ``s``; checked
+    as in ``rsf_moments_u8``) and one candidate index per plane (``sel``: host ints [planes], checked here: ``0 <= sel < K``) -> uint8
+    [..., h - 2m, w - 2m], ``m = register_margin(s, radius)``: ``D_sel[p]`` of every plane, ``y`` blurred and reduced by that row."""
+    import numpy as np
+    if not torch.is_tensor(y) or y.dtype != torch.uint8 or not y.is_cuda or y.dim() < 2:
+        raise ValueError("rsf_reduce_u8 needs a uint8 device tensor [..., s*h, s*w]")
+    table, K, s = _rsf_table("rsf_reduce_u8", taps, radius)
+    radius = int(radius)
+    H, W = y.shape[-2:]
+    h, w = H // s, W // s
+    if h < 1 or w < 1 or H != s * h or W != s * w:
+        raise ValueError(f"rsf_reduce_u8: a {H}x{W} image is no multiple of the scale {s} of the tap table")
+    if h * w > 1 << 28:
+        raise ValueError(f"rsf_reduce_u8: {h * w} pixels per LR plane (at most 2**28)")
+    planes = y.numel() // (H * W)
+    m = register_margin(s, radius)
+    if planes < 1 or h - 2 * m < 1 or w - 2 * m < 1:
+        raise ValueError(f"rsf_reduce_u8: {planes} planes; a {h}x{w} LR image leaves nothing inside the margin of {m} pixels on every side")
+    rows = [int(v) for v in (sel.tolist() if hasattr(sel, "tolist") else sel)]
+    if len(rows) != planes or any(not 0 <= v < K for v in rows):
+        raise ValueError(f"rsf_reduce_u8 needs {planes} candidate indices sel with 0 <= sel < {K}")
+    y = y.contiguous()
+    dev_taps = torch.from_numpy(table).to(y.device)
+    dev_sel = torch.from_numpy(np.asarray(rows, dtype=np.int32)).to(y.device)
+    d = torch.empty(*y.shape[:-2], h - 2 * m, w - 2 * m, dtype=torch.uint8, device=y.device)
+    L.check(L.lib().pssr_rsf_reduce_u8(L.ptr(y), L.ptr(dev_taps), L.ptr(dev_sel), L.ptr(d), planes, h, w, s, K, radius, L.stream_ptr()),
+            "pssr_rsf_reduce_u8")
+    return d
+
+
+# ----------------------------------------------------------------------------------------------
 # Fourier ring correlation (csrc/frc.hip; definitions in include/pssr_mi355.h)
 FRC_WINDOWS = ("hann", "none")       # frc's ``window``
 FRC_MIN_BLOCK, FRC_MAX_BLOCK = 16, 1024

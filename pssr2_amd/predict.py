@@ -86,12 +86,12 @@ def _check_consistency(consistency, fit, device):
         raise RuntimeError("pssr2_amd.predict runs on an MI355X (HIP) device only; there is no CPU fallback")
 
 
-def _score_items(lr: torch.Tensor, hat: torch.Tensor, crop_res: int, scale: int, fit: str):
+def _score_items(lr: torch.Tensor, hat: torch.Tensor, crop_res: int, scale: int, fit: str, rsf: bool = False):
     """``util.consistency_map`` of a device batch for ``predict_images`` / ``test_metrics``: the cropped uint8 predictions ``hat``
     [n, C, H', W'] (not normalised, in HBM) against their LR items ``lr`` [n, m, h, w] cut to ``crop_res // scale`` as the predictions were
     cut to ``crop_res`` (``scale``: the model's).  A float item is quantised as a prediction is (``ops.clip_u8``); the datasets hand out
-    integers, for which that is the identity."""
-    from .util import consistency_map
+    integers, for which that is the identity.  ``rsf=True``: ``util.estimate_rsf`` of the same two batches instead."""
+    from .util import consistency_map, estimate_rsf
     if scale < 1 or crop_res % scale:
         raise ValueError(f"consistency=True compares the cropped prediction with the LR item cut to crop_res // scale: the crop ({crop_res}) "
                          f"must be a multiple of the model's scale ({scale}).")
@@ -100,6 +100,8 @@ def _score_items(lr: torch.Tensor, hat: torch.Tensor, crop_res: int, scale: int,
         lr = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
         ops.clip_u8(x, lr)
     cut = crop_res // scale
+    if rsf:
+        return estimate_rsf(lr[:, :, :cut, :cut].contiguous(), hat.contiguous())
     return consistency_map(lr[:, :, :cut, :cut].contiguous(), hat.contiguous(), fit=fit)
 
 
@@ -488,7 +490,11 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
 
     ``metrics`` may name ``"frc"`` too (not in the default tuple either): the resolution that the prediction reached, in HR pixels --
     ``util.frc`` with its defaults (one block per plane, Hann window, the 1/7 threshold) of the cropped uint8 prediction, before ``norm``,
-    against the cropped ground truth, the image's planes pooled.  A call that does not name it launches what it launched before."""
+    against the cropped ground truth, the image's planes pooled.  A call that does not name it launches what it launched before.
+
+    ``"rsf"`` (not in the default tuple either) reports how much sharper the prediction is than the optics behind its LR side: the width
+    ``sigma``, in HR pixels, of the Gaussian resolution-scaling function that ``util.estimate_rsf`` (default candidates, one choice per image)
+    finds between the cropped uint8 prediction, before ``norm``, and the item's own LR side, cut as for ``"rse"``.  No ground truth is needed."""
     import math
     from .util import pixel_metric
     _check_ensemble(ensemble, device)
@@ -497,7 +503,7 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
     image_range = 255
     metrics = [metrics] if type(metrics) is str else list(metrics)
     out = {m: [] for m in metrics}
-    if "frc" in out and torch.device(device).type != "cuda":                   # as _check_ensemble: before model, dataset or device are touched
+    if ("frc" in out or "rsf" in out) and torch.device(device).type != "cuda":                   # as _check_ensemble: before model, dataset or device are touched
         raise RuntimeError("pssr2_amd.predict runs on an MI355X (HIP) device only; there is no CPU fallback")
     model.to(device)
     model.eval()
@@ -522,6 +528,8 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
             if "frc" in out:
                 from .util import frc
                 out["frc"].extend(frc(hat_dev, hr_dev).resolution.tolist())
+            if "rsf" in out:
+                out["rsf"].extend(_score_items(lr, hat_dev, crop_res, hr_hat.shape[-1] // lr.shape[-1], fit, rsf=True).sigma.tolist())
             if norm:
                 hr_dev, hat_dev = ops.normalize_preds_u8(hr_dev, hat_dev)
             n, c, h, w = hr_dev.shape

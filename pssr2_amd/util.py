@@ -350,7 +350,153 @@ def _consistency_fit(n: int, sums, fit: str):
     return alpha, beta, rsp, table
 
 
-def consistency_map(lr, hr_hat, *, fit: str = "affine", to_numpy: bool = True):
+RSF = namedtuple("RSF", "sigma fwhm score curve index margin")
+RSFConsistency = namedtuple("RSFConsistency", "map alpha beta rse rsp sigma margin")
+RSF_POOLS = ("item", "all")                          # estimate_rsf's ``pool``
+RSF_SIGMAS = tuple(0.25 * i for i in range(33))      # estimate_rsf's default candidates: 0, 0.25, .. 8 HR pixels (K = 33, R = 24)
+_FWHM = 2.0 * math.sqrt(2.0 * math.log(2.0))
+
+
+def _rsf_choose(n: int, rows, K: int):
+    """``(k, curve)`` from the exact sums of the pooled planes (``rows``: one list of ``3 K + 2`` ints per plane, the layout of
+    ``pssr_rsf_moments_u8``) over ``n`` pixels in all, in exactly the expressions of include/pssr_mi355.h: the planes' sums add, the score of
+    a candidate is the signed squared Pearson correlation ``num |num| / (den denl)`` (0 when ``den`` or ``denl`` is 0), compared by
+    cross-multiplying Python ints; ties go to the smaller ``k``.  ``curve``: the Pearson correlation of every candidate."""
+    pooled = [sum(int(v) for v in col) for col in zip(*rows)]
+    sl, sll = pooled[3 * K], pooled[3 * K + 1]
+    best, curve = None, []                              # (p, q, k): the score p / (q denl), q > 0
+    for k in range(K):
+        sd, sdd, sdl = pooled[3 * k:3 * k + 3]
+        num, den, denl, r = _pearson_terms(n, sd, sl, sdd, sdl, sll)
+        p, q = (num * abs(num), den) if den > 0 and denl > 0 else (0, 1)
+        if best is None or p * best[1] > best[0] * q:
+            best = (p, q, k)
+        curve.append(r)
+    return best[2], curve
+
+
+def _rsf_sigmas(sigmas, what="sigmas"):
+    """The candidate widths as a list of floats: 1 .. 64 finite numbers >= 0 with ``ceil(3 sigma) <= 32``."""
+    if sigmas is None:
+        return list(RSF_SIGMAS)
+    try:
+        sig = [float(v) for v in (sigmas.tolist() if hasattr(sigmas, "tolist") else sigmas)]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a sequence of numbers. Given {sigmas!r}.") from None
+    if not 1 <= len(sig) <= ops.MAX_RSF_CANDIDATES:
+        raise ValueError(f"{what} must hold 1 to {ops.MAX_RSF_CANDIDATES} candidates. Given {len(sig)}.")
+    if any(not math.isfinite(v) or v < 0 or ops.rsf_radius(v) > ops.MAX_REGISTER_RADIUS for v in sig):
+        raise ValueError(f"{what} must be finite, >= 0 and at most {ops.MAX_REGISTER_RADIUS / 3:.2f} HR pixels (ceil(3 sigma) <= "
+                         f"{ops.MAX_REGISTER_RADIUS}). Given {sig}.")
+    return sig
+
+
+def _rsf_sums(who, lr, hr_hat, sig):
+    """The shared front half of ``estimate_rsf`` and ``consistency_map(rsf=...)``: the checks of the pair, the centre-frame rule, the tap
+    table of the candidates ``sig`` and the one sums launch -> ``(hat, frames, batched, scale, taps, R, m, rows)`` with both tensors on the
+    device and ``rows`` the sums on the host, one list of ``3 K + 2`` ints per plane.  Every check comes before any device work."""
+    hr_hat, lr, batched, scale, dev = _u8_image_pair(who, hr_hat, lr, ("hr_hat", "lr"), ("A prediction of {} planes", "an input of {} frames"))
+    c, (h, w) = hr_hat.shape[1], lr.shape[-2:]
+    taps, R = ops.rsf_taps(scale, sig)
+    m = ops.register_margin(scale, R)
+    if h - 2 * m < 1 or w - 2 * m < 1:
+        raise ValueError(f"An LR image of {h}x{w} leaves nothing inside the margin of {m} pixels that a largest sigma of {max(sig)} (radius {R}) "
+                         f"at scale {scale} needs on every side.")
+    if not (hr_hat.is_cuda or lr.is_cuda or torch.cuda.is_available()):
+        raise RuntimeError(f"pssr2_amd.util.{who} needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
+    from .data import _slice_center
+    hat, frames = hr_hat.to(dev).contiguous(), _slice_center(lr.to(dev), c).contiguous()
+    return hat, frames, batched, scale, taps, R, m, ops.rsf_moments_u8(hat, frames, taps, R).cpu().tolist()
+
+
+def estimate_rsf(lr, hr_hat, *, sigmas=None, pool: str = "item", pixel_size: float = 1.0, to_numpy: bool = True):
+    r"""Estimates the resolution-scaling function between sharp images and measured ones: the width of the Gaussian blur that, applied
+    before this package's forward model (``_gen_pair``'s Pillow-bilinear reduction), makes ``hr_hat`` look most like ``lr``.  ``lr``: uint8
+    array or device tensor [N, m, h, w]; ``hr_hat``: uint8 [N, C, s*h, s*w], ``s`` an integer in 1 .. 16 (or both 3-D, without the batch
+    axis) -- a prediction and its own input, or a real HR / LR pair (``register_pairs`` first).  Plane ``j`` meets frame ``j`` of the ``C``
+    centre frames of ``lr`` (``_slice_center``).  For every candidate ``sigma`` (``sigmas``: 1 .. 64 widths in HR pixels, finite, >= 0,
+    ``ceil(3 sigma) <= 32``; ``None``: 0, 0.25, .. 8) the sharp image is blurred and reduced to the LR grid in integer arithmetic and
+    correlated with ``lr`` inside a margin of ``m = 1 + ceil(R / s)`` LR pixels, ``R`` the largest ``ceil(3 sigma)``.  The best intensity fit
+    ``L ~ alpha D_sigma + beta`` leaves the residual ``(1 - rho**2) var(L)``, so the candidate with the largest signed squared Pearson
+    correlation wins (ties: the first) -- one choice per item, its planes pooled, or with ``pool="all"`` one for the whole batch: one sigma
+    for one microscope.  include/pssr_mi355.h has the definitions, exact integers throughout.  Returns
+    ``RSF(sigma, fwhm, score, curve, index, margin)``:
+
+    * ``sigma``: float64 [N], the chosen width in HR pixels times ``pixel_size``; ``fwhm = 2 sqrt(2 ln 2) sigma``: a resolution figure that
+      needs no second image; ``index``: int [N], the chosen candidate;
+    * ``score``: float64 [N], the Pearson correlation at the choice; ``curve``: float64 [N, K], that of every candidate (``pool="all"``: the
+      pooled curve in every row); ``margin``: ``m``.
+
+    One sums launch for all candidates (``pssr_rsf_moments_u8``) and one copy of the sums to the host; the choice is made in Python ints.
+    A choice on the last candidate of a grid of several emits a ``UserWarning`` naming the items: the optimum may lie beyond the grid.
+    ``to_numpy=False`` leaves ``curve`` on the device.  To start ``approximate_crappifier``'s search from the measured blur, pass
+    ``sigma`` as the initial value of its ``Blur`` dimension."""
+    import warnings
+    if pool not in RSF_POOLS:
+        raise ValueError(f"pool must be one of {RSF_POOLS}. Given {pool!r}.")
+    if isinstance(pixel_size, bool) or not isinstance(pixel_size, (int, float, np.integer, np.floating)) or not pixel_size > 0 \
+            or not math.isfinite(pixel_size):
+        raise ValueError(f"pixel_size must be a positive number. Given {pixel_size!r}.")
+    sig = _rsf_sigmas(sigmas)
+    hat, frames, batched, _, _, _, m, rows = _rsf_sums("estimate_rsf", lr, hr_hat, sig)
+    (n_img, c), K = hat.shape[:2], len(sig)
+    n = c * (frames.shape[-2] - 2 * m) * (frames.shape[-1] - 2 * m)
+    if pool == "all":
+        chosen = [_rsf_choose(n_img * n, rows, K)] * n_img
+    else:
+        chosen = [_rsf_choose(n, rows[i * c:(i + 1) * c], K) for i in range(n_img)]
+    edge = [i for i, (k, _) in enumerate(chosen) if K > 1 and k == K - 1]
+    if edge:
+        warnings.warn(f"estimate_rsf: the choice of item(s) {edge} is the last candidate (sigma={sig[-1]}); the optimum may lie beyond the "
+                      "grid", UserWarning, stacklevel=2)
+    index = np.array([k for k, _ in chosen], dtype=np.int64)
+    sigma = np.array([sig[k] * float(pixel_size) for k, _ in chosen], dtype=np.float64)
+    score = np.array([curve[k] for k, curve in chosen], dtype=np.float64)
+    curve = np.array([curve for _, curve in chosen], dtype=np.float64).reshape(n_img, K)
+    fwhm = _FWHM * sigma
+    if not batched:
+        sigma, fwhm, score, curve, index = float(sigma[0]), float(fwhm[0]), float(score[0]), curve[0], int(index[0])
+    return RSF(sigma, fwhm, score, curve if to_numpy else torch.from_numpy(curve).to(hat.device), index, m)
+
+
+def _consistency_rsf(lr, hr_hat, fit, rsf, to_numpy):
+    """``consistency_map(rsf=...)``: the map after a resolution-scaling function has been fitted (``"fit"``) or given (a width in HR pixels,
+    or one per item)."""
+    if isinstance(rsf, str):
+        if rsf != "fit":
+            raise ValueError(f'rsf must be None, "fit", a sigma in HR pixels or one sigma per item. Given {rsf!r}.')
+        sig, per_item = list(RSF_SIGMAS), None                   # None: chosen from the sums
+    elif isinstance(rsf, (int, float, np.integer, np.floating)) and not isinstance(rsf, bool):
+        sig, per_item = _rsf_sigmas([rsf], "rsf"), "first"        # the one row, for every item
+    else:
+        given = _rsf_sigmas(rsf, "rsf")
+        sig = sorted(set(given))
+        per_item = [sig.index(v) for v in given]
+    shape = tuple(hr_hat.shape) if hasattr(hr_hat, "shape") else np.shape(hr_hat)
+    if isinstance(per_item, list) and (len(shape) != 4 or len(per_item) != shape[0]):
+        raise ValueError(f"rsf as a sequence needs one sigma per item of a 4-D batch. Given {len(per_item)} for a shape of {shape}.")
+    hat, frames, batched, scale, taps, R, m, rows = _rsf_sums("consistency_map", lr, hr_hat, sig)
+    (n_img, c), K = hat.shape[:2], len(sig)
+    hc, wc = frames.shape[-2] - 2 * m, frames.shape[-1] - 2 * m
+    if per_item is None:
+        per_item = [_rsf_choose(c * hc * wc, rows[i * c:(i + 1) * c], K)[0] for i in range(n_img)]
+    elif per_item == "first":
+        per_item = [0] * n_img
+    sel = [k for k in per_item for _ in range(c)]
+    d = ops.rsf_reduce_u8(hat, taps, R, sel)
+    lc = ops.crop_shift_u8(frames, [(m, m)] * (n_img * c), hc, wc)
+    fits = [_consistency_fit(hc * wc, (row[3 * k], row[3 * K], row[3 * k + 1], row[3 * k + 2], row[3 * K + 1]), fit) for row, k in zip(rows, sel)]
+    tables = torch.tensor([f[3] for f in fits], dtype=torch.int32).to(hat.device)
+    cmap, sse = ops.consistency_map_u8(d, lc, tables)
+    stats = [np.array([f[k] for f in fits], dtype=np.float64).reshape(n_img, c) for k in range(3)]
+    rse = np.array([math.sqrt(v / (hc * wc)) / 256 for v in sse.cpu().tolist()], dtype=np.float64).reshape(n_img, c)
+    sigma = np.array([sig[k] for k in per_item], dtype=np.float64)
+    if not batched:
+        cmap, stats, rse, sigma = cmap[0], [v[0] for v in stats], rse[0], float(sigma[0])
+    return RSFConsistency(cmap.cpu().numpy() if to_numpy else cmap, stats[0], stats[1], rse, stats[2], sigma, m)
+
+
+def consistency_map(lr, hr_hat, *, fit: str = "affine", to_numpy: bool = True, rsf=None):
     r"""Scores predictions against their own low-resolution input, without ground truth: the resolution-scaled error map of the
     super-resolution microscopy literature under this package's forward model (``_gen_pair``'s Pillow-bilinear reduction).  ``lr``: uint8
     array or device tensor [N, m, h, w]; ``hr_hat``: uint8 [N, C, s*h, s*w], ``s`` an integer in 1 .. 16 (or both 3-D, without the batch
@@ -366,8 +512,18 @@ def consistency_map(lr, hr_hat, *, fit: str = "affine", to_numpy: bool = True):
     One fused reduction + moments launch (``pssr_reduce_moments_u8``), one copy of ``5 N C`` integers to the host, the fit and the 256-entry
     tables in Python from those integers (exact; include/pssr_mi355.h has the expressions), one upload, one map launch
     (``pssr_consistency_map_u8``).  Everything after the fit is integer arithmetic: the result is a pure function of the bytes.
-    ``to_numpy=False`` leaves ``map`` in HBM."""
+    ``to_numpy=False`` leaves ``map`` in HBM.
+
+    ``rsf`` (keyword-only; ``None``: everything above, untouched) puts a Gaussian resolution-scaling function in front of the reduction, as
+    the resolution-scaled error is defined: a prediction that is rightly sharper than the optics behind its input is then not marked at
+    every edge.  ``"fit"``: the width that ``estimate_rsf`` chooses per item among its default candidates; a number: that sigma in HR
+    pixels for every item; a sequence: one sigma per item.  ``D`` is then the blurred reduction of the chosen width
+    (``pssr_rsf_reduce_u8``) inside the margin ``m`` of the search, the fit of every plane comes from that plane's own row of the search
+    sums (no second moments launch), and the result is ``RSFConsistency(map, alpha, beta, rse, rsp, sigma, margin)`` with ``map``
+    [N, C, h - 2m, w - 2m] and ``sigma`` float64 [N] in HR pixels."""
     _check_fit(fit)
+    if rsf is not None:
+        return _consistency_rsf(lr, hr_hat, fit, rsf, to_numpy)
     hr_hat, lr, batched, _, dev = _u8_image_pair("consistency_map", hr_hat, lr, ("hr_hat", "lr"), ("A prediction of {} planes", "an input of {} frames"))
     (n_img, c), (h, w) = hr_hat.shape[:2], lr.shape[-2:]
     from .data import _slice_center
