@@ -215,10 +215,12 @@ __global__ void maxpool_k_bwd_kernel(Ref act, Ref dpool, MRef dx, int n, int h, 
     }
 }
 
-// torch's bilinear source index for align_corners = False: src = max((dst + 0.5) * in / out - 0.5, 0)
+// torch's bilinear source index for align_corners = False: src = max((dst + 0.5) * in / out - 0.5, 0), in f32 with the product and
+// the difference in one fused multiply-add (what torch's vectorised CPU and device kernels compute; written out so that the
+// coordinates, which the tests take as part of the operation's definition, do not hang on the compiler's contraction setting)
 __device__ __forceinline__ void bil_src(int dst, int in_size, int out_size, int& i0, int& i1, float& l1) {
     const float scale = (float)in_size / (float)out_size;
-    float src = ((float)dst + 0.5f) * scale - 0.5f;
+    float src = fmaf((float)dst + 0.5f, scale, -0.5f);
     src = src < 0.f ? 0.f : src;
     i0 = (int)src;
     if (i0 > in_size - 1) i0 = in_size - 1;
@@ -280,6 +282,7 @@ __global__ void bilinear_up_bwd_kernel(Ref dout, MRef din, int n, int hs, int ws
 extern "C" int pssr_input_plain(const float* x_nchw, void* out, int n, int c, int h, int w, int out_cs, float pre_scale, float pre_shift,
                                 int dtype, pssr_stream_t s) {
     PSSR_CHECK(x_nchw && out && n > 0 && c > 0 && h > 0 && w > 0 && out_cs >= c, PSSR_ERR_ARG, "input_plain: bad args");
+    CHECK_DTYPE("input_plain", dtype);
     const long hw = (long)h * w;
     DISPATCH_T(dtype, hipLaunchKernelGGL(input_plain_kernel<T>, dim3(grid1d((long)n * hw * out_cs, 16384)), dim3(TPB), 0, (hipStream_t)s, x_nchw, out, n, c, hw,
                                          out_cs, pre_scale, pre_shift));
@@ -289,7 +292,9 @@ extern "C" int pssr_input_plain(const float* x_nchw, void* out, int n, int c, in
 
 extern "C" int pssr_im2col_dil(const void* in, int in_cs, int in_co, int c, const float* scale, const float* shift, void* col, int cp,
                                int n, int h, int w, int dil, int dtype, pssr_stream_t s) {
-    PSSR_CHECK(in && col && c > 0 && cp >= c && n > 0 && h > 0 && w > 0 && dil >= 1 && in_co + c <= in_cs, PSSR_ERR_ARG, "im2col_dil: bad args");
+    PSSR_CHECK(in && col && c > 0 && cp >= c && n > 0 && h > 0 && w > 0 && dil >= 1, PSSR_ERR_ARG, "im2col_dil: bad args");
+    CHECK_SLICE("im2col_dil", in_cs, in_co, c);
+    CHECK_DTYPE("im2col_dil", dtype);
     PSSR_CHECK((scale == nullptr) == (shift == nullptr), PSSR_ERR_ARG, "im2col_dil: scale and shift go together");
     DISPATCH_T(dtype, hipLaunchKernelGGL(im2col_dil_kernel<T>, dim3(grid1d((long)n * h * w * 9 * cp, 16384)), dim3(TPB), 0, (hipStream_t)s,
                                          Ref{in, in_cs, in_co}, c, scale, shift, col, cp, n, h, w, dil));
@@ -300,9 +305,12 @@ extern "C" int pssr_im2col_dil(const void* in, int in_cs, int in_co, int c, cons
 extern "C" int pssr_col2im_dil(const void* dcol, int cp, void* out, int out_cs, int out_co, int c, int n, int h, int w, int dil,
                                const void* y, int y_cs, int y_co, const float* scale, const float* shift, const float* mean,
                                const float* invstd, double* stats, int dtype, pssr_stream_t s) {
-    PSSR_CHECK(dcol && out && c > 0 && cp >= c && n > 0 && h > 0 && w > 0 && dil >= 1 && out_co + c <= out_cs, PSSR_ERR_ARG, "col2im_dil: bad args");
+    PSSR_CHECK(dcol && out && c > 0 && cp >= c && n > 0 && h > 0 && w > 0 && dil >= 1, PSSR_ERR_ARG, "col2im_dil: bad args");
+    CHECK_SLICE("col2im_dil", out_cs, out_co, c);
+    CHECK_DTYPE("col2im_dil", dtype);
     PSSR_CHECK(!y || (scale && shift), PSSR_ERR_ARG, "col2im_dil: the ReLU mask needs scale / shift");
     PSSR_CHECK(!stats || (y && mean && invstd), PSSR_ERR_ARG, "col2im_dil: statistics need the pre-activation, mean and invstd");
+    if (y) CHECK_SLICE("col2im_dil", y_cs, y_co, c);
     const Walk wk = make_walk(c);
     long blocks = ((long)n * h * w + wk.rows - 1) / wk.rows;
     if (blocks > 2048) blocks = 2048;
@@ -313,7 +321,9 @@ extern "C" int pssr_col2im_dil(const void* dcol, int cp, void* out, int out_cs, 
 }
 
 extern "C" int pssr_channel_stats_nhwc(const void* x, int cs, int co, int c, int64_t npix, double* stats, int dtype, pssr_stream_t s) {
-    PSSR_CHECK(x && stats && c > 0 && npix > 0 && co + c <= cs, PSSR_ERR_ARG, "channel_stats_nhwc: bad args");
+    PSSR_CHECK(x && stats && c > 0 && npix > 0, PSSR_ERR_ARG, "channel_stats_nhwc: bad args");
+    CHECK_SLICE("channel_stats_nhwc", cs, co, c);
+    CHECK_DTYPE("channel_stats_nhwc", dtype);
     const Walk wk = make_walk(c);
     long blocks = (npix + wk.rows - 1) / wk.rows;
     if (blocks > 2048) blocks = 2048;
@@ -325,9 +335,15 @@ extern "C" int pssr_channel_stats_nhwc(const void* x, int cs, int co, int c, int
 extern "C" int pssr_sum_relu(const void* const* ins, const int* in_cs, const int* in_co, int n_in, void* out, int out_cs, int out_co,
                              int64_t npix, int c, int relu, int dtype, pssr_stream_t s) {
     PSSR_CHECK(ins && in_cs && in_co && out && n_in >= 1 && n_in <= 8 && npix > 0 && c > 0, PSSR_ERR_ARG, "sum_relu: 1..8 inputs");
+    CHECK_SLICE("sum_relu", out_cs, out_co, c);
+    CHECK_DTYPE("sum_relu", dtype);
     SumArgs a;
     a.n = n_in;
-    for (int k = 0; k < n_in; ++k) { a.p[k] = ins[k]; a.cs[k] = in_cs[k]; a.co[k] = in_co[k]; }
+    for (int k = 0; k < n_in; ++k) {
+        PSSR_CHECK(ins[k], PSSR_ERR_ARG, "sum_relu: input %d is null", k);
+        CHECK_SLICE("sum_relu", in_cs[k], in_co[k], c);
+        a.p[k] = ins[k]; a.cs[k] = in_cs[k]; a.co[k] = in_co[k];
+    }
     DISPATCH_T(dtype, hipLaunchKernelGGL(sum_relu_kernel<T>, dim3(grid1d((long)npix * c, 16384)), dim3(TPB), 0, (hipStream_t)s, a, MRef{out, out_cs, out_co},
                                          (long)npix, c, relu));
     PSSR_LAUNCH_CHECK();
@@ -337,6 +353,10 @@ extern "C" int pssr_sum_relu(const void* const* ins, const int* in_cs, const int
 extern "C" int pssr_relu_mask(const void* dout, int do_cs, int do_co, const void* out, int o_cs, int o_co, void* dz, int dz_cs, int dz_co,
                               int64_t npix, int c, int dtype, pssr_stream_t s) {
     PSSR_CHECK(dout && out && dz && npix > 0 && c > 0, PSSR_ERR_ARG, "relu_mask: bad args");
+    CHECK_SLICE("relu_mask", do_cs, do_co, c);
+    CHECK_SLICE("relu_mask", o_cs, o_co, c);
+    CHECK_SLICE("relu_mask", dz_cs, dz_co, c);
+    CHECK_DTYPE("relu_mask", dtype);
     DISPATCH_T(dtype, hipLaunchKernelGGL(mask_or_affine_kernel<T>, dim3(grid1d((long)npix * c, 16384)), dim3(TPB), 0, (hipStream_t)s, Ref{dout, do_cs, do_co},
                                          Ref{out, o_cs, o_co}, (const float*)nullptr, (const float*)nullptr, MRef{dz, dz_cs, dz_co}, (long)npix, c, 0));
     PSSR_LAUNCH_CHECK();
@@ -346,6 +366,9 @@ extern "C" int pssr_relu_mask(const void* dout, int do_cs, int do_co, const void
 extern "C" int pssr_affine_relu(const void* x, int cs, int co, const float* scale, const float* shift, void* out, int out_cs, int out_co,
                                 int64_t npix, int c, int dtype, pssr_stream_t s) {
     PSSR_CHECK(x && scale && shift && out && npix > 0 && c > 0, PSSR_ERR_ARG, "affine_relu: bad args");
+    CHECK_SLICE("affine_relu", cs, co, c);
+    CHECK_SLICE("affine_relu", out_cs, out_co, c);
+    CHECK_DTYPE("affine_relu", dtype);
     DISPATCH_T(dtype, hipLaunchKernelGGL(mask_or_affine_kernel<T>, dim3(grid1d((long)npix * c, 16384)), dim3(TPB), 0, (hipStream_t)s, Ref{x, cs, co},
                                          Ref{nullptr, 0, 0}, scale, shift, MRef{out, out_cs, out_co}, (long)npix, c, 1));
     PSSR_LAUNCH_CHECK();
@@ -355,6 +378,9 @@ extern "C" int pssr_affine_relu(const void* x, int cs, int co, const float* scal
 extern "C" int pssr_maxpool_k(const void* in, int in_cs, int in_co, void* out, int out_cs, int out_co, int n, int h, int w, int c, int k,
                               int dtype, pssr_stream_t s) {
     PSSR_CHECK(in && out && n > 0 && c > 0 && k >= 1 && h >= k && w >= k, PSSR_ERR_ARG, "maxpool_k: bad args (k=%d on %dx%d)", k, h, w);
+    CHECK_SLICE("maxpool_k", in_cs, in_co, c);
+    CHECK_SLICE("maxpool_k", out_cs, out_co, c);
+    CHECK_DTYPE("maxpool_k", dtype);
     DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_k_kernel<T>, dim3(grid1d((long)n * (h / k) * (w / k) * c, 16384)), dim3(TPB), 0, (hipStream_t)s,
                                          Ref{in, in_cs, in_co}, MRef{out, out_cs, out_co}, n, h, w, c, k));
     PSSR_LAUNCH_CHECK();
@@ -364,6 +390,10 @@ extern "C" int pssr_maxpool_k(const void* in, int in_cs, int in_co, void* out, i
 extern "C" int pssr_maxpool_k_bwd(const void* act, int act_cs, int act_co, const void* dpool, int dp_cs, int dp_co, void* dx, int dx_cs, int dx_co,
                                   int n, int h, int w, int c, int k, int dtype, pssr_stream_t s) {
     PSSR_CHECK(act && dpool && dx && n > 0 && c > 0 && k >= 1 && h >= k && w >= k, PSSR_ERR_ARG, "maxpool_k_bwd: bad args");
+    CHECK_SLICE("maxpool_k_bwd", act_cs, act_co, c);
+    CHECK_SLICE("maxpool_k_bwd", dp_cs, dp_co, c);
+    CHECK_SLICE("maxpool_k_bwd", dx_cs, dx_co, c);
+    CHECK_DTYPE("maxpool_k_bwd", dtype);
     DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_k_bwd_kernel<T>, dim3(grid1d((long)n * h * w * c, 16384)), dim3(TPB), 0, (hipStream_t)s, Ref{act, act_cs, act_co},
                                          Ref{dpool, dp_cs, dp_co}, MRef{dx, dx_cs, dx_co}, n, h, w, c, k));
     PSSR_LAUNCH_CHECK();
@@ -373,6 +403,9 @@ extern "C" int pssr_maxpool_k_bwd(const void* act, int act_cs, int act_co, const
 extern "C" int pssr_bilinear_up(const void* in, int in_cs, int in_co, void* out, int out_cs, int out_co, int n, int hs, int ws, int h, int w,
                                 int c, int dtype, pssr_stream_t s) {
     PSSR_CHECK(in && out && n > 0 && c > 0 && hs > 0 && ws > 0 && h >= hs && w >= ws, PSSR_ERR_ARG, "bilinear_up: bad args");
+    CHECK_SLICE("bilinear_up", in_cs, in_co, c);
+    CHECK_SLICE("bilinear_up", out_cs, out_co, c);
+    CHECK_DTYPE("bilinear_up", dtype);
     DISPATCH_T(dtype, hipLaunchKernelGGL(bilinear_up_kernel<T>, dim3(grid1d((long)n * h * w * c, 16384)), dim3(TPB), 0, (hipStream_t)s, Ref{in, in_cs, in_co},
                                          MRef{out, out_cs, out_co}, n, hs, ws, h, w, c));
     PSSR_LAUNCH_CHECK();
@@ -382,6 +415,9 @@ extern "C" int pssr_bilinear_up(const void* in, int in_cs, int in_co, void* out,
 extern "C" int pssr_bilinear_up_bwd(const void* dout, int do_cs, int do_co, void* din, int di_cs, int di_co, int n, int hs, int ws, int h, int w,
                                     int c, int dtype, pssr_stream_t s) {
     PSSR_CHECK(dout && din && n > 0 && c > 0 && hs > 0 && ws > 0 && h >= hs && w >= ws, PSSR_ERR_ARG, "bilinear_up_bwd: bad args");
+    CHECK_SLICE("bilinear_up_bwd", do_cs, do_co, c);
+    CHECK_SLICE("bilinear_up_bwd", di_cs, di_co, c);
+    CHECK_DTYPE("bilinear_up_bwd", dtype);
     DISPATCH_T(dtype, hipLaunchKernelGGL(bilinear_up_bwd_kernel<T>, dim3(grid1d((long)n * hs * ws * c, 16384)), dim3(TPB), 0, (hipStream_t)s, Ref{dout, do_cs, do_co},
                                          MRef{din, di_cs, di_co}, n, hs, ws, h, w, c));
     PSSR_LAUNCH_CHECK();

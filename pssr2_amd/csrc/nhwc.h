@@ -33,3 +33,10 @@ __device__ __forceinline__ PixPos split_pix(long pix, int h, int w) {
 
 #define CHECK_REF(name, cs, co, c)                                                                               \
     PSSR_CHECK((cs) % 4 == 0 && (co) % 4 == 0 && (co) + (c) <= (cs), PSSR_ERR_ARG, name ": bad channel stride/offset (%d,%d,%d)", cs, co, c)
+
+// the slice of a scalar kernel: any offset (the engines pass unaligned chunk offsets), inside its stride
+#define CHECK_SLICE(name, cs, co, c)                                                                             \
+    PSSR_CHECK((c) > 0 && (co) >= 0 && (long)(co) + (c) <= (long)(cs), PSSR_ERR_ARG, name ": channel slice outside its stride (%d,%d,%d)", cs, co, c)
+
+#define CHECK_DTYPE(name, dtype) \
+    PSSR_CHECK((dtype) == PSSR_BF16 || (dtype) == PSSR_F16 || (dtype) == PSSR_F32, PSSR_ERR_ARG, name ": bad dtype %d", dtype)
