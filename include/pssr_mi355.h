@@ -906,6 +906,51 @@ int64_t pssr_frc_workspace_bytes(int planes, int H, int W, int n);
 int pssr_frc_rings_u8(const uint8_t* a, const uint8_t* b, const float* ct, const float* st, double* sums, int planes, int H, int W, int n,
                       void* workspace, pssr_stream_t stream);
 
+/* Resolution of one image by decorrelation analysis (pssr2_amd.util.decorr; csrc/frc.hip): the figure FRC gives for a pair, from a single
+ * image, with no threshold and no calibration (Descloux, Grussmayer, Radenovic, Nature Methods 16, 2019).  The spectrum F is correlated
+ * with its own normalised self F / |F| inside a disc of radius r; that correlation, d(r), rises while the disc gathers signal and falls
+ * once it gathers noise alone, and the position of its peak is the cut-off.  High-pass filtering the image first moves the peak outwards
+ * as far as the signal reaches; the largest peak position over a family of filters is the resolution.  Because |F / |F|| = 1 and a radial
+ * filter is one weight per ring, every curve of the family follows from two sums per ring, sum |F| and sum |F|^2, of one transform.
+ * Inputs: a uint8 stack A [planes][H][W] and an even block side n, 16 <= n <= 1024, n <= min(H, W); blocks, the centred grid, the tables
+ * Ct, St (step 1 of the FRC block above, the caller's contract) and the ring index r = (isqrt(4 q) + 1) / 2, rings 0 .. R = n / 2 kept,
+ * are FRC's.  On the device:
+ *   1. Mean.  S = sum of the block's n^2 bytes, an exact integer (at most 2^20 x 255).  m = float32(S / n^2), the quotient taken in double
+ *      and rounded once to float32.  c[y][x] = float32(a[y][x]) - m, one float32 subtraction.  A constant block is exactly zero.  The mean
+ *      is the block's own, not the plane's.  (Without it the window leaks the mean into rings 1 - 2 and every curve peaks there.)
+ *   2. Spectrum and sums.  F = W^T c W, W = Ct + i St, in float32 exactly as step 2 of FRC (x first, then y, ascending chains of fused
+ *      multiply-adds).  With fr = Re F and fi = Im F as they leave the accumulators: p = fmaf(fr, fr, fi * fi) (the product fi * fi rounded,
+ *      then one fused multiply-add) is |F|^2 and sqrtf(p), correctly rounded, is |F|; both float32.  Per plane, block and ring r two
+ *      float64 sums over the full spectrum: A[r] = sum |F| and P[r] = sum |F|^2.  The kernel visits kx <= n / 2 and doubles (exactly, in
+ *      float32) the columns 0 < kx < n / 2.  Layout [planes][nby nbx][R + 1][2], A first.
+ * On the host (pssr2_amd.util._decorr_resolve, Python floats, no device), with pop[r] the number of coefficients of the full spectrum in
+ * ring r (counted from the ring index, kx signed like ky), A[r] and P[r] the pooled sums and B the number of block spectra pooled:
+ *   3. Pooling.  An item's planes and blocks add their sums ring by ring (pool "item"), or every block stands alone (pool "block": the
+ *      planes of an item still pool per block position).  M(r) = B sum_{rho = 1 .. r} pop[rho].  Ring 0 never enters.
+ *   4. Curve.  For ring weights g[rho]: d_g(r) = sum_{rho = 1 .. r} g[rho] A[rho] / sqrt(sum_{rho = 1 .. R} g[rho]^2 P[rho] . M(r)),
+ *      r = 1 .. R; 0 where the denominator is 0; d_g(0) = 0.  The unfiltered curve has g = 1.  (It is the Pearson-like correlation
+ *      sum Re(G conj(N_r)) / sqrt(sum |G|^2 sum |N_r|^2) of the weighted spectrum G = g F over rings 1 .. R with N_r = F / |F| inside rings 1 .. r.)
+ *   5. Peak rule.  For e = R down to 2: i = the first index of the maximum of d[1 .. e]; if i == e, go on; if d[i] - min(d[i .. e]) >= 5e-4
+ *      the peak is ring i with amplitude d[i]; otherwise go on.  No e succeeds: no peak.  Refinement: p = i + (d[i-1] - d[i+1]) /
+ *      (2 (d[i-1] - 2 d[i] + d[i+1])) where that second difference is negative, else p = i (d[0] = 0 serves for i = 1).
+ *   6. Filter family.  Ng filters, 0 .. 64 (default 10).  s_0 = min(2 R / i0, R) with i0 the unfiltered peak's ring, s_0 = R without one;
+ *      s_j = s_0 (0.15 / s_0)^(j / (Ng - 1)), j = 0 .. Ng - 1 (s_0 alone for Ng = 1).  g_j[rho] = 1 - exp(-2 s_j^2 (rho / R)^2): the
+ *      Gaussian high-pass I - I * G evaluated at the ring's own radius.
+ *   7. Result.  p* = the largest refined position among the peaks of the Ng + 1 curves (the first such curve on a tie);
+ *      resolution = pixel_size n / p*, found = true.  No curve has a peak: found = false, resolution = 2 pixel_size, as FRC without a
+ *      crossing.
+ * pssr_decorr_rings_u8: steps 1 - 2.  a [planes][H][W], ct, st [n][n], sums [planes][nby nbx][n / 2 + 1][2].  The kernels are FRC's with one
+ *   image per block: a small launch leaves the block means in the workspace, the row pass stages float(a) - m (zeros past the block) and
+ *   leaves T = c (Ct + i St)[:, 0 .. n/2], [2][n][K] floats per block; the column pass forms 64 x 64 tiles of F in registers, p and sqrtf(p)
+ *   per lane, and reduces them ring by ring in float64; the fold adds the tiles' rows in tile order.  F never goes to memory.  No atomics,
+ *   no fence: the same bits on every run.
+ * Both validate on the host before anything is launched (null pointers, planes, sizes, n odd or outside 16 .. 1024 or larger than the
+ * plane, more than 2^24 blocks, workspace_bytes below pssr_decorr_workspace_bytes): PSSR_ERR_ARG with a message.
+ * pssr_decorr_workspace_bytes is 0 for arguments the entry point rejects and at most about 256 MB: blocks are worked off in chunks. */
+int64_t pssr_decorr_workspace_bytes(int planes, int H, int W, int n);
+int pssr_decorr_rings_u8(const uint8_t* a, const float* ct, const float* st, double* sums, int planes, int H, int W, int n, void* workspace,
+                         int64_t workspace_bytes, pssr_stream_t stream);
+
 /* Several small f32 device-to-device copies in one launch (host struct passed by value to the kernel): the hand-written
  * backward pass moves side results (dbeta doubling as a bias gradient, centre taps, ...) into the flat gradient buffer the
  * all-reduce and AdamW read (the reference leaves this to autograd's .grad accumulation). */

@@ -55,6 +55,9 @@ def __getattr__(name):
     if name in ("frc",):
         from .util import frc
         return frc
+    if name in ("decorr",):
+        from .util import decorr
+        return decorr
     if name in ("estimate_rsf",):
         from .util import estimate_rsf
         return estimate_rsf

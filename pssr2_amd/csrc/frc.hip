@@ -23,6 +23,13 @@
 // Padding: tiles and stages past n or K are zeros in LDS (tables and images both), never reads past a block, a table or T.
 // Determinism: every float32 product and every float64 sum has one fixed order; no atomics, no fence between workgroups.
 // Blocks are worked off in chunks that keep T and the partial rows inside FRC_WS_BYTES of workspace.
+//
+// Decorrelation analysis (pssr2_amd.util.decorr; "Resolution of one image by decorrelation analysis" in include/pssr_mi355.h) is the same
+// transform of one image with the block's mean taken off, so the three kernels are templates on NI, the images per block: NI = 2 is
+// everything above, NI = 1 has half the products (two MFMAs per k-step in the row pass, four in the column pass, T [2][n][K]) and
+// another epilogue: |F|^2 and |F| = sqrtf(|F|^2) of every coefficient in place of the three products, two sums per ring.  In front of
+// it frc_block_means_kernel, one workgroup per block: the integer sum of the block's bytes (a fixed tree in LDS, exact in any order)
+// and m = float(S / n^2), the quotient in double; the row pass stages float(a) - m, zeros past the block as before.
 #include "common.h"
 
 namespace {
@@ -46,7 +53,8 @@ inline bool frc_args_ok(int planes, int H, int W, int n) {
     return (long)planes * (H / n) * (W / n) <= FRC_MAX_BLOCKS;
 }
 
-inline FrcGeom frc_geom(int planes, int H, int W, int n) {
+// ni: images per block (2: the pair of FRC; 1: decorrelation analysis, which keeps a float mean per block beside T)
+inline FrcGeom frc_geom(int planes, int H, int W, int n, int ni) {
     FrcGeom g;
     g.n = n; g.K = n / 2 + 1; g.R = n / 2;
     g.nby = H / n; g.nbx = W / n;
@@ -54,7 +62,8 @@ inline FrcGeom frc_geom(int planes, int H, int W, int n) {
     g.ty = cdiv(n, FRC_TILE); g.tk = cdiv(g.K, FRC_TILE);
     g.tiles = g.ty * g.tk;
     g.nblocks = (long)planes * g.nby * g.nbx;
-    g.per_block_bytes = (long)g.tiles * (g.R + 1) * 3 * (long)sizeof(double) + 4L * n * g.K * (long)sizeof(float);
+    g.per_block_bytes = (long)g.tiles * (g.R + 1) * (ni + 1) * (long)sizeof(double) + 2L * ni * n * g.K * (long)sizeof(float) +
+                        (ni == 1 ? (long)sizeof(float) : 0L);
     long chunk = FRC_WS_BYTES / g.per_block_bytes;
     if (chunk < 1) chunk = 1;
     if (chunk > FRC_MAX_CHUNK) chunk = FRC_MAX_CHUNK;
@@ -86,26 +95,53 @@ __device__ __forceinline__ void stage_f32_32x64(const float* __restrict__ src, l
     }
 }
 
-__global__ __launch_bounds__(256) void frc_rows_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, const float* __restrict__ ct,
-                                                       const float* __restrict__ st, float* __restrict__ T, long block0, int H, int W, int n, int nby,
-                                                       int nbx, int oy, int ox, int tk) {
-    __shared__ float la[FRC_TILE * FRC_APITCH], lb[FRC_TILE * FRC_APITCH], lc[FRC_KT * FRC_TILE], ls[FRC_KT * FRC_TILE];
+// The origin of block g of the call (plane, then row and column of the grid of blocks) in its stack of planes.
+__device__ __forceinline__ long block_origin(long g, int H, int W, int n, int nby, int nbx, int oy, int ox) {
+    const int nb = nby * nbx, blk = (int)(g % nb);
+    return (g / nb * H + oy + blk / nbx * n) * (long)W + ox + blk % nbx * n;
+}
+
+// mean[block of the chunk] = float(S / n^2), S the sum of the block's bytes: partial sums per thread, then a fixed tree in LDS.
+__global__ __launch_bounds__(256) void frc_block_means_kernel(const uint8_t* __restrict__ a, float* __restrict__ mean, long block0, int H, int W,
+                                                              int n, int nby, int nbx, int oy, int ox) {
+    __shared__ unsigned part[256];
+    const int tid = threadIdx.x;
+    const long origin = block_origin(block0 + blockIdx.x, H, W, n, nby, nbx, oy, ox);
+    unsigned s = 0;                                             // at most 2^20 x 255 in all
+    for (int y = tid >> 5; y < n; y += 8)
+        for (int x = tid & 31; x < n; x += 32) s += a[origin + (long)y * W + x];
+    part[tid] = s;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+        if (tid < half) part[tid] += part[tid + half];
+        __syncthreads();
+    }
+    if (tid == 0) mean[blockIdx.x] = (float)((double)part[0] / (double)(n * n));
+}
+
+template <int NI>
+__global__ __launch_bounds__(256) void frc_rows_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, const float* __restrict__ mean,
+                                                       const float* __restrict__ ct, const float* __restrict__ st, float* __restrict__ T, long block0,
+                                                       int H, int W, int n, int nby, int nbx, int oy, int ox, int tk) {
+    __shared__ float limg[NI * FRC_TILE * FRC_APITCH], lc[FRC_KT * FRC_TILE], ls[FRC_KT * FRC_TILE];
     const int K = n / 2 + 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wy = wave >> 1, wx = wave & 1;
     const int y0 = (int)blockIdx.x / tk * FRC_TILE, k0 = (int)blockIdx.x % tk * FRC_TILE;
-    const long g = block0 + blockIdx.y;                         // block of the call: plane, then row and column of the grid of blocks
-    const int nb = nby * nbx, blk = (int)(g % nb);
-    const long origin = (g / nb * H + oy + blk / nbx * n) * (long)W + ox + blk % nbx * n;
-    f32x16 acc[4] = {};                                         // a Ct, a St, b Ct, b St
+    const long origin = block_origin(block0 + blockIdx.y, H, W, n, nby, nbx, oy, ox);
+    float m = 0.f;
+    if constexpr (NI == 1) m = mean[blockIdx.y];
+    f32x16 acc[2 * NI] = {};                                    // a Ct, a St (, b Ct, b St)
     for (int x0 = 0; x0 < n; x0 += FRC_KT) {
-        uint8_t va[8], vb[8];
+        uint8_t v[NI][8];
 #pragma unroll
         for (int it = 0; it < 8; ++it) {
             const int idx = tid + 256 * it, r = idx >> 5, c = idx & 31;
-            va[it] = vb[it] = 0;
+#pragma unroll
+            for (int i = 0; i < NI; ++i) v[i][it] = 0;
             if (y0 + r < n && x0 + c < n) {
                 const long at = origin + (long)(y0 + r) * W + x0 + c;
-                va[it] = a[at]; vb[it] = b[at];
+                v[0][it] = a[at];
+                if constexpr (NI == 2) v[1][it] = b[at];
             }
         }
         stage_f32_32x64(ct, n, x0, n, k0, K, lc);
@@ -113,87 +149,110 @@ __global__ __launch_bounds__(256) void frc_rows_kernel(const uint8_t* __restrict
 #pragma unroll
         for (int it = 0; it < 8; ++it) {
             const int idx = tid + 256 * it, r = idx >> 5, c = idx & 31;
-            la[r * FRC_APITCH + c] = (float)va[it];
-            lb[r * FRC_APITCH + c] = (float)vb[it];
+            if constexpr (NI == 2) {
+                limg[r * FRC_APITCH + c] = (float)v[0][it];
+                limg[FRC_TILE * FRC_APITCH + r * FRC_APITCH + c] = (float)v[1][it];
+            } else {
+                limg[r * FRC_APITCH + c] = y0 + r < n && x0 + c < n ? (float)v[0][it] - m : 0.f;    // zeros past the block, not -m
+            }
         }
         __syncthreads();
 #pragma unroll
         for (int kk = 0; kk < FRC_KT / 2; ++kk) {
             const int k = 2 * kk + (lane >> 5);
-            const float pa = la[(32 * wy + (lane & 31)) * FRC_APITCH + k], pb = lb[(32 * wy + (lane & 31)) * FRC_APITCH + k];
+            float p[NI];
+#pragma unroll
+            for (int i = 0; i < NI; ++i) p[i] = limg[i * FRC_TILE * FRC_APITCH + (32 * wy + (lane & 31)) * FRC_APITCH + k];
             const float c = lc[k * FRC_TILE + 32 * wx + (lane & 31)], s = ls[k * FRC_TILE + 32 * wx + (lane & 31)];
-            acc[0] = mma(pa, c, acc[0]);
-            acc[1] = mma(pa, s, acc[1]);
-            acc[2] = mma(pb, c, acc[2]);
-            acc[3] = mma(pb, s, acc[3]);
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                acc[2 * i] = mma(p[i], c, acc[2 * i]);
+                acc[2 * i + 1] = mma(p[i], s, acc[2 * i + 1]);
+            }
         }
         __syncthreads();
     }
-    float* const out = T + (long)blockIdx.y * 4 * n * K;
+    float* const out = T + (long)blockIdx.y * 2 * NI * n * K;
     const int kx = k0 + 32 * wx + (lane & 31);
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
         const int y = y0 + 32 * wy + acc_row(reg, lane);
         if (y < n && kx < K)
 #pragma unroll
-            for (int m = 0; m < 4; ++m) out[((long)m * n + y) * K + kx] = acc[m][reg];
+            for (int q = 0; q < 2 * NI; ++q) out[((long)q * n + y) * K + kx] = acc[q][reg];
     }
 }
 
+template <int NI>
 __global__ __launch_bounds__(256) void frc_cols_kernel(const float* __restrict__ T, const float* __restrict__ ct, const float* __restrict__ st,
                                                        double* __restrict__ partial, int n, int tk) {
-    // stages: the tables' pieces [2][32][64] and T's four [32][64]; afterwards the three products [3][64][64]
-    __shared__ float lds[6 * FRC_KT * FRC_TILE];
-    static_assert(6 * FRC_KT * FRC_TILE >= 3 * FRC_TILE * FRC_TILE, "the products take the place of the stages");
+    // stages: the tables' pieces [2][32][64] and T's 2 NI planes [32][64]; afterwards the NS = NI + 1 values per coefficient [NS][64][64]
+    constexpr int NS = NI + 1;
+    __shared__ float lds[(2 + 2 * NI) * FRC_KT * FRC_TILE];
+    static_assert((2 + 2 * NI) * FRC_KT * FRC_TILE >= NS * FRC_TILE * FRC_TILE, "the products take the place of the stages");
     const int K = n / 2 + 1, R = n / 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wy = wave >> 1, wx = wave & 1;
     const int ky0 = (int)blockIdx.x / tk * FRC_TILE, k0 = (int)blockIdx.x % tk * FRC_TILE;
-    const float* const Tb = T + (long)blockIdx.y * 4 * n * K;
+    const float* const Tb = T + (long)blockIdx.y * 2 * NI * n * K;
     float* const lc = lds, * const ls = lds + FRC_KT * FRC_TILE, * const lt = lds + 2 * FRC_KT * FRC_TILE;
-    f32x16 acc[4] = {};                                         // Re Fa, Im Fa, Re Fb, Im Fb
+    f32x16 acc[2 * NI] = {};                                    // Re Fa, Im Fa (, Re Fb, Im Fb)
     for (int yy = 0; yy < n; yy += FRC_KT) {
         stage_f32_32x64(ct, n, yy, n, ky0, n, lc);
         stage_f32_32x64(st, n, yy, n, ky0, n, ls);
 #pragma unroll
-        for (int m = 0; m < 4; ++m) stage_f32_32x64(Tb + (long)m * n * K, K, yy, n, k0, K, lt + m * FRC_KT * FRC_TILE);
+        for (int q = 0; q < 2 * NI; ++q) stage_f32_32x64(Tb + (long)q * n * K, K, yy, n, k0, K, lt + q * FRC_KT * FRC_TILE);
         __syncthreads();
 #pragma unroll
         for (int kk = 0; kk < FRC_KT / 2; ++kk) {
             const int k = 2 * kk + (lane >> 5);
             const float c = lc[k * FRC_TILE + 32 * wy + (lane & 31)], s = ls[k * FRC_TILE + 32 * wy + (lane & 31)];
             const float* t = lt + k * FRC_TILE + 32 * wx + (lane & 31);
-            const float ar = t[0], ai = t[FRC_KT * FRC_TILE], br = t[2 * FRC_KT * FRC_TILE], bi = t[3 * FRC_KT * FRC_TILE];
-            acc[0] = mma(c, ar, acc[0]);
-            acc[1] = mma(c, ai, acc[1]);
-            acc[2] = mma(c, br, acc[2]);
-            acc[3] = mma(c, bi, acc[3]);
-            acc[0] = mma(-s, ai, acc[0]);
-            acc[1] = mma(s, ar, acc[1]);
-            acc[2] = mma(-s, bi, acc[2]);
-            acc[3] = mma(s, br, acc[3]);
+            float tr[NI], ti[NI];
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                tr[i] = t[2 * i * FRC_KT * FRC_TILE];
+                ti[i] = t[(2 * i + 1) * FRC_KT * FRC_TILE];
+            }
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                acc[2 * i] = mma(c, tr[i], acc[2 * i]);
+                acc[2 * i + 1] = mma(c, ti[i], acc[2 * i + 1]);
+            }
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                acc[2 * i] = mma(-s, ti[i], acc[2 * i]);
+                acc[2 * i + 1] = mma(s, tr[i], acc[2 * i + 1]);
+            }
         }
         __syncthreads();
     }
-    // the three products of every coefficient of the tile, weighted, into LDS [3][64][64]
+    // the NS values of every coefficient of the tile, weighted, into LDS [NS][64][64]
     {
         const int col = 32 * wx + (lane & 31), kx = k0 + col;
         const float wgt = kx > 0 && kx < R ? 2.f : 1.f;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const int row = 32 * wy + acc_row(reg, lane);
-            const float far = acc[0][reg], fai = acc[1][reg], fbr = acc[2][reg], fbi = acc[3][reg];
-            lds[row * FRC_TILE + col] = wgt * (far * fbr + fai * fbi);
-            lds[(FRC_TILE + row) * FRC_TILE + col] = wgt * (far * far + fai * fai);
-            lds[(2 * FRC_TILE + row) * FRC_TILE + col] = wgt * (fbr * fbr + fbi * fbi);
+            if constexpr (NI == 2) {
+                const float far = acc[0][reg], fai = acc[1][reg], fbr = acc[2][reg], fbi = acc[3][reg];
+                lds[row * FRC_TILE + col] = wgt * (far * fbr + fai * fbi);
+                lds[(FRC_TILE + row) * FRC_TILE + col] = wgt * (far * far + fai * fai);
+                lds[(2 * FRC_TILE + row) * FRC_TILE + col] = wgt * (fbr * fbr + fbi * fbi);
+            } else {
+                const float fr = acc[0][reg], fi = acc[1][reg];
+                const float p = __builtin_fmaf(fr, fr, fi * fi);            // |F|^2, the expression of include/pssr_mi355.h
+                lds[row * FRC_TILE + col] = wgt * __builtin_sqrtf(p);      // |F|
+                lds[(FRC_TILE + row) * FRC_TILE + col] = wgt * p;
+            }
         }
     }
     __syncthreads();
     // ring r of the tile: per spectrum row the run of kx with floor(sqrt(fy^2 + kx^2) + 1/2) == r, that is
     // r^2 - r + 1 <= fy^2 + kx^2 <= r^2 + r (ring 0: the origin alone), cut to the tile's valid columns
-    double* const prow = partial + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (R + 1) * 3;
+    double* const prow = partial + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (R + 1) * NS;
     const int klast = k0 + FRC_TILE - 1 < K - 1 ? k0 + FRC_TILE - 1 : K - 1;
     for (int r = tid; r <= R; r += 256) {
-        double sab = 0., saa = 0., sbb = 0.;
+        double sum[NS] = {};
         for (int row = 0; row < FRC_TILE && ky0 + row < n; ++row) {
             const int ky = ky0 + row, fy = ky <= R ? ky : ky - n, f2 = fy * fy;
             const int hi2 = r * r + r - f2, lo2 = (r > 0 ? r * r - r + 1 : 0) - f2;
@@ -201,13 +260,12 @@ __global__ __launch_bounds__(256) void frc_cols_kernel(const float* __restrict__
             int lo = lo2 <= 0 ? 0 : isqrt_i(lo2 - 1) + 1, hi = isqrt_i(hi2);
             if (lo < k0) lo = k0;
             if (hi > klast) hi = klast;
-            for (int at = row * FRC_TILE + lo - k0; at <= row * FRC_TILE + hi - k0; ++at) {
-                sab += (double)lds[at];
-                saa += (double)lds[FRC_TILE * FRC_TILE + at];
-                sbb += (double)lds[2 * FRC_TILE * FRC_TILE + at];
-            }
+            for (int at = row * FRC_TILE + lo - k0; at <= row * FRC_TILE + hi - k0; ++at)
+#pragma unroll
+                for (int q = 0; q < NS; ++q) sum[q] += (double)lds[q * FRC_TILE * FRC_TILE + at];
         }
-        prow[3 * r] = sab; prow[3 * r + 1] = saa; prow[3 * r + 2] = sbb;
+#pragma unroll
+        for (int q = 0; q < NS; ++q) prow[NS * r + q] = sum[q];
     }
 }
 
@@ -222,11 +280,38 @@ __global__ __launch_bounds__(256) void frc_fold_kernel(const double* __restrict_
     }
 }
 
+// The launches of one call: per chunk of blocks (the means,) the row pass, the column pass and the fold.
+template <int NI>
+int frc_launch(const uint8_t* a, const uint8_t* b, const float* ct, const float* st, double* sums, int H, int W, const FrcGeom& g, void* workspace,
+               pssr_stream_t stream) {
+    const int k = (g.R + 1) * (NI + 1);
+    double* const partial = (double*)workspace;
+    float* const T = (float*)((char*)workspace + (long)g.chunk * g.tiles * k * (long)sizeof(double));
+    float* const mean = T + (long)g.chunk * 2 * NI * g.n * g.K;          // NI == 1 only
+    hipStream_t s = (hipStream_t)stream;
+    for (long block0 = 0; block0 < g.nblocks; block0 += g.chunk) {
+        const int count = (int)(g.nblocks - block0 < g.chunk ? g.nblocks - block0 : g.chunk);
+        if (NI == 1) {
+            hipLaunchKernelGGL(frc_block_means_kernel, dim3(count), dim3(256), 0, s, a, mean, block0, H, W, g.n, g.nby, g.nbx, g.oy, g.ox);
+            PSSR_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(frc_rows_kernel<NI>, dim3(g.tiles, count), dim3(256), 0, s, a, b, (const float*)mean, ct, st, T, block0, H, W, g.n, g.nby,
+                           g.nbx, g.oy, g.ox, g.tk);
+        PSSR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(frc_cols_kernel<NI>, dim3(g.tiles, count), dim3(256), 0, s, (const float*)T, ct, st, partial, g.n, g.tk);
+        PSSR_LAUNCH_CHECK();
+        const long values = (long)count * k;
+        hipLaunchKernelGGL(frc_fold_kernel, dim3(grid1d(values, 4096)), dim3(256), 0, s, (const double*)partial, sums + block0 * k, values, g.tiles, k);
+        PSSR_LAUNCH_CHECK();
+    }
+    return PSSR_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t pssr_frc_workspace_bytes(int planes, int H, int W, int n) {
     if (!frc_args_ok(planes, H, W, n)) return 0;
-    const FrcGeom g = frc_geom(planes, H, W, n);
+    const FrcGeom g = frc_geom(planes, H, W, n, 2);
     return (int64_t)g.chunk * g.per_block_bytes;
 }
 
@@ -238,20 +323,25 @@ extern "C" int pssr_frc_rings_u8(const uint8_t* a, const uint8_t* b, const float
                FRC_MIN_N, FRC_MAX_N, n);
     PSSR_CHECK(n <= H && n <= W, PSSR_ERR_ARG, "frc_rings_u8: a block of %d does not fit a %d x %d plane", n, H, W);
     PSSR_CHECK(frc_args_ok(planes, H, W, n), PSSR_ERR_ARG, "frc_rings_u8: %ld blocks in all (at most 2^24 per call)", (long)planes * (H / n) * (W / n));
-    const FrcGeom g = frc_geom(planes, H, W, n);
-    const int k = (g.R + 1) * 3;
-    double* const partial = (double*)workspace;
-    float* const T = (float*)((char*)workspace + (long)g.chunk * g.tiles * k * (long)sizeof(double));
-    hipStream_t s = (hipStream_t)stream;
-    for (long block0 = 0; block0 < g.nblocks; block0 += g.chunk) {
-        const int count = (int)(g.nblocks - block0 < g.chunk ? g.nblocks - block0 : g.chunk);
-        hipLaunchKernelGGL(frc_rows_kernel, dim3(g.tiles, count), dim3(256), 0, s, a, b, ct, st, T, block0, H, W, n, g.nby, g.nbx, g.oy, g.ox, g.tk);
-        PSSR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(frc_cols_kernel, dim3(g.tiles, count), dim3(256), 0, s, (const float*)T, ct, st, partial, n, g.tk);
-        PSSR_LAUNCH_CHECK();
-        const long values = (long)count * k;
-        hipLaunchKernelGGL(frc_fold_kernel, dim3(grid1d(values, 4096)), dim3(256), 0, s, (const double*)partial, sums + block0 * k, values, g.tiles, k);
-        PSSR_LAUNCH_CHECK();
-    }
-    return PSSR_OK;
+    return frc_launch<2>(a, b, ct, st, sums, H, W, frc_geom(planes, H, W, n, 2), workspace, stream);
+}
+
+extern "C" int64_t pssr_decorr_workspace_bytes(int planes, int H, int W, int n) {
+    if (!frc_args_ok(planes, H, W, n)) return 0;
+    const FrcGeom g = frc_geom(planes, H, W, n, 1);
+    return (int64_t)g.chunk * g.per_block_bytes;
+}
+
+extern "C" int pssr_decorr_rings_u8(const uint8_t* a, const float* ct, const float* st, double* sums, int planes, int H, int W, int n, void* workspace,
+                                    int64_t workspace_bytes, pssr_stream_t stream) {
+    PSSR_CHECK(a && ct && st && sums && workspace, PSSR_ERR_ARG, "decorr_rings_u8: null pointer");
+    PSSR_CHECK(planes > 0 && H > 0 && W > 0, PSSR_ERR_ARG, "decorr_rings_u8: planes, H and W must be positive (%d, %d, %d)", planes, H, W);
+    PSSR_CHECK(n >= FRC_MIN_N && n <= FRC_MAX_N && n % 2 == 0, PSSR_ERR_ARG, "decorr_rings_u8: the block side must be even and in %d .. %d, given %d",
+               FRC_MIN_N, FRC_MAX_N, n);
+    PSSR_CHECK(n <= H && n <= W, PSSR_ERR_ARG, "decorr_rings_u8: a block of %d does not fit a %d x %d plane", n, H, W);
+    PSSR_CHECK(frc_args_ok(planes, H, W, n), PSSR_ERR_ARG, "decorr_rings_u8: %ld blocks in all (at most 2^24 per call)", (long)planes * (H / n) * (W / n));
+    const FrcGeom g = frc_geom(planes, H, W, n, 1);
+    PSSR_CHECK(workspace_bytes >= (int64_t)g.chunk * g.per_block_bytes, PSSR_ERR_ARG, "decorr_rings_u8: a workspace of %ld bytes is short of the %ld needed",
+               (long)workspace_bytes, (long)((int64_t)g.chunk * g.per_block_bytes));
+    return frc_launch<1>(a, nullptr, ct, st, sums, H, W, g, workspace, stream);
 }

@@ -1415,3 +1415,32 @@ def frc_rings_u8(a, b, block, window="hann"):
     L.check(lib.pssr_frc_rings_u8(L.ptr(a), L.ptr(b), L.ptr(ct), L.ptr(st), L.ptr(sums), planes, H, W, block, L.ptr(ws), L.stream_ptr()),
             "pssr_frc_rings_u8")
     return sums
+
+
+def decorr_rings_u8(a, block, window="hann"):
+    """uint8 device tensor ``a`` [..., H, W], an even block side ``block`` in 16 .. 1024 (at most ``min(H, W)``) -> float64 device tensor
+    [planes, nby * nbx, block // 2 + 1, 2]: per plane, per block of the centred grid of ``(H // block) x (W // block)`` blocks and per ring
+    of spatial frequency the sums ``|F|`` and ``|F|**2`` over the windowed spectrum of the block minus its own mean (steps 1 - 2 of
+    "decorrelation analysis" in include/pssr_mi355.h).  The tables are ``frc_tables``' and so is their device cache; the same bits on every
+    call."""
+    if not torch.is_tensor(a) or a.dtype != torch.uint8 or not a.is_cuda or a.dim() < 2:
+        raise ValueError("decorr_rings_u8 needs a uint8 device tensor [..., H, W]")
+    _check_frc_block("decorr_rings_u8", block)
+    if window not in FRC_WINDOWS:
+        raise ValueError(f"window must be one of {FRC_WINDOWS}. Given {window!r}.")
+    H, W = a.shape[-2:]
+    if block > min(H, W):
+        raise ValueError(f"decorr_rings_u8: a block of {block} does not fit a {H}x{W} plane")
+    planes = a.numel() // (H * W)
+    nb = (H // block) * (W // block)
+    if planes < 1 or planes * nb > 1 << 24:
+        raise ValueError(f"decorr_rings_u8: {planes} planes of {nb} blocks (at least one plane, at most 2**24 blocks in all)")
+    a = a.contiguous()
+    ct, st = _frc_device_tables(block, window, a.device)
+    lib = L.lib()
+    nbytes = lib.pssr_decorr_workspace_bytes(planes, H, W, block)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+    sums = torch.empty(planes, nb, block // 2 + 1, 2, dtype=torch.float64, device=a.device)
+    L.check(lib.pssr_decorr_rings_u8(L.ptr(a), L.ptr(ct), L.ptr(st), L.ptr(sums), planes, H, W, block, L.ptr(ws), nbytes, L.stream_ptr()),
+            "pssr_decorr_rings_u8")
+    return sums

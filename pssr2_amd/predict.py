@@ -494,7 +494,11 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
 
     ``"rsf"`` (not in the default tuple either) reports how much sharper the prediction is than the optics behind its LR side: the width
     ``sigma``, in HR pixels, of the Gaussian resolution-scaling function that ``util.estimate_rsf`` (default candidates, one choice per image)
-    finds between the cropped uint8 prediction, before ``norm``, and the item's own LR side, cut as for ``"rse"``.  No ground truth is needed."""
+    finds between the cropped uint8 prediction, before ``norm``, and the item's own LR side, cut as for ``"rse"``.  No ground truth is needed.
+
+    ``"decorr"`` (not in the default tuple either) is the resolution of the prediction alone, in HR pixels: ``util.decorr`` with its defaults
+    (one block per plane, Hann window, ten high-pass filters, the image's planes pooled) of the cropped uint8 prediction, before ``norm``.
+    Unlike ``"frc"`` it does not look at the ground truth: it measures the detail the prediction holds, not its agreement with anything."""
     import math
     from .util import pixel_metric
     _check_ensemble(ensemble, device)
@@ -503,7 +507,7 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
     image_range = 255
     metrics = [metrics] if type(metrics) is str else list(metrics)
     out = {m: [] for m in metrics}
-    if ("frc" in out or "rsf" in out) and torch.device(device).type != "cuda":                   # as _check_ensemble: before model, dataset or device are touched
+    if ("frc" in out or "rsf" in out or "decorr" in out) and torch.device(device).type != "cuda":                   # as _check_ensemble: before model, dataset or device are touched
         raise RuntimeError("pssr2_amd.predict runs on an MI355X (HIP) device only; there is no CPU fallback")
     model.to(device)
     model.eval()
@@ -528,6 +532,9 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
             if "frc" in out:
                 from .util import frc
                 out["frc"].extend(frc(hat_dev, hr_dev).resolution.tolist())
+            if "decorr" in out:
+                from .util import decorr
+                out["decorr"].extend(decorr(hat_dev).resolution.tolist())
             if "rsf" in out:
                 out["rsf"].extend(_score_items(lr, hat_dev, crop_res, hr_hat.shape[-1] // lr.shape[-1], fit, rsf=True).sigma.tolist())
             if norm:

@@ -710,6 +710,159 @@ def frc(a, b, *, block=None, window: str = "hann", threshold: float = 1 / 7, smo
     return FRC(curve if to_numpy else torch.from_numpy(curve).to(dev), freq, resolution, crossed, block)
 
 
+Decorr = namedtuple("Decorr", "resolution found peak amplitude curves freq block")
+DECORR_POOLS = ("item", "block")     # decorr's ``pool``
+DECORR_MAX_FILTERS = 64
+DECORR_MIN_DROP = 5e-4               # how far a curve must fall behind its maximum for that to count as a peak
+DECORR_LAST_SIGMA = 0.15             # the weakest high-pass of the family
+
+_DECORR_POP = {}                     # n -> float64 [n // 2 + 1], the ring populations of the full spectrum
+
+
+def _decorr_pop(n: int):
+    if n not in _DECORR_POP:
+        R = n // 2
+        f = np.arange(n, dtype=np.int64)
+        f = np.where(f <= R, f, f - n)
+        q = f[:, None] ** 2 + f[None, :] ** 2
+        r = np.floor(np.sqrt(q.astype(np.float64)) + 0.5).astype(np.int64)
+        r += (q > r * r + r).astype(np.int64) - ((r > 0) & (q < r * r - r + 1)).astype(np.int64)     # (isqrt(4 q) + 1) // 2 whatever the float root did
+        _DECORR_POP[n] = np.bincount(r[r <= R], minlength=R + 1).astype(np.float64)
+    return _DECORR_POP[n]
+
+
+def _decorr_peak(d):
+    """Step 5 of include/pssr_mi355.h on one curve ``d[0 .. R]`` -> ``(ring, refined position, amplitude)`` or ``None``."""
+    R = len(d) - 1
+    for e in range(R, 1, -1):
+        i = 1 + int(np.argmax(d[1:e + 1]))                     # the first of equal maxima
+        if i == e:
+            continue
+        if d[i] - d[i:e + 1].min() >= DECORR_MIN_DROP:
+            before, here, after = float(d[i - 1]), float(d[i]), float(d[i + 1])
+            bend = before - 2.0 * here + after
+            return i, (i + 0.5 * (before - after) / bend if bend < 0 else float(i)), here
+    return None
+
+
+def _decorr_resolve(sums, n: int, filters: int, pixel_size: float):
+    """``(resolution, found, peak, amplitude, curves, chosen)`` of one item (or one block) from the ring sums of the spectra it pools
+    (``sums``: float64 [..., n // 2 + 1, 2], the layout of ``pssr_decorr_rings_u8``; every leading axis pools), in exactly the expressions of
+    steps 3 - 7 of include/pssr_mi355.h: the sums add ring by ring, ``d_g(r) = sum_{1..r} g A / sqrt(sum_{1..R} g^2 P . M(r))`` for the
+    unfiltered curve and the ``filters`` high-passed ones, the peak rule on each, the largest refined peak position ``p*`` (``chosen``: the
+    index of its curve, ``None`` without one; ``peak`` is then NaN and ``amplitude`` 0) and ``resolution = pixel_size n / p*``, or the
+    sampling limit ``2 pixel_size`` where no curve peaks.  No device involved."""
+    R = n // 2
+    flat = np.asarray(sums, dtype=np.float64).reshape(-1, R + 1, 2)
+    pooled = flat.sum(axis=0)
+    A, P = pooled[1:, 0], pooled[1:, 1]
+    M = flat.shape[0] * np.cumsum(_decorr_pop(n)[1:])
+    rho2 = (np.arange(1, R + 1, dtype=np.float64) / R) ** 2
+
+    def curve(g):
+        den = np.sqrt(float((g * g * P).sum()) * M)
+        d = np.zeros(R + 1, dtype=np.float64)
+        np.divide(np.cumsum(g * A), den, out=d[1:], where=den > 0)
+        return d
+
+    curves = [curve(np.ones(R, dtype=np.float64))]
+    peaks = [_decorr_peak(curves[0])]
+    if filters > 0:
+        s0 = min(2.0 * R / peaks[0][0], float(R)) if peaks[0] else float(R)
+        for j in range(filters):
+            s = s0 * (DECORR_LAST_SIGMA / s0) ** (j / (filters - 1)) if filters > 1 else s0
+            curves.append(curve(1.0 - np.exp(-2.0 * s * s * rho2)))
+            peaks.append(_decorr_peak(curves[-1]))
+    chosen = None
+    for k, pk in enumerate(peaks):
+        if pk is not None and (chosen is None or pk[1] > peaks[chosen][1]):
+            chosen = k
+    curves = np.stack(curves)
+    if chosen is None:
+        return 2.0 * pixel_size, False, math.nan, 0.0, curves, None
+    _, p, amplitude = peaks[chosen]
+    return pixel_size * n / p, True, p, amplitude, curves, chosen
+
+
+def _decorr_assemble(sums, n_img: int, c: int, nby: int, nbx: int, n: int, filters: int, pool: str, pixel_size: float, batched: bool):
+    """The host half of ``decorr``: ``_decorr_resolve`` per item (``pool="item"``) or per block of the grid (``"block"``; the item's planes
+    pool either way) of the ring sums of a batch, and the result arrays in their shapes."""
+    R = n // 2
+    sums = np.asarray(sums, dtype=np.float64).reshape(n_img, c, nby * nbx, R + 1, 2)
+    if pool == "item":
+        items = [_decorr_resolve(sums[i], n, filters, pixel_size) for i in range(n_img)]
+        shape = (n_img,)
+    else:
+        items = [_decorr_resolve(sums[i, :, k], n, filters, pixel_size) for i in range(n_img) for k in range(nby * nbx)]
+        shape = (n_img, nby, nbx)
+    resolution = np.array([it[0] for it in items], dtype=np.float64).reshape(shape)
+    found = np.array([it[1] for it in items], dtype=bool).reshape(shape)
+    peak = np.array([it[2] for it in items], dtype=np.float64).reshape(shape)
+    amplitude = np.array([it[3] for it in items], dtype=np.float64).reshape(shape)
+    curves = np.stack([it[4] for it in items]).reshape(shape + (filters + 1, R + 1))
+    if not batched:
+        resolution, found, peak, amplitude, curves = resolution[0], found[0], peak[0], amplitude[0], curves[0]
+        if pool == "item":
+            resolution, found, peak, amplitude = float(resolution), bool(found), float(peak), float(amplitude)
+    return resolution, found, peak, amplitude, curves
+
+
+def decorr(img, *, block=None, window: str = "hann", filters: int = 10, pool: str = "item", pixel_size: float = 1.0, to_numpy: bool = True):
+    r"""Resolution of one image by decorrelation analysis (Descloux, Grußmayer, Radenovic, Nature Methods 2019): the figure ``frc`` gives
+    for a pair, from a single image, with no threshold and no calibration.  ``img``: a uint8 array or device tensor [N, C, H, W] (or one
+    [C, H, W] or [H, W] image).  Each plane is cut into the centred grid of ``block x block`` blocks as in ``frc`` (``None``: the largest
+    even side that fits, at most 1024), each block loses its own mean, is windowed and transformed, and its spectrum is correlated with its
+    normalised self inside a growing disc; the position of that curve's peak, pushed outwards by a family of ``filters`` (0 .. 64) Gaussian
+    high-passes, is the cut-off (include/pssr_mi355.h has the definitions).  ``pool="item"`` pools the planes and blocks of an item;
+    ``pool="block"`` keeps every block of the grid apart (the planes of an item still pool) and returns a local-resolution map.
+    Returns ``Decorr(resolution, found, peak, amplitude, curves, freq, block)``:
+
+    * ``resolution``: float64 [N] (``"block"``: [N, nby, nbx]), ``pixel_size * block / peak``; ``found``: bool of the same shape, ``False``
+      where no curve has a peak -- nothing below the sampling limit separates signal from noise -- and the resolution is then
+      ``2 * pixel_size``; ``peak``: the refined peak position in rings (NaN where none), ``amplitude``: the curve's value there (0 where none);
+    * ``curves``: float64 [N, filters + 1, block // 2 + 1] (``"block"``: [N, nby, nbx, filters + 1, block // 2 + 1]), the unfiltered curve
+      first; ``freq``: float64 [block // 2 + 1], ``r / (block * pixel_size)``.
+
+    One sums launch sequence for the whole batch (``pssr_decorr_rings_u8``: the transform as two matrix products per block on the f32-input
+    MFMA, two ring sums in float64 in a fixed order -- every filter is a weight per ring of those two sums, so no filter costs a transform)
+    and one copy of the sums to the host; the curves and peaks are computed there.  An image without the batch axis gets ``curves``
+    [filters + 1, block // 2 + 1] and scalars (maps [nby, nbx]).  ``to_numpy=False`` leaves ``curves`` on the device."""
+    if window not in ops.FRC_WINDOWS:
+        raise ValueError(f"window must be one of {ops.FRC_WINDOWS}. Given {window!r}.")
+    if isinstance(filters, bool) or not isinstance(filters, (int, np.integer)) or not 0 <= filters <= DECORR_MAX_FILTERS:
+        raise ValueError(f"filters must be an int from 0 to {DECORR_MAX_FILTERS} (high-passed curves beside the plain one). Given {filters!r}.")
+    if pool not in DECORR_POOLS:
+        raise ValueError(f"pool must be one of {DECORR_POOLS}. Given {pool!r}.")
+    if isinstance(pixel_size, bool) or not isinstance(pixel_size, (int, float, np.integer, np.floating)) or not pixel_size > 0:
+        raise ValueError(f"pixel_size must be a positive number. Given {pixel_size!r}.")
+    host = torch.is_tensor(img) and not img.is_cuda
+    a = img if torch.is_tensor(img) else torch.as_tensor(np.ascontiguousarray(img))
+    if a.dtype != torch.uint8:
+        raise TypeError(f"decorr takes uint8 images; img is {a.dtype}")
+    if host:
+        raise RuntimeError("pssr2_amd.util.decorr runs on an MI355X (HIP) device only; there is no CPU fallback")
+    if a.dim() not in (2, 3, 4):
+        raise ValueError(f"img must be [images, planes, height, width] or one [planes, height, width] or [height, width] image. The shape is {tuple(a.shape)}.")
+    batched = a.dim() == 4
+    a = a.reshape((1,) * (4 - a.dim()) + tuple(a.shape))
+    n_img, c, H, W = a.shape
+    if min(n_img, c) < 1 or min(H, W) < ops.FRC_MIN_BLOCK:
+        raise ValueError(f"decorr needs at least one plane of at least {ops.FRC_MIN_BLOCK}x{ops.FRC_MIN_BLOCK} pixels. The shape is {tuple(a.shape)}.")
+    if block is None:
+        block = min(H, W, ops.FRC_MAX_BLOCK) // 2 * 2
+    elif isinstance(block, bool) or not isinstance(block, (int, np.integer)) or block % 2 or not ops.FRC_MIN_BLOCK <= block <= min(H, W, ops.FRC_MAX_BLOCK):
+        raise ValueError(f"block must be an even int from {ops.FRC_MIN_BLOCK} to {min(H, W, ops.FRC_MAX_BLOCK)} (the smaller side, at most "
+                         f"{ops.FRC_MAX_BLOCK}). Given {block!r}.")
+    block, filters, pixel_size = int(block), int(filters), float(pixel_size)
+    if not (a.is_cuda or torch.cuda.is_available()):
+        raise RuntimeError("pssr2_amd.util.decorr needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
+    dev = a.device if a.is_cuda else "cuda"
+    sums = ops.decorr_rings_u8(a.to(dev), block, window).cpu().numpy()
+    resolution, found, peak, amplitude, curves = _decorr_assemble(sums, n_img, c, H // block, W // block, block, filters, pool, pixel_size, batched)
+    freq = np.arange(block // 2 + 1, dtype=np.float64) / (block * pixel_size)
+    return Decorr(resolution, found, peak, amplitude, curves if to_numpy else torch.from_numpy(curves).to(dev), freq, block)
+
+
 def _sort_tiles(name: str):
     """Sort key of tile names ``{sheet}_{tile}_{slice}[.ext]`` (pssr/util.py:110-114): slice first, then tile."""
     if "." not in name:
