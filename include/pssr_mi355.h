@@ -951,6 +951,36 @@ int64_t pssr_decorr_workspace_bytes(int planes, int H, int W, int n);
 int pssr_decorr_rings_u8(const uint8_t* a, const float* ct, const float* st, double* sums, int planes, int H, int W, int n, void* workspace,
                          int64_t workspace_bytes, pssr_stream_t stream);
 
+/* The noise model of a pair, measured: level-conditional moments (pssr2_amd.util.estimate_noise; csrc/levels.hip).  Let D be the reduced
+ * (and, if wanted, RSF-blurred) HR image and L = clip8(rint(D (1 - i) + i Poisson(D) + g + N(0, sigma_n))), the crappifier family of this
+ * package.  On every grey level v far from the clipping ends E[L | D = v] = v + g and Var[L | D = v] = i^2 v + sigma_n^2: a
+ * photon-transfer curve, binned by the signal the pair already contains.  The slope of the variance against the level is i^2, its
+ * intercept sigma_n^2 (plus the 1/12 of the rounding, which is not taken off), the mean residual is g, and pixels at exactly 0 or 255 on
+ * levels where noise cannot reach them are salt and pepper.
+ * Inputs: two uint8 stacks D, L [planes][per_plane], per_plane 1 .. 2^28.
+ *   1. Table (device).  Per plane and level v = 0 .. 255, over the pixels with D = v: n = their number, S1 = sum L, S2 = sum L^2,
+ *      n0 = #{L = 0}, n255 = #{L = 255}.  Exact unsigned 64-bit integers, layout [planes][256][5] in that order.
+ *   2. Pooling (device, int64 adds).  The planes of an item add their tables (pool "item"), or every plane of every item (pool "all").
+ *   3. Fit (host, pssr2_amd.util._noise_fit, Python ints and floats, from one [256][5] table, with min_count >= 2 and guard > 0).
+ *      Saturated pixels are taken off: n' = n - n0 - n255, S1' = S1 - 255 n255, S2' = S2 - 255^2 n255.
+ *      pepper = sum_{v >= 128} n0[v] / sum_{v >= 128} n[v], salt = sum_{v < 128} n255[v] / sum_{v < 128} n[v], each 0 for an empty
+ *      denominator; amount = pepper + salt, or twice the one side when the other has no pixels.
+ *      Level v is used when n' >= min_count (and n' >= 2) and, with mean_v = S1' / n', var_v = (S2' - S1'^2 / n') / (n' - 1) and
+ *      sd = sqrt(var_v): mean_v - guard sd > 0 and mean_v + guard sd < 255.
+ *      Two weighted least-squares lines over the used levels, weights n', in the centred form sum w (v - vbar)(y - ybar) / sum w (v - vbar)^2:
+ *      var_v ~ slope v + intercept and mean_v ~ alpha v + beta.  With fewer than two distinct used levels slope = 0, intercept = the
+ *      weighted mean variance, alpha = 1, beta = the weighted mean of mean_v - v.  With none everything is 0 and found = false.
+ *      gain = sum n' (mean_v - v) / sum n', poisson = sqrt(max(slope, 0)), gaussian = sqrt(max(intercept, 0)), saltpepper = 100 amount.
+ * pssr_level_moments_u8: step 1.  Per-wave private LDS tables, integer LDS adds, a flush into 64-bit registers every 2^14 pixels, one
+ *   row of 1280 64-bit partial sums per workgroup and plane in the workspace, and a second small launch that adds the rows: no global
+ *   atomics, no fence, no floating point, the same bits on every run.  Planes may start at any address.
+ * It validates on the host before anything is launched (null pointers, planes < 1, per_plane outside 1 .. 2^28, workspace_bytes below
+ * pssr_level_moments_workspace_bytes): PSSR_ERR_ARG with a message.  pssr_level_moments_workspace_bytes is 0 for arguments the entry
+ * point rejects. */
+int64_t pssr_level_moments_workspace_bytes(int planes, int64_t per_plane);
+int pssr_level_moments_u8(const uint8_t* d, const uint8_t* l, uint64_t* table, int planes, int64_t per_plane, void* workspace,
+                          int64_t workspace_bytes, pssr_stream_t stream);
+
 /* Several small f32 device-to-device copies in one launch (host struct passed by value to the kernel): the hand-written
  * backward pass moves side results (dbeta doubling as a bias gradient, centre taps, ...) into the flat gradient buffer the
  * all-reduce and AdamW read (the reference leaves this to autograd's .grad accumulation). */

@@ -61,6 +61,9 @@ def __getattr__(name):
     if name in ("estimate_rsf",):
         from .util import estimate_rsf
         return estimate_rsf
+    if name in ("estimate_noise",):
+        from .util import estimate_noise
+        return estimate_noise
     if name in ("FusedAdamW",):
         from .optim import FusedAdamW
         return FusedAdamW

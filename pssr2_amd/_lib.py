@@ -157,6 +157,10 @@ def lib():
         _lib.pssr_decorr_workspace_bytes.restype = c_i64
         _lib.pssr_decorr_workspace_bytes.argtypes = [c_int] * 4
         _lib.pssr_decorr_rings_u8.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_i64, c_void_p]
+        # level-conditional moments of a pair (csrc/levels.hip)
+        _lib.pssr_level_moments_workspace_bytes.restype = c_i64
+        _lib.pssr_level_moments_workspace_bytes.argtypes = [c_int, c_i64]
+        _lib.pssr_level_moments_u8.argtypes = [c_void_p] * 3 + [c_int, c_i64, c_void_p, c_i64, c_void_p]
         # one-pass backward of a flat-K source (csrc/pre_xcol_bwd.hip)
         _lib.pssr_flatk_bwd_pair_supported.argtypes = [c_int] * 3
         _lib.pssr_flatk_bwd_pair_parts.argtypes = [c_i64]

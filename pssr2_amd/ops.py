@@ -1351,6 +1351,32 @@ def rsf_reduce_u8(y, taps, radius, sel):
 
 
 # ----------------------------------------------------------------------------------------------
+# level-conditional moments of a pair (csrc/levels.hip; definitions in include/pssr_mi355.h)
+LEVEL_MOMENTS = 5                    # per level of d: n, sum l, sum l*l, #{l == 0}, #{l == 255}
+
+
+def level_moments_u8(d, l):
+    """uint8 device tensors ``d`` and ``l`` of the same shape [planes, h, w] or [planes, n] (1 .. 2**28 pixels per plane) -> int64
+    [planes, 256, 5]: per plane and grey level ``v`` of ``d``, over the pixels with ``d == v``, their number, the exact ``sum l`` and
+    ``sum l*l``, and how many of them have ``l == 0`` and ``l == 255``.  One pass over both; the same bits on every run."""
+    if not (torch.is_tensor(d) and torch.is_tensor(l)) or d.dtype != torch.uint8 or l.dtype != torch.uint8 or d.shape != l.shape \
+            or not (d.is_cuda and l.is_cuda) or d.dim() not in (2, 3):
+        raise ValueError("level_moments_u8 needs two uint8 device tensors of the same shape [planes, h, w] or [planes, n]")
+    planes = d.shape[0]
+    per_plane = d.numel() // planes if planes else 0
+    if planes < 1 or per_plane < 1 or per_plane > 1 << 28:
+        raise ValueError(f"level_moments_u8: {planes} planes of {per_plane} pixels (at least one, at most 2**28 pixels each)")
+    d, l = d.contiguous(), l.contiguous()
+    lib = L.lib()
+    ws_bytes = lib.pssr_level_moments_workspace_bytes(planes, per_plane)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d.device)
+    table = torch.empty(planes, 256, LEVEL_MOMENTS, dtype=torch.int64, device=d.device)
+    L.check(lib.pssr_level_moments_u8(L.ptr(d), L.ptr(l), L.ptr(table), planes, per_plane, L.ptr(ws), ws_bytes, L.stream_ptr()),
+            "pssr_level_moments_u8")
+    return table
+
+
+# ----------------------------------------------------------------------------------------------
 # Fourier ring correlation (csrc/frc.hip; definitions in include/pssr_mi355.h)
 FRC_WINDOWS = ("hann", "none")       # frc's ``window``
 FRC_MIN_BLOCK, FRC_MAX_BLOCK = 16, 1024

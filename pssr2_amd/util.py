@@ -459,9 +459,11 @@ def estimate_rsf(lr, hr_hat, *, sigmas=None, pool: str = "item", pixel_size: flo
     return RSF(sigma, fwhm, score, curve if to_numpy else torch.from_numpy(curve).to(hat.device), index, m)
 
 
-def _consistency_rsf(lr, hr_hat, fit, rsf, to_numpy):
-    """``consistency_map(rsf=...)``: the map after a resolution-scaling function has been fitted (``"fit"``) or given (a width in HR pixels,
-    or one per item)."""
+def _rsf_reduced(who, lr, hr_hat, rsf):
+    """The shared front half of ``consistency_map(rsf=...)`` and ``estimate_noise(rsf=...)``: the resolution-scaling function fitted
+    (``"fit"``) or given (a width in HR pixels, or one per item), one ``_rsf_sums`` launch, and both sides inside its margin ->
+    ``(d, lc, rows, sel, sig, per_item, batched, scale, m)`` with ``d`` uint8 [N, C, h - 2m, w - 2m] the blurred reduction of every plane at
+    its item's width ``sig[per_item[i]]`` (row ``sel[p]`` of the search sums ``rows``) and ``lc`` the matching frames of ``lr``."""
     if isinstance(rsf, str):
         if rsf != "fit":
             raise ValueError(f'rsf must be None, "fit", a sigma in HR pixels or one sigma per item. Given {rsf!r}.')
@@ -475,7 +477,7 @@ def _consistency_rsf(lr, hr_hat, fit, rsf, to_numpy):
     shape = tuple(hr_hat.shape) if hasattr(hr_hat, "shape") else np.shape(hr_hat)
     if isinstance(per_item, list) and (len(shape) != 4 or len(per_item) != shape[0]):
         raise ValueError(f"rsf as a sequence needs one sigma per item of a 4-D batch. Given {len(per_item)} for a shape of {shape}.")
-    hat, frames, batched, scale, taps, R, m, rows = _rsf_sums("consistency_map", lr, hr_hat, sig)
+    hat, frames, batched, scale, taps, R, m, rows = _rsf_sums(who, lr, hr_hat, sig)
     (n_img, c), K = hat.shape[:2], len(sig)
     hc, wc = frames.shape[-2] - 2 * m, frames.shape[-1] - 2 * m
     if per_item is None:
@@ -485,8 +487,16 @@ def _consistency_rsf(lr, hr_hat, fit, rsf, to_numpy):
     sel = [k for k in per_item for _ in range(c)]
     d = ops.rsf_reduce_u8(hat, taps, R, sel)
     lc = ops.crop_shift_u8(frames, [(m, m)] * (n_img * c), hc, wc)
+    return d, lc, rows, sel, sig, per_item, batched, scale, m
+
+
+def _consistency_rsf(lr, hr_hat, fit, rsf, to_numpy):
+    """``consistency_map(rsf=...)``: the map after a resolution-scaling function has been fitted (``"fit"``) or given (a width in HR pixels,
+    or one per item)."""
+    d, lc, rows, sel, sig, per_item, batched, _, m = _rsf_reduced("consistency_map", lr, hr_hat, rsf)
+    (n_img, c, hc, wc), K = d.shape, len(sig)
     fits = [_consistency_fit(hc * wc, (row[3 * k], row[3 * K], row[3 * k + 1], row[3 * k + 2], row[3 * K + 1]), fit) for row, k in zip(rows, sel)]
-    tables = torch.tensor([f[3] for f in fits], dtype=torch.int32).to(hat.device)
+    tables = torch.tensor([f[3] for f in fits], dtype=torch.int32).to(d.device)
     cmap, sse = ops.consistency_map_u8(d, lc, tables)
     stats = [np.array([f[k] for f in fits], dtype=np.float64).reshape(n_img, c) for k in range(3)]
     rse = np.array([math.sqrt(v / (hc * wc)) / 256 for v in sse.cpu().tolist()], dtype=np.float64).reshape(n_img, c)
@@ -537,6 +547,162 @@ def consistency_map(lr, hr_hat, *, fit: str = "affine", to_numpy: bool = True, r
     if not batched:
         cmap, stats, rse = cmap[0], [v[0] for v in stats], rse[0]
     return Consistency(cmap.cpu().numpy() if to_numpy else cmap, stats[0], stats[1], rse, stats[2])
+
+
+NOISE_POOLS = ("all", "item")                        # estimate_noise's ``pool``
+
+
+class Noise(namedtuple("Noise", "poisson gaussian gain saltpepper slope intercept alpha beta levels found table sigma margin")):
+    """What ``estimate_noise`` measured: the crappifier parameters ``poisson`` (the intensity ``i``), ``gaussian`` (the additive width in
+    grey levels), ``gain`` (grey levels) and ``saltpepper`` (percent, as the ``SaltPepper`` constructor takes it); the two fitted lines
+    ``var ~ slope v + intercept`` and ``mean ~ alpha v + beta`` they come from; ``levels``, how many grey levels the lines rest on, and
+    ``found``, whether there was one; the pooled int64 ``table`` [256, 5]; the RSF width ``sigma`` in HR pixels and the ``margin`` in LR
+    pixels the pair was compared inside.  Scalars for ``pool="all"`` (and for a pair without the batch axis), arrays [N] for ``"item"``."""
+    __slots__ = ()
+
+    def crappifier(self, scale=None, item=None):
+        """The measurement as a ``MultiCrappifier(..., clip=True)`` of the stages that are not zero, in the order ``Blur(sigma / scale)``,
+        ``Poisson(poisson, gain)``, ``AdditiveGaussian(gaussian)``, ``SaltPepper(saltpepper)``; an empty one where nothing was
+        measurable.  ``scale``: the pair's integer scale, needed when ``sigma > 0``: the RSF is measured in HR pixels before the reduction
+        and ``Blur`` acts on the LR tile, so the stage has the width ``sigma / scale`` -- the small-sigma approximation that blur and
+        reduction commute.  ``item``: which item of a ``pool="item"`` result.  Two uses::
+
+            noise = estimate_noise(lr, hr, rsf="fit")
+            dataset = ImageDataset(hr_path, crappifier=noise.crappifier(scale=4))      # train directly with what was measured
+            build = lambda i, g, s: MultiCrappifier(Poisson(i, g), AdditiveGaussian(s))
+            approximate_crappifier(build, space, pairs,                                # or start the search from it
+                                   opt_kwargs={"x0": [noise.poisson, noise.gain, noise.gaussian]})
+
+        (``bayes.gp_minimize`` and skopt both take ``x0``, in the order of the search's dimensions.)"""
+        from .crappifiers import AdditiveGaussian, Blur, MultiCrappifier, Poisson, SaltPepper
+        if np.ndim(self.poisson):
+            if isinstance(item, bool) or not isinstance(item, (int, np.integer)) or not 0 <= item < len(self.poisson):
+                raise ValueError(f"crappifier needs item, 0 .. {len(self.poisson) - 1}, for a result of pool=\"item\". Given {item!r}.")
+            pick = lambda v: v[item].item()                       # noqa: E731
+        elif item is not None:
+            raise ValueError(f"item is for a result of pool=\"item\"; this one has scalars. Given {item!r}.")
+        else:
+            pick = lambda v: v                                   # noqa: E731
+        poisson, gaussian, gain, saltpepper, sigma = (float(pick(v)) for v in (self.poisson, self.gaussian, self.gain, self.saltpepper, self.sigma))
+        stages = []
+        if sigma > 0:
+            if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or not 1 <= scale <= 16:
+                raise ValueError(f"crappifier needs the pair's scale, an int from 1 to 16, to turn sigma={sigma} HR pixels into LR pixels. "
+                                 f"Given {scale!r}.")
+            stages.append(Blur(sigma / int(scale)))
+        if poisson > 0 or gain != 0:
+            stages.append(Poisson(poisson, gain))
+        if gaussian > 0:
+            stages.append(AdditiveGaussian(gaussian))
+        if saltpepper > 0:
+            stages.append(SaltPepper(saltpepper))
+        return MultiCrappifier(*stages, clip=True)
+
+
+def _noise_fit(table, min_count, guard):
+    """``(poisson, gaussian, gain, saltpepper, slope, intercept, alpha, beta, levels, found)`` from one level table (``[256][5]`` ints:
+    ``n, sum L, sum L^2, n0, n255`` of every level of ``D``), in exactly the expressions of include/pssr_mi355.h.  The moments of a level
+    are quotients of Python ints (exact before the one division); the two lines are fitted in floats, centred."""
+    rows = [[int(x) for x in row] for row in table]
+
+    def share(levels, col):
+        den = sum(rows[v][0] for v in levels)
+        return (sum(rows[v][col] for v in levels) / den if den else 0.0), den
+
+    (pepper, bright), (salt, dark) = share(range(128, 256), 3), share(range(128), 4)
+    amount = pepper + salt if bright and dark else 2.0 * (pepper + salt)
+    used = []                                            # (v, n', mean, var)
+    for v, (n, s1, s2, n0, n255) in enumerate(rows):
+        k, s1, s2 = n - n0 - n255, s1 - 255 * n255, s2 - 255 * 255 * n255
+        if k < max(min_count, 2):
+            continue
+        mean, var = s1 / k, (k * s2 - s1 * s1) / (k * (k - 1))
+        reach = guard * math.sqrt(var)
+        if mean - reach > 0 and mean + reach < 255:
+            used.append((float(v), k, mean, var))
+    if not used:
+        return 0.0, 0.0, 0.0, 100.0 * amount, 0.0, 0.0, 0.0, 0.0, 0, False
+    total = sum(k for _, k, _, _ in used)
+    vbar = sum(k * v for v, k, _, _ in used) / total
+    mbar = sum(k * mean for _, k, mean, _ in used) / total
+    qbar = sum(k * var for _, k, _, var in used) / total
+    gain = sum(k * (mean - v) for v, k, mean, _ in used) / total
+    if len(used) < 2:
+        slope, intercept, alpha, beta = 0.0, qbar, 1.0, gain
+    else:
+        svv = sum(k * (v - vbar) * (v - vbar) for v, k, _, _ in used)
+        slope = sum(k * (v - vbar) * (var - qbar) for v, k, _, var in used) / svv
+        alpha = sum(k * (v - vbar) * (mean - mbar) for v, k, mean, _ in used) / svv
+        intercept, beta = qbar - slope * vbar, mbar - alpha * vbar
+    return math.sqrt(max(slope, 0.0)), math.sqrt(max(intercept, 0.0)), gain, 100.0 * amount, slope, intercept, alpha, beta, len(used), True
+
+
+def estimate_noise(lr, hr, *, rsf=None, pool: str = "all", min_count: int = 32, guard: float = 4.0, to_numpy: bool = True):
+    r"""Measures the noise model between a sharp image and a measured one, in the terms of this package's own crappifiers: what
+    ``approximate_crappifier`` searches for, read off the pair directly.  ``lr``: uint8 array or device tensor [N, m, h, w]; ``hr``: uint8
+    [N, C, s*h, s*w], ``s`` an integer in 1 .. 16 (or both 3-D, without the batch axis) -- a real HR / LR pair (``register_pairs``
+    first).  Plane ``j`` meets frame ``j`` of the ``C`` centre frames of ``lr`` (``_slice_center``).  With ``D`` the reduced HR image and
+    ``L = clip8(rint(D (1 - i) + i Poisson(D) + g + N(0, sigma_n)))``, on every grey level ``v`` far from the clipping ends
+    ``E[L | D = v] = v + g`` and ``Var[L | D = v] = i**2 v + sigma_n**2``: a photon-transfer curve binned by the signal the pair already
+    contains.  The slope of the variance against the level gives ``poisson``, its intercept ``gaussian``, the mean residual ``gain``, and
+    pixels at exactly 0 on bright levels or 255 on dark ones give ``saltpepper``.  The 1/12 that rounding to integers adds to every
+    variance is not taken off the intercept.  include/pssr_mi355.h has the definitions.
+
+    * ``rsf`` (``None``: ``D = bilinear_down_u8(hr)``, margin 0): ``"fit"``, a sigma in HR pixels or one per item, as in
+      ``consistency_map(rsf=...)`` -- ``D`` is then the blurred reduction of that width and both sides lose the search's margin ``m``;
+    * ``pool``: ``"all"``, one microscope: every plane of every item adds its table (the default: one tile rarely fills enough levels);
+      ``"item"``: the planes of an item add theirs;
+    * ``min_count`` (>= 2) and ``guard`` (> 0): a level is used when it keeps ``min_count`` unsaturated pixels and its mean stays
+      ``guard`` standard deviations inside (0, 255).
+
+    One table launch for the batch (``pssr_level_moments_u8``: exact integers), one copy to the host, the fit in Python
+    (``_noise_fit``).  Returns ``Noise(poisson, gaussian, gain, saltpepper, slope, intercept, alpha, beta, levels, found, table, sigma,
+    margin)``; ``Noise.crappifier`` turns it into a ``MultiCrappifier``.  ``sigma`` is the RSF width used (``pool="all"``: the mean of the
+    items').  ``found = False`` (no level could be used; every parameter but ``saltpepper`` is 0) emits a ``UserWarning`` naming the
+    items, and so does ``|alpha - 1| > 0.1``: the crappifier family has no intensity scale, so ``gain`` then means little.
+    ``to_numpy=False`` leaves ``table`` on the device."""
+    import warnings
+    if pool not in NOISE_POOLS:
+        raise ValueError(f"pool must be one of {NOISE_POOLS}. Given {pool!r}.")
+    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or min_count < 2:
+        raise ValueError(f"min_count must be an int of at least 2. Given {min_count!r}.")
+    if isinstance(guard, bool) or not isinstance(guard, (int, float, np.integer, np.floating)) or not guard > 0 or not math.isfinite(guard):
+        raise ValueError(f"guard must be a finite positive number. Given {guard!r}.")
+    if rsf is None:
+        hr, lr, batched, _, dev = _u8_image_pair("estimate_noise", hr, lr, ("hr", "lr"), ("An HR item of {} planes", "an LR item of {} frames"))
+        (n_img, c), (h, w) = hr.shape[:2], lr.shape[-2:]
+        if not (hr.is_cuda or lr.is_cuda or torch.cuda.is_available()):
+            raise RuntimeError("pssr2_amd.util.estimate_noise needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
+        from .data import _slice_center
+        lc = _slice_center(lr.to(dev), c).contiguous()
+        d = ops.bilinear_down_u8(hr.to(dev).contiguous(), h, w)
+        m, sigma = 0, [0.0] * n_img
+    else:
+        d, lc, _, _, sig, per_item, batched, _, m = _rsf_reduced("estimate_noise", lr, hr, rsf)
+        n_img, c = d.shape[:2]
+        sigma = [sig[k] for k in per_item]
+    table = ops.level_moments_u8(d.reshape(n_img * c, -1), lc.reshape(n_img * c, -1)).view(n_img, c, 256, ops.LEVEL_MOMENTS)
+    table = table.sum(dim=(0, 1)) if pool == "all" else table.sum(dim=1)
+    host = table.cpu()
+    fits = [_noise_fit(t, int(min_count), float(guard)) for t in (host[None] if pool == "all" else host).tolist()]
+    whom = "the pooled batch" if pool == "all" else "item(s) {}"
+    missing = [i for i, f in enumerate(fits) if not f[9]]
+    if missing:
+        warnings.warn(f"estimate_noise: no grey level of {whom.format(missing)} keeps {min_count} pixels {guard} standard deviations inside "
+                      "(0, 255); nothing but saltpepper could be measured", UserWarning, stacklevel=2)
+    scaled = [i for i, f in enumerate(fits) if f[9] and abs(f[6] - 1.0) > 0.1]
+    if scaled:
+        warnings.warn(f"estimate_noise: the mean of lr follows hr with a slope of {[fits[i][6] for i in scaled]} for {whom.format(scaled)}; "
+                      "the crappifiers have no intensity scale, so gain means little here", UserWarning, stacklevel=2)
+    if not to_numpy:
+        host = table
+    else:
+        host = host.numpy()
+    if pool == "all" or not batched:
+        return Noise(*fits[0], host if pool == "all" else host[0], float(sum(sigma) / len(sigma)), m)
+    cols = list(zip(*fits))
+    fields = [np.array(col, dtype=np.float64) for col in cols[:8]] + [np.array(cols[8], dtype=np.int64), np.array(cols[9], dtype=bool)]
+    return Noise(*fields, host, np.array(sigma, dtype=np.float64), m)
 
 
 Registration = namedtuple("Registration", "hr lr shift score margin")
