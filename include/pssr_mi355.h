@@ -951,6 +951,53 @@ int64_t pssr_decorr_workspace_bytes(int planes, int H, int W, int n);
 int pssr_decorr_rings_u8(const uint8_t* a, const float* ct, const float* st, double* sums, int planes, int H, int W, int n, void* workspace,
                          int64_t workspace_bytes, pssr_stream_t stream);
 
+/* Directional resolution: sectorial FRC and decorrelation analysis (pssr2_amd.util.frc_sectors, decorr_sectors; csrc/frc.hip).  A ring
+ * pools every direction, and a point-scanning microscope is not isotropic: its fast axis (along a line) and its slow axis (line to line)
+ * differ in bandwidth.  Here every ring is cut into S sectors of the direction of the frequency vector, 1 <= S <= 16, and the sums of FRC
+ * (three) and of decorrelation analysis (two) are kept per (ring, sector) cell.  Blocks, the centred grid, windows, tables, the transform,
+ * the ring index, the doubling of the columns 0 < kx < n / 2 and the float32 / float64 split are exactly those of pssr_frc_rings_u8 and
+ * pssr_decorr_rings_u8 above; only the cell that a coefficient's products are added to differs.
+ *   S1. Boundary vectors (the caller's contract, made once on the host, int32 [S] each; pssr2_amd.ops.frc_sector_bounds makes them; the
+ *       kernels evaluate no sine).  For j = 0 .. S - 1: beta_j = (j + 1/2) pi / S, bx[j] = rint(2^20 cos beta_j),
+ *       by[j] = rint(2^20 sin beta_j).
+ *   S2. Sector of a coefficient, exact in integers like the ring index.  A kept coefficient is (ky, kx) with kx <= n / 2 and
+ *       fy = ky if ky <= n / 2 else ky - n.  Its upper-half-plane representative is (gx, gy) = (kx, fy) if fy >= 0, else (-kx, -fy).
+ *       sector = #{ j : bx[j] gy - by[j] gx >= 0 } mod S; |g| <= 512, so a product stays below 2^30.  A coefficient with kx > n / 2 has the
+ *       sector of its Hermitian mirror ((n - ky) mod n, n - kx), so doubling the columns 0 < kx < n / 2 stays valid sector by sector.
+ *       Sector s is centred on the direction s pi / S of the frequency vector: sector 0 holds frequencies along x (detail along a scan
+ *       line), and for even S sector S / 2 holds frequencies along y.  Ties: the origin falls into sector 0 (all S products are 0, and
+ *       S mod S = 0); at S = 2 the diagonal gy = gx goes to sector 1 and gy = -gx to sector 0.  At S = 1 every coefficient is in sector 0.
+ *   S3. Sums.  The three sums of step 4 of FRC, or the two of step 2 of decorrelation analysis, per plane, block, ring and sector, float64:
+ *       [planes][nby nbx][R + 1][S][3] and [planes][nby nbx][R + 1][S][2].  Every cell is one float64 chain: the rows of a 64 x 64 tile of
+ *       the spectrum in row order and kx order within a row, then the tiles in tile order -- so two calls give equal bits, and S = 1 gives
+ *       exactly the bits of pssr_frc_rings_u8 and pssr_decorr_rings_u8.
+ *   S4. Populations (host).  pop[r][s] = the number of coefficients of the full spectrum (kx in [0, n), the mirror rule of S2) in the cell;
+ *       pssr2_amd.ops.frc_sector_pop.  Rings >= 1 have empty cells once S is large against the ring's few coefficients (6 cells at S = 8,
+ *       32 - 33 at S = 16).
+ *   S5. FRC per sector (host, pssr2_amd.util._frc_resolve_sector): step 5 of FRC on the sector's sums, with a rule for empty cells.  With
+ *       smooth = k the cell (r, s), r >= 1, pools the sums and the populations of the cells (max(1, r - k) .. min(R, r + k), s).  A cell
+ *       whose pooled population is 0 has the curve value NaN and is skipped: the crossing search walks the populated rings r >= 1 of the
+ *       sector in ascending order, and at the first one below the threshold, with r_prev the populated ring before it (ring 0 counts) and
+ *       c the curve, r* = r_prev + (c[r_prev] - t) / (c[r_prev] - c[r]) (r - r_prev); r* = 1 where ring 0 lies below the threshold too, or where
+ *       no populated ring comes before (ring 0, the origin alone, is populated in sector 0 only).  No crossing: resolution = 2 pixel_size,
+ *       crossed = false.
+ *   S6. Decorrelation analysis per sector (host): steps 3 - 7 on the sector's two sums with M(r) = B sum_{rho = 1 .. r} pop[rho][s].
+ *       Empty cells add nothing to either sum and need no rule.
+ * pssr_frc_sectors_u8, pssr_decorr_sectors_u8: the row pass of the unsectored call, and a column pass whose reduction bins by (ring,
+ *   sector): the thread that owns ring r walks the ring's run of each row of the tile as before and follows the sector with a pointer into
+ *   the boundary vectors (the vectors with a non-negative product are a prefix of the list); the cell's chain continues in the thread's own
+ *   slot of the tile's partial row, [R + 1][S][3 or 2] float64.  No atomics, no fence.  Partial rows are S times those of the unsectored
+ *   call, and the chunk of blocks shrinks so that a chunk stays inside about 256 MB.
+ * Both validate on the host before anything is launched (the checks of the unsectored calls; S outside 1 .. 16; null bx or by;
+ * workspace_bytes below the _workspace_bytes figure): PSSR_ERR_ARG with a message.  The _workspace_bytes functions return 0 for arguments
+ * that the entry point rejects. */
+int64_t pssr_frc_sectors_workspace_bytes(int planes, int H, int W, int n, int S);
+int pssr_frc_sectors_u8(const uint8_t* a, const uint8_t* b, const float* ct, const float* st, const int32_t* bx, const int32_t* by, double* sums,
+                        int planes, int H, int W, int n, int S, void* workspace, int64_t workspace_bytes, pssr_stream_t stream);
+int64_t pssr_decorr_sectors_workspace_bytes(int planes, int H, int W, int n, int S);
+int pssr_decorr_sectors_u8(const uint8_t* a, const float* ct, const float* st, const int32_t* bx, const int32_t* by, double* sums, int planes,
+                           int H, int W, int n, int S, void* workspace, int64_t workspace_bytes, pssr_stream_t stream);
+
 /* The noise model of a pair, measured: level-conditional moments (pssr2_amd.util.estimate_noise; csrc/levels.hip).  Let D be the reduced
  * (and, if wanted, RSF-blurred) HR image and L = clip8(rint(D (1 - i) + i Poisson(D) + g + N(0, sigma_n))), the crappifier family of this
  * package.  On every grey level v far from the clipping ends E[L | D = v] = v + g and Var[L | D = v] = i^2 v + sigma_n^2: a

@@ -58,6 +58,9 @@ def __getattr__(name):
     if name in ("decorr",):
         from .util import decorr
         return decorr
+    if name in ("frc_sectors", "decorr_sectors"):
+        from . import util
+        return getattr(util, name)
     if name in ("estimate_rsf",):
         from .util import estimate_rsf
         return estimate_rsf

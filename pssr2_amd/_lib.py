@@ -157,6 +157,13 @@ def lib():
         _lib.pssr_decorr_workspace_bytes.restype = c_i64
         _lib.pssr_decorr_workspace_bytes.argtypes = [c_int] * 4
         _lib.pssr_decorr_rings_u8.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_i64, c_void_p]
+        # sectorial sums of both (csrc/frc.hip): ..., bx, by, sums, planes, H, W, n, S, workspace, workspace_bytes, stream
+        _lib.pssr_frc_sectors_workspace_bytes.restype = c_i64
+        _lib.pssr_frc_sectors_workspace_bytes.argtypes = [c_int] * 5
+        _lib.pssr_frc_sectors_u8.argtypes = [c_void_p] * 7 + [c_int] * 5 + [c_void_p, c_i64, c_void_p]
+        _lib.pssr_decorr_sectors_workspace_bytes.restype = c_i64
+        _lib.pssr_decorr_sectors_workspace_bytes.argtypes = [c_int] * 5
+        _lib.pssr_decorr_sectors_u8.argtypes = [c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_i64, c_void_p]
         # level-conditional moments of a pair (csrc/levels.hip)
         _lib.pssr_level_moments_workspace_bytes.restype = c_i64
         _lib.pssr_level_moments_workspace_bytes.argtypes = [c_int, c_i64]

@@ -30,6 +30,16 @@
 // another epilogue: |F|^2 and |F| = sqrtf(|F|^2) of every coefficient in place of the three products, two sums per ring.  In front of
 // it frc_block_means_kernel, one workgroup per block: the integer sum of the block's bytes (a fixed tree in LDS, exact in any order)
 // and m = float(S / n^2), the quotient in double; the row pass stages float(a) - m, zeros past the block as before.
+//
+// Sectorial sums (pssr2_amd.util.frc_sectors / decorr_sectors; "Directional resolution" in include/pssr_mi355.h): the same two passes, and a
+// column pass whose epilogue (SECT) bins each coefficient by (ring, sector), S <= 16 sectors of the direction of the frequency vector.
+// The sector is the count c of the caller's S integer boundary vectors b_j (ascending in angle, strictly inside the upper half plane) with
+// b_j x g >= 0 for the upper-half-plane representative g of the coefficient, taken mod S: the counted j are a prefix 0 .. c - 1, so thread r,
+// which walks ring r's runs as before, keeps c as a pointer and moves it down while b_(c-1) x g < 0 and up while b_c x g >= 0 (a step or
+// two per coefficient: neighbours in a ring are neighbours in angle).  The tile's partial row is [R + 1][S][NS]; a cell's chain lives in
+// its slot there, which only thread r touches: the thread zeroes its S slots, keeps the sums of the sector it is in in registers, and on
+// a change of sector stores them and loads the new cell's, so every cell stays one float64 chain in row order and kx order and S = 1
+// gives the bits of the unsectored kernel.  The boundary vectors sit in 128 bytes of LDS beside the products.
 #include "common.h"
 
 namespace {
@@ -41,6 +51,7 @@ constexpr int FRC_APITCH = FRC_KT + 1;          // words per staged image row: t
 constexpr long FRC_WS_BYTES = 256L << 20;       // workspace a chunk of blocks aims to stay below
 constexpr int FRC_MAX_CHUNK = 32768;            // grid.y
 constexpr long FRC_MAX_BLOCKS = 1L << 24;       // blocks per call
+constexpr int FRC_MAX_SECTORS = 16;
 
 struct FrcGeom {
     int n, K, R, nby, nbx, oy, ox, ty, tk, tiles;     // ty, tk: 64-tiles along y (or ky) and along kx; both passes have ty * tk tiles
@@ -53,8 +64,9 @@ inline bool frc_args_ok(int planes, int H, int W, int n) {
     return (long)planes * (H / n) * (W / n) <= FRC_MAX_BLOCKS;
 }
 
-// ni: images per block (2: the pair of FRC; 1: decorrelation analysis, which keeps a float mean per block beside T)
-inline FrcGeom frc_geom(int planes, int H, int W, int n, int ni) {
+// ni: images per block (2: the pair of FRC; 1: decorrelation analysis, which keeps a float mean per block beside T); S: sectors per ring
+// of the partial rows (1: the unsectored calls)
+inline FrcGeom frc_geom(int planes, int H, int W, int n, int ni, int S = 1) {
     FrcGeom g;
     g.n = n; g.K = n / 2 + 1; g.R = n / 2;
     g.nby = H / n; g.nbx = W / n;
@@ -62,7 +74,7 @@ inline FrcGeom frc_geom(int planes, int H, int W, int n, int ni) {
     g.ty = cdiv(n, FRC_TILE); g.tk = cdiv(g.K, FRC_TILE);
     g.tiles = g.ty * g.tk;
     g.nblocks = (long)planes * g.nby * g.nbx;
-    g.per_block_bytes = (long)g.tiles * (g.R + 1) * (ni + 1) * (long)sizeof(double) + 2L * ni * n * g.K * (long)sizeof(float) +
+    g.per_block_bytes = (long)g.tiles * (g.R + 1) * S * (ni + 1) * (long)sizeof(double) + 2L * ni * n * g.K * (long)sizeof(float) +
                         (ni == 1 ? (long)sizeof(float) : 0L);
     long chunk = FRC_WS_BYTES / g.per_block_bytes;
     if (chunk < 1) chunk = 1;
@@ -183,12 +195,15 @@ __global__ __launch_bounds__(256) void frc_rows_kernel(const uint8_t* __restrict
     }
 }
 
-template <int NI>
+// SECT: the sectorial epilogue, partial rows [R + 1][S][NS], bx, by [S] the boundary vectors (S, bx, by unused without it)
+template <int NI, bool SECT = false>
 __global__ __launch_bounds__(256) void frc_cols_kernel(const float* __restrict__ T, const float* __restrict__ ct, const float* __restrict__ st,
-                                                       double* __restrict__ partial, int n, int tk) {
+                                                       double* __restrict__ partial, int n, int tk, int S, const int* __restrict__ bx,
+                                                       const int* __restrict__ by) {
     // stages: the tables' pieces [2][32][64] and T's 2 NI planes [32][64]; afterwards the NS = NI + 1 values per coefficient [NS][64][64]
     constexpr int NS = NI + 1;
     __shared__ float lds[(2 + 2 * NI) * FRC_KT * FRC_TILE];
+    __shared__ int lb[SECT ? 2 * FRC_MAX_SECTORS : 1];           // bx, then by
     static_assert((2 + 2 * NI) * FRC_KT * FRC_TILE >= NS * FRC_TILE * FRC_TILE, "the products take the place of the stages");
     const int K = n / 2 + 1, R = n / 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wy = wave >> 1, wx = wave & 1;
@@ -246,11 +261,56 @@ __global__ __launch_bounds__(256) void frc_cols_kernel(const float* __restrict__
             }
         }
     }
+    if constexpr (SECT) {
+        if (tid < S) {
+            lb[tid] = bx[tid];
+            lb[FRC_MAX_SECTORS + tid] = by[tid];
+        }
+    }
     __syncthreads();
     // ring r of the tile: per spectrum row the run of kx with floor(sqrt(fy^2 + kx^2) + 1/2) == r, that is
     // r^2 - r + 1 <= fy^2 + kx^2 <= r^2 + r (ring 0: the origin alone), cut to the tile's valid columns
-    double* const prow = partial + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (R + 1) * NS;
     const int klast = k0 + FRC_TILE - 1 < K - 1 ? k0 + FRC_TILE - 1 : K - 1;
+    if constexpr (SECT) {
+        double* const prow = partial + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (R + 1) * S * NS;
+        for (int r = tid; r <= R; r += 256) {
+            double* const cells = prow + (long)r * S * NS;     // this thread's alone
+            for (int i = 0; i < S * NS; ++i) cells[i] = 0.;
+            double sum[NS] = {};
+            int c = 0, cur = -1;                                // boundaries below the direction; the sector whose sums are in registers
+            for (int row = 0; row < FRC_TILE && ky0 + row < n; ++row) {
+                const int ky = ky0 + row, fy = ky <= R ? ky : ky - n, f2 = fy * fy;
+                const int hi2 = r * r + r - f2, lo2 = (r > 0 ? r * r - r + 1 : 0) - f2;
+                if (hi2 < 0) continue;
+                int lo = lo2 <= 0 ? 0 : isqrt_i(lo2 - 1) + 1, hi = isqrt_i(hi2);
+                if (lo < k0) lo = k0;
+                if (hi > klast) hi = klast;
+                const int gy = fy >= 0 ? fy : -fy;
+                for (int kx = lo; kx <= hi; ++kx) {
+                    const int gx = fy >= 0 ? kx : -kx;
+                    while (c > 0 && lb[c - 1] * gy - lb[FRC_MAX_SECTORS + c - 1] * gx < 0) --c;
+                    while (c < S && lb[c] * gy - lb[FRC_MAX_SECTORS + c] * gx >= 0) ++c;
+                    const int sector = c == S ? 0 : c;
+                    if (sector != cur) {
+                        if (cur >= 0)
+#pragma unroll
+                            for (int q = 0; q < NS; ++q) cells[cur * NS + q] = sum[q];
+#pragma unroll
+                        for (int q = 0; q < NS; ++q) sum[q] = cells[sector * NS + q];
+                        cur = sector;
+                    }
+                    const int at = row * FRC_TILE + kx - k0;
+#pragma unroll
+                    for (int q = 0; q < NS; ++q) sum[q] += (double)lds[q * FRC_TILE * FRC_TILE + at];
+                }
+            }
+            if (cur >= 0)
+#pragma unroll
+                for (int q = 0; q < NS; ++q) cells[cur * NS + q] = sum[q];
+        }
+        return;
+    }
+    double* const prow = partial + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (R + 1) * NS;
     for (int r = tid; r <= R; r += 256) {
         double sum[NS] = {};
         for (int row = 0; row < FRC_TILE && ky0 + row < n; ++row) {
@@ -283,8 +343,8 @@ __global__ __launch_bounds__(256) void frc_fold_kernel(const double* __restrict_
 // The launches of one call: per chunk of blocks (the means,) the row pass, the column pass and the fold.
 template <int NI>
 int frc_launch(const uint8_t* a, const uint8_t* b, const float* ct, const float* st, double* sums, int H, int W, const FrcGeom& g, void* workspace,
-               pssr_stream_t stream) {
-    const int k = (g.R + 1) * (NI + 1);
+               pssr_stream_t stream, int S = 0, const int* bx = nullptr, const int* by = nullptr) {        // S = 0: the unsectored column pass
+    const int k = (g.R + 1) * (S ? S : 1) * (NI + 1);
     double* const partial = (double*)workspace;
     float* const T = (float*)((char*)workspace + (long)g.chunk * g.tiles * k * (long)sizeof(double));
     float* const mean = T + (long)g.chunk * 2 * NI * g.n * g.K;          // NI == 1 only
@@ -298,7 +358,12 @@ int frc_launch(const uint8_t* a, const uint8_t* b, const float* ct, const float*
         hipLaunchKernelGGL(frc_rows_kernel<NI>, dim3(g.tiles, count), dim3(256), 0, s, a, b, (const float*)mean, ct, st, T, block0, H, W, g.n, g.nby,
                            g.nbx, g.oy, g.ox, g.tk);
         PSSR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(frc_cols_kernel<NI>, dim3(g.tiles, count), dim3(256), 0, s, (const float*)T, ct, st, partial, g.n, g.tk);
+        if (S)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(frc_cols_kernel<NI, true>), dim3(g.tiles, count), dim3(256), 0, s, (const float*)T, ct, st, partial, g.n,
+                               g.tk, S, bx, by);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(frc_cols_kernel<NI, false>), dim3(g.tiles, count), dim3(256), 0, s, (const float*)T, ct, st, partial, g.n,
+                               g.tk, 0, (const int*)nullptr, (const int*)nullptr);
         PSSR_LAUNCH_CHECK();
         const long values = (long)count * k;
         hipLaunchKernelGGL(frc_fold_kernel, dim3(grid1d(values, 4096)), dim3(256), 0, s, (const double*)partial, sums + block0 * k, values, g.tiles, k);
@@ -344,4 +409,55 @@ extern "C" int pssr_decorr_rings_u8(const uint8_t* a, const float* ct, const flo
     PSSR_CHECK(workspace_bytes >= (int64_t)g.chunk * g.per_block_bytes, PSSR_ERR_ARG, "decorr_rings_u8: a workspace of %ld bytes is short of the %ld needed",
                (long)workspace_bytes, (long)((int64_t)g.chunk * g.per_block_bytes));
     return frc_launch<1>(a, nullptr, ct, st, sums, H, W, g, workspace, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- sectorial sums
+namespace {
+
+// The checks that the four sector entry points share; 0 or the error code.
+int frc_sectors_check(const char* who, int planes, int H, int W, int n, int S) {
+    PSSR_CHECK(planes > 0 && H > 0 && W > 0, PSSR_ERR_ARG, "%s: planes, H and W must be positive (%d, %d, %d)", who, planes, H, W);
+    PSSR_CHECK(n >= FRC_MIN_N && n <= FRC_MAX_N && n % 2 == 0, PSSR_ERR_ARG, "%s: the block side must be even and in %d .. %d, given %d", who,
+               FRC_MIN_N, FRC_MAX_N, n);
+    PSSR_CHECK(n <= H && n <= W, PSSR_ERR_ARG, "%s: a block of %d does not fit a %d x %d plane", who, n, H, W);
+    PSSR_CHECK(frc_args_ok(planes, H, W, n), PSSR_ERR_ARG, "%s: %ld blocks in all (at most 2^24 per call)", who, (long)planes * (H / n) * (W / n));
+    PSSR_CHECK(S >= 1 && S <= FRC_MAX_SECTORS, PSSR_ERR_ARG, "%s: the sector count must be in 1 .. %d, given %d", who, FRC_MAX_SECTORS, S);
+    return PSSR_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t pssr_frc_sectors_workspace_bytes(int planes, int H, int W, int n, int S) {
+    if (!frc_args_ok(planes, H, W, n) || S < 1 || S > FRC_MAX_SECTORS) return 0;
+    const FrcGeom g = frc_geom(planes, H, W, n, 2, S);
+    return (int64_t)g.chunk * g.per_block_bytes;
+}
+
+extern "C" int pssr_frc_sectors_u8(const uint8_t* a, const uint8_t* b, const float* ct, const float* st, const int32_t* bx, const int32_t* by,
+                                   double* sums, int planes, int H, int W, int n, int S, void* workspace, int64_t workspace_bytes,
+                                   pssr_stream_t stream) {
+    PSSR_CHECK(a && b && ct && st && sums && workspace, PSSR_ERR_ARG, "frc_sectors_u8: null pointer");
+    PSSR_CHECK(bx && by, PSSR_ERR_ARG, "frc_sectors_u8: null boundary table");
+    if (const int e = frc_sectors_check("frc_sectors_u8", planes, H, W, n, S)) return e;
+    const FrcGeom g = frc_geom(planes, H, W, n, 2, S);
+    PSSR_CHECK(workspace_bytes >= (int64_t)g.chunk * g.per_block_bytes, PSSR_ERR_ARG, "frc_sectors_u8: a workspace of %ld bytes is short of the %ld needed",
+               (long)workspace_bytes, (long)((int64_t)g.chunk * g.per_block_bytes));
+    return frc_launch<2>(a, b, ct, st, sums, H, W, g, workspace, stream, S, bx, by);
+}
+
+extern "C" int64_t pssr_decorr_sectors_workspace_bytes(int planes, int H, int W, int n, int S) {
+    if (!frc_args_ok(planes, H, W, n) || S < 1 || S > FRC_MAX_SECTORS) return 0;
+    const FrcGeom g = frc_geom(planes, H, W, n, 1, S);
+    return (int64_t)g.chunk * g.per_block_bytes;
+}
+
+extern "C" int pssr_decorr_sectors_u8(const uint8_t* a, const float* ct, const float* st, const int32_t* bx, const int32_t* by, double* sums,
+                                      int planes, int H, int W, int n, int S, void* workspace, int64_t workspace_bytes, pssr_stream_t stream) {
+    PSSR_CHECK(a && ct && st && sums && workspace, PSSR_ERR_ARG, "decorr_sectors_u8: null pointer");
+    PSSR_CHECK(bx && by, PSSR_ERR_ARG, "decorr_sectors_u8: null boundary table");
+    if (const int e = frc_sectors_check("decorr_sectors_u8", planes, H, W, n, S)) return e;
+    const FrcGeom g = frc_geom(planes, H, W, n, 1, S);
+    PSSR_CHECK(workspace_bytes >= (int64_t)g.chunk * g.per_block_bytes, PSSR_ERR_ARG, "decorr_sectors_u8: a workspace of %ld bytes is short of the %ld needed",
+               (long)workspace_bytes, (long)((int64_t)g.chunk * g.per_block_bytes));
+    return frc_launch<1>(a, nullptr, ct, st, sums, H, W, g, workspace, stream, S, bx, by);
 }

@@ -1414,26 +1414,33 @@ def _frc_device_tables(n, window, device):
     return _FRC_DEVICE_TABLES[key]
 
 
+def _frc_sums_args(who, tensors, block, window):
+    """The argument checks that the ring-sum and sector-sum drivers share -> ``(contiguous tensors, H, W, planes, blocks per plane)``."""
+    first = tensors[0]
+    if not all(torch.is_tensor(t) and t.dtype == torch.uint8 and t.is_cuda for t in tensors) or first.dim() < 2 \
+            or any(t.shape != first.shape for t in tensors):
+        raise ValueError(f"{who} needs two uint8 device tensors of the same shape [..., H, W]" if len(tensors) == 2 else
+                         f"{who} needs a uint8 device tensor [..., H, W]")
+    _check_frc_block(who, block)
+    if window not in FRC_WINDOWS:
+        raise ValueError(f"window must be one of {FRC_WINDOWS}. Given {window!r}.")
+    H, W = first.shape[-2:]
+    if block > min(H, W):
+        raise ValueError(f"{who}: a block of {block} does not fit a {H}x{W} plane")
+    planes = first.numel() // (H * W)
+    nb = (H // block) * (W // block)
+    if planes < 1 or planes * nb > 1 << 24:
+        raise ValueError(f"{who}: {planes} planes of {nb} blocks (at least one plane, at most 2**24 blocks in all)")
+    return [t.contiguous() for t in tensors], H, W, planes, nb
+
+
 def frc_rings_u8(a, b, block, window="hann"):
     """uint8 device tensors ``a`` and ``b`` of the same shape [..., H, W], an even block side ``block`` in 16 .. 1024 (at most
     ``min(H, W)``) -> float64 device tensor [planes, nby * nbx, block // 2 + 1, 3]: per plane, per block of the centred grid of
     ``(H // block) x (W // block)`` blocks and per ring of spatial frequency the sums ``Re(Fa conj Fb), |Fa|**2, |Fb|**2`` over the
     windowed spectra of the two blocks.  Two matrix products per block on the f32-input MFMA and a fixed-order reduction: the same bits on
     every call."""
-    if not (torch.is_tensor(a) and torch.is_tensor(b)) or a.dtype != torch.uint8 or b.dtype != torch.uint8 or not (a.is_cuda and b.is_cuda) \
-            or a.dim() < 2 or a.shape != b.shape:
-        raise ValueError("frc_rings_u8 needs two uint8 device tensors of the same shape [..., H, W]")
-    _check_frc_block("frc_rings_u8", block)
-    if window not in FRC_WINDOWS:
-        raise ValueError(f"window must be one of {FRC_WINDOWS}. Given {window!r}.")
-    H, W = a.shape[-2:]
-    if block > min(H, W):
-        raise ValueError(f"frc_rings_u8: a block of {block} does not fit a {H}x{W} plane")
-    planes = a.numel() // (H * W)
-    nb = (H // block) * (W // block)
-    if planes < 1 or planes * nb > 1 << 24:
-        raise ValueError(f"frc_rings_u8: {planes} planes of {nb} blocks (at least one plane, at most 2**24 blocks in all)")
-    a, b = a.contiguous(), b.contiguous()
+    (a, b), H, W, planes, nb = _frc_sums_args("frc_rings_u8", (a, b), block, window)
     ct, st = _frc_device_tables(block, window, a.device)
     lib = L.lib()
     ws = torch.empty(lib.pssr_frc_workspace_bytes(planes, H, W, block), dtype=torch.uint8, device=a.device)
@@ -1449,19 +1456,7 @@ def decorr_rings_u8(a, block, window="hann"):
     of spatial frequency the sums ``|F|`` and ``|F|**2`` over the windowed spectrum of the block minus its own mean (steps 1 - 2 of
     "decorrelation analysis" in include/pssr_mi355.h).  The tables are ``frc_tables``' and so is their device cache; the same bits on every
     call."""
-    if not torch.is_tensor(a) or a.dtype != torch.uint8 or not a.is_cuda or a.dim() < 2:
-        raise ValueError("decorr_rings_u8 needs a uint8 device tensor [..., H, W]")
-    _check_frc_block("decorr_rings_u8", block)
-    if window not in FRC_WINDOWS:
-        raise ValueError(f"window must be one of {FRC_WINDOWS}. Given {window!r}.")
-    H, W = a.shape[-2:]
-    if block > min(H, W):
-        raise ValueError(f"decorr_rings_u8: a block of {block} does not fit a {H}x{W} plane")
-    planes = a.numel() // (H * W)
-    nb = (H // block) * (W // block)
-    if planes < 1 or planes * nb > 1 << 24:
-        raise ValueError(f"decorr_rings_u8: {planes} planes of {nb} blocks (at least one plane, at most 2**24 blocks in all)")
-    a = a.contiguous()
+    (a,), H, W, planes, nb = _frc_sums_args("decorr_rings_u8", (a,), block, window)
     ct, st = _frc_device_tables(block, window, a.device)
     lib = L.lib()
     nbytes = lib.pssr_decorr_workspace_bytes(planes, H, W, block)
@@ -1469,4 +1464,93 @@ def decorr_rings_u8(a, block, window="hann"):
     sums = torch.empty(planes, nb, block // 2 + 1, 2, dtype=torch.float64, device=a.device)
     L.check(lib.pssr_decorr_rings_u8(L.ptr(a), L.ptr(ct), L.ptr(st), L.ptr(sums), planes, H, W, block, L.ptr(ws), nbytes, L.stream_ptr()),
             "pssr_decorr_rings_u8")
+    return sums
+
+
+# Directional resolution: the sums per (ring, sector) cell ("Directional resolution" in include/pssr_mi355.h)
+FRC_MAX_SECTORS = 16
+
+_FRC_SECTOR_BOUNDS = {}              # S -> (bx, by) int32 numpy
+_FRC_DEVICE_BOUNDS = {}              # (S, device) -> their device copies
+_FRC_SECTOR_POP = {}                 # (n, S) -> int64 [n // 2 + 1, S]
+
+
+def _check_frc_sectors(who, sectors):
+    if isinstance(sectors, bool) or not isinstance(sectors, int) or not 1 <= sectors <= FRC_MAX_SECTORS:
+        raise ValueError(f"{who}: sectors must be an int in 1 .. {FRC_MAX_SECTORS}. Given {sectors!r}.")
+
+
+def frc_sector_bounds(S):
+    """The boundary vectors of step S1 of include/pssr_mi355.h -> ``(bx, by)``, int32 numpy [S]: ``rint(2**20 cos beta_j)`` and
+    ``rint(2**20 sin beta_j)``, ``beta_j = (j + 1/2) pi / S``; float64 on the host, rounded once."""
+    import numpy as np
+    _check_frc_sectors("frc_sector_bounds", S)
+    if S not in _FRC_SECTOR_BOUNDS:
+        beta = (np.arange(S, dtype=np.float64) + 0.5) * np.pi / S
+        _FRC_SECTOR_BOUNDS[S] = (np.rint(2.0 ** 20 * np.cos(beta)).astype(np.int32), np.rint(2.0 ** 20 * np.sin(beta)).astype(np.int32))
+    return _FRC_SECTOR_BOUNDS[S]
+
+
+def _frc_device_bounds(S, device):
+    key = (S, torch.device(device))
+    if key not in _FRC_DEVICE_BOUNDS:
+        _FRC_DEVICE_BOUNDS[key] = tuple(torch.from_numpy(t).to(device) for t in frc_sector_bounds(S))
+        torch.cuda.current_stream(key[1]).synchronize()        # as _frc_device_tables
+    return _FRC_DEVICE_BOUNDS[key]
+
+
+def frc_sector_pop(n, S):
+    """int64 numpy [n // 2 + 1, S]: the coefficients of the full n x n spectrum per (ring, sector) cell (steps S2 and S4 of
+    include/pssr_mi355.h; a coefficient with kx > n / 2 counts in the cell of its Hermitian mirror).  Host only."""
+    import numpy as np
+    _check_frc_block("frc_sector_pop", n)
+    _check_frc_sectors("frc_sector_pop", S)
+    if (n, S) not in _FRC_SECTOR_POP:
+        R = n // 2
+        ky, kx = np.meshgrid(np.arange(n, dtype=np.int64), np.arange(n, dtype=np.int64), indexing="ij")
+        mirror = kx > R
+        ky, kx = np.where(mirror, (n - ky) % n, ky), np.where(mirror, n - kx, kx)
+        fy = np.where(ky <= R, ky, ky - n)
+        q = fy * fy + kx * kx
+        r = np.floor(np.sqrt(q.astype(np.float64)) + 0.5).astype(np.int64)
+        r += (q > r * r + r).astype(np.int64) - ((r > 0) & (q < r * r - r + 1)).astype(np.int64)     # (isqrt(4 q) + 1) // 2 whatever the float root did
+        gx, gy = np.where(fy >= 0, kx, -kx), np.abs(fy)
+        bx, by = (t.astype(np.int64) for t in frc_sector_bounds(S))
+        sector = (bx[:, None, None] * gy - by[:, None, None] * gx >= 0).sum(axis=0) % S
+        keep = r <= R
+        _FRC_SECTOR_POP[n, S] = np.bincount((r * S + sector)[keep], minlength=(R + 1) * S).reshape(R + 1, S)
+    return _FRC_SECTOR_POP[n, S]
+
+
+def frc_sectors_u8(a, b, block, sectors, window="hann"):
+    """``frc_rings_u8`` per direction: -> float64 device tensor [planes, nby * nbx, block // 2 + 1, sectors, 3], the three sums of every
+    ring cut into ``sectors`` (1 .. 16) sectors of the direction of the frequency vector, sector ``s`` centred on ``s pi / sectors``
+    (0: along x).  The same transform; the reduction bins by (ring, sector) in one fixed order, and ``sectors=1`` gives the bits of
+    ``frc_rings_u8``."""
+    (a, b), H, W, planes, nb = _frc_sums_args("frc_sectors_u8", (a, b), block, window)
+    _check_frc_sectors("frc_sectors_u8", sectors)
+    ct, st = _frc_device_tables(block, window, a.device)
+    bx, by = _frc_device_bounds(sectors, a.device)
+    lib = L.lib()
+    nbytes = lib.pssr_frc_sectors_workspace_bytes(planes, H, W, block, sectors)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+    sums = torch.empty(planes, nb, block // 2 + 1, sectors, 3, dtype=torch.float64, device=a.device)
+    L.check(lib.pssr_frc_sectors_u8(L.ptr(a), L.ptr(b), L.ptr(ct), L.ptr(st), L.ptr(bx), L.ptr(by), L.ptr(sums), planes, H, W, block, sectors,
+                                    L.ptr(ws), nbytes, L.stream_ptr()), "pssr_frc_sectors_u8")
+    return sums
+
+
+def decorr_sectors_u8(a, block, sectors, window="hann"):
+    """``decorr_rings_u8`` per direction: -> float64 device tensor [planes, nby * nbx, block // 2 + 1, sectors, 2], ``sum |F|`` and
+    ``sum |F|**2`` per (ring, sector) cell, the sectors as in ``frc_sectors_u8``; ``sectors=1`` gives the bits of ``decorr_rings_u8``."""
+    (a,), H, W, planes, nb = _frc_sums_args("decorr_sectors_u8", (a,), block, window)
+    _check_frc_sectors("decorr_sectors_u8", sectors)
+    ct, st = _frc_device_tables(block, window, a.device)
+    bx, by = _frc_device_bounds(sectors, a.device)
+    lib = L.lib()
+    nbytes = lib.pssr_decorr_sectors_workspace_bytes(planes, H, W, block, sectors)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+    sums = torch.empty(planes, nb, block // 2 + 1, sectors, 2, dtype=torch.float64, device=a.device)
+    L.check(lib.pssr_decorr_sectors_u8(L.ptr(a), L.ptr(ct), L.ptr(st), L.ptr(bx), L.ptr(by), L.ptr(sums), planes, H, W, block, sectors, L.ptr(ws),
+                                       nbytes, L.stream_ptr()), "pssr_decorr_sectors_u8")
     return sums

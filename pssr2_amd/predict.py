@@ -498,7 +498,12 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
 
     ``"decorr"`` (not in the default tuple either) is the resolution of the prediction alone, in HR pixels: ``util.decorr`` with its defaults
     (one block per plane, Hann window, ten high-pass filters, the image's planes pooled) of the cropped uint8 prediction, before ``norm``.
-    Unlike ``"frc"`` it does not look at the ground truth: it measures the detail the prediction holds, not its agreement with anything."""
+    Unlike ``"frc"`` it does not look at the ground truth: it measures the detail the prediction holds, not its agreement with anything.
+
+    ``"frc_x"``, ``"frc_y"``, ``"decorr_x"`` and ``"decorr_y"`` (none in the default tuple) are the directional forms of those two:
+    ``util.frc_sectors`` and ``util.decorr_sectors`` with ``sectors=2`` and otherwise their defaults, on the same images; ``_x`` is sector 0,
+    the resolution of detail along a scan line, ``_y`` sector 1, the resolution from line to line.  One sums call per method and item,
+    however many of the four are named."""
     import math
     from .util import pixel_metric
     _check_ensemble(ensemble, device)
@@ -507,7 +512,8 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
     image_range = 255
     metrics = [metrics] if type(metrics) is str else list(metrics)
     out = {m: [] for m in metrics}
-    if ("frc" in out or "rsf" in out or "decorr" in out) and torch.device(device).type != "cuda":                   # as _check_ensemble: before model, dataset or device are touched
+    sectored = [m for m in ("frc", "decorr") if f"{m}_x" in out or f"{m}_y" in out]
+    if ("frc" in out or "rsf" in out or "decorr" in out or sectored) and torch.device(device).type != "cuda":                   # as _check_ensemble: before model, dataset or device are touched
         raise RuntimeError("pssr2_amd.predict runs on an MI355X (HIP) device only; there is no CPU fallback")
     model.to(device)
     model.eval()
@@ -535,6 +541,12 @@ def test_metrics(model: nn.Module, dataset: Dataset, device: str = "cpu", metric
             if "decorr" in out:
                 from .util import decorr
                 out["decorr"].extend(decorr(hat_dev).resolution.tolist())
+            for method in sectored:
+                from . import util
+                res = (util.frc_sectors(hat_dev, hr_dev) if method == "frc" else util.decorr_sectors(hat_dev)).resolution
+                for s, axis in enumerate("xy"):
+                    if f"{method}_{axis}" in out:
+                        out[f"{method}_{axis}"].extend(res[:, s].tolist())
             if "rsf" in out:
                 out["rsf"].extend(_score_items(lr, hat_dev, crop_res, hr_hat.shape[-1] // lr.shape[-1], fit, rsf=True).sigma.tolist())
             if norm:

@@ -784,6 +784,42 @@ def register_pairs(hr, lr, *, radius: int = 8, to_numpy: bool = True):
     return Registration(hr_out, lr_out, shift, score, m)
 
 
+def _spectral_inputs(who: str, named, block):
+    """The checks of the images and the block side that ``frc``, ``decorr`` and their sectorial forms share, in their order (``named``:
+    ``(name, image)`` pairs) -> ``(device tensors [N, C, H, W], batched, block, device)``."""
+    tensors = []
+    for name, t in named:
+        host = torch.is_tensor(t) and not t.is_cuda
+        if not torch.is_tensor(t):
+            t = torch.as_tensor(np.ascontiguousarray(t))
+        if t.dtype != torch.uint8:
+            raise TypeError(f"{who} takes uint8 images; {name} is {t.dtype}")
+        if host:
+            raise RuntimeError(f"pssr2_amd.util.{who} runs on an MI355X (HIP) device only; there is no CPU fallback")
+        tensors.append(t)
+    a = tensors[0]
+    if len(tensors) == 2:
+        if a.shape != tensors[1].shape or a.dim() not in (2, 3, 4):
+            raise ValueError("a and b must have the same shape, [images, planes, height, width] or one [planes, height, width] or [height, width] "
+                             f"pair. Shapes are {tuple(a.shape)} and {tuple(tensors[1].shape)} respectively.")
+    elif a.dim() not in (2, 3, 4):
+        raise ValueError(f"img must be [images, planes, height, width] or one [planes, height, width] or [height, width] image. The shape is {tuple(a.shape)}.")
+    batched = a.dim() == 4
+    tensors = [t.reshape((1,) * (4 - t.dim()) + tuple(t.shape)) for t in tensors]
+    n_img, c, H, W = tensors[0].shape
+    if min(n_img, c) < 1 or min(H, W) < ops.FRC_MIN_BLOCK:
+        raise ValueError(f"{who} needs at least one plane of at least {ops.FRC_MIN_BLOCK}x{ops.FRC_MIN_BLOCK} pixels. The shape is {tuple(tensors[0].shape)}.")
+    if block is None:
+        block = min(H, W, ops.FRC_MAX_BLOCK) // 2 * 2
+    elif isinstance(block, bool) or not isinstance(block, (int, np.integer)) or block % 2 or not ops.FRC_MIN_BLOCK <= block <= min(H, W, ops.FRC_MAX_BLOCK):
+        raise ValueError(f"block must be an even int from {ops.FRC_MIN_BLOCK} to {min(H, W, ops.FRC_MAX_BLOCK)} (the smaller side, at most "
+                         f"{ops.FRC_MAX_BLOCK}). Given {block!r}.")
+    if not (any(t.is_cuda for t in tensors) or torch.cuda.is_available()):
+        raise RuntimeError(f"pssr2_amd.util.{who} needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
+    dev = next((t.device for t in tensors if t.is_cuda), "cuda")
+    return [t.to(dev) for t in tensors], batched, int(block), dev
+
+
 FRC = namedtuple("FRC", "curve freq resolution crossed block")
 
 
@@ -837,35 +873,9 @@ def frc(a, b, *, block=None, window: str = "hann", threshold: float = 1 / 7, smo
         raise ValueError(f"smooth must be a non-negative int (rings pooled on either side). Given {smooth!r}.")
     if isinstance(pixel_size, bool) or not isinstance(pixel_size, (int, float, np.integer, np.floating)) or not pixel_size > 0:
         raise ValueError(f"pixel_size must be a positive number. Given {pixel_size!r}.")
-    tensors = []
-    for name, t in (("a", a), ("b", b)):
-        host = torch.is_tensor(t) and not t.is_cuda
-        if not torch.is_tensor(t):
-            t = torch.as_tensor(np.ascontiguousarray(t))
-        if t.dtype != torch.uint8:
-            raise TypeError(f"frc takes uint8 images; {name} is {t.dtype}")
-        if host:
-            raise RuntimeError("pssr2_amd.util.frc runs on an MI355X (HIP) device only; there is no CPU fallback")
-        tensors.append(t)
-    a, b = tensors
-    if a.shape != b.shape or a.dim() not in (2, 3, 4):
-        raise ValueError("a and b must have the same shape, [images, planes, height, width] or one [planes, height, width] or [height, width] "
-                         f"pair. Shapes are {tuple(a.shape)} and {tuple(b.shape)} respectively.")
-    batched = a.dim() == 4
-    a, b = a.reshape((1,) * (4 - a.dim()) + tuple(a.shape)), b.reshape((1,) * (4 - b.dim()) + tuple(b.shape))
-    n_img, c, H, W = a.shape
-    if min(n_img, c) < 1 or min(H, W) < ops.FRC_MIN_BLOCK:
-        raise ValueError(f"frc needs at least one plane of at least {ops.FRC_MIN_BLOCK}x{ops.FRC_MIN_BLOCK} pixels. The shape is {tuple(a.shape)}.")
-    if block is None:
-        block = min(H, W, ops.FRC_MAX_BLOCK) // 2 * 2
-    elif isinstance(block, bool) or not isinstance(block, (int, np.integer)) or block % 2 or not ops.FRC_MIN_BLOCK <= block <= min(H, W, ops.FRC_MAX_BLOCK):
-        raise ValueError(f"block must be an even int from {ops.FRC_MIN_BLOCK} to {min(H, W, ops.FRC_MAX_BLOCK)} (the smaller side, at most "
-                         f"{ops.FRC_MAX_BLOCK}). Given {block!r}.")
-    block, smooth = int(block), int(smooth)
-    if not (a.is_cuda or b.is_cuda or torch.cuda.is_available()):
-        raise RuntimeError("pssr2_amd.util.frc needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
-    dev = a.device if a.is_cuda else (b.device if b.is_cuda else "cuda")
-    sums = ops.frc_rings_u8(a.to(dev), b.to(dev), block, window).cpu().numpy().reshape(n_img, -1, block // 2 + 1, 3)
+    (a, b), batched, block, dev = _spectral_inputs("frc", (("a", a), ("b", b)), block)
+    n_img, smooth = a.shape[0], int(smooth)
+    sums = ops.frc_rings_u8(a, b, block, window).cpu().numpy().reshape(n_img, -1, block // 2 + 1, 3)
     items = [_frc_resolve(sums[i], block, float(threshold), smooth, float(pixel_size)) for i in range(n_img)]
     curve = np.stack([it[0] for it in items])
     resolution = np.array([it[1] for it in items], dtype=np.float64)
@@ -874,6 +884,88 @@ def frc(a, b, *, block=None, window: str = "hann", threshold: float = 1 / 7, smo
     if not batched:
         curve, resolution, crossed = curve[0], float(resolution[0]), bool(crossed[0])
     return FRC(curve if to_numpy else torch.from_numpy(curve).to(dev), freq, resolution, crossed, block)
+
+
+SectorFRC = namedtuple("SectorFRC", "curve freq resolution crossed angles anisotropy block")
+
+
+def _check_sectors(sectors):
+    if isinstance(sectors, bool) or not isinstance(sectors, (int, np.integer)) or not 1 <= sectors <= ops.FRC_MAX_SECTORS:
+        raise ValueError(f"sectors must be an int from 1 to {ops.FRC_MAX_SECTORS}. Given {sectors!r}.")
+
+
+def _frc_resolve_sector(sums, pop, n: int, threshold: float, smooth: int, pixel_size: float):
+    """``_frc_resolve`` for one sector (step S5 of include/pssr_mi355.h): ``sums`` float64 [..., n // 2 + 1, 3], the sector's cells, every
+    leading axis pooled; ``pop`` [n // 2 + 1], the sector's populations.  ``smooth = k`` pools sums and populations of rings
+    ``max(1, r - k) .. min(R, r + k)``; a cell whose pooled population is 0 has the curve value NaN and is skipped: the search walks the
+    populated rings ``r >= 1`` in ascending order, and the first one below ``threshold`` is crossed at
+    ``r* = r_prev + (c_prev - threshold) / (c_prev - c_r) (r - r_prev)``, ``r_prev`` the populated ring before it (ring 0 counts); ``r* = 1``
+    where that ring lies below the threshold too, or where there is none (ring 0 is populated in sector 0 alone)."""
+    R = n // 2
+    pooled = np.asarray(sums, dtype=np.float64).reshape(-1, R + 1, 3).sum(axis=0)
+    pop = np.asarray(pop, dtype=np.int64)
+    rings, count = pooled.copy(), pop.copy()
+    for r in range(1, R + 1):
+        lo, hi = max(1, r - smooth), min(R, r + smooth) + 1
+        rings[r], count[r] = pooled[lo:hi].sum(axis=0), pop[lo:hi].sum()
+    curve = np.full(R + 1, math.nan, dtype=np.float64)
+    for r in range(R + 1):
+        if count[r] > 0:
+            sab, saa, sbb = (float(v) for v in rings[r])
+            curve[r] = sab / math.sqrt(saa * sbb) if saa * sbb > 0 else 0.0
+    prev = 0 if count[0] > 0 else None
+    for r in range(1, R + 1):
+        if count[r] == 0:
+            continue
+        if curve[r] < threshold:
+            r_star = 1.0
+            if prev is not None and curve[prev] >= threshold:
+                before, here = float(curve[prev]), float(curve[r])
+                r_star = prev + (before - threshold) / (before - here) * (r - prev)
+            return curve, (pixel_size * n / r_star if r_star > 0 else math.inf), True
+        prev = r
+    return curve, 2.0 * pixel_size, False
+
+
+def frc_sectors(a, b, *, sectors: int = 2, block=None, window: str = "hann", threshold: float = 1 / 7, smooth: int = 0, pixel_size: float = 1.0,
+                to_numpy: bool = True):
+    r"""``frc`` per direction: every ring is cut into ``sectors`` (1 .. 16) sectors of the direction of the frequency vector, sector ``s``
+    centred on ``s * 180 / sectors`` degrees, and each sector gets its own curve and crossing.  Sector 0 holds frequencies along ``x``
+    (detail along a scan line); with an even count, sector ``sectors // 2`` holds frequencies along ``y`` (detail from line to line).  Inputs,
+    ``block``, ``window``, ``threshold``, ``smooth`` and ``pixel_size`` are ``frc``'s (include/pssr_mi355.h, "Directional resolution", has the
+    definitions).  Returns ``SectorFRC(curve, freq, resolution, crossed, angles, anisotropy, block)``:
+
+    * ``curve``: float64 [N, sectors, block // 2 + 1], NaN in a (ring, sector) cell that holds no coefficient (low rings of many sectors);
+      such cells are skipped by the crossing search, which interpolates between the populated rings on either side; ``freq`` as in ``frc``;
+    * ``resolution``, ``crossed``: [N, sectors]; ``angles``: float64 [sectors], the sectors' directions in degrees;
+    * ``anisotropy``: float64 [N], the largest over the smallest sector resolution of the item (1: isotropic).
+
+    One sums launch for the whole batch (``pssr_frc_sectors_u8``: the transform of ``frc``, and a fixed-order reduction over (ring, sector)
+    cells); ``sectors=1`` is ``frc``.  A pair without the batch axis loses the leading axis everywhere."""
+    if window not in ops.FRC_WINDOWS:
+        raise ValueError(f"window must be one of {ops.FRC_WINDOWS}. Given {window!r}.")
+    _check_sectors(sectors)
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or not 0 < threshold < 1:
+        raise ValueError(f"threshold must be a number inside (0, 1). Given {threshold!r}.")
+    if isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)) or smooth < 0:
+        raise ValueError(f"smooth must be a non-negative int (rings pooled on either side). Given {smooth!r}.")
+    if isinstance(pixel_size, bool) or not isinstance(pixel_size, (int, float, np.integer, np.floating)) or not pixel_size > 0:
+        raise ValueError(f"pixel_size must be a positive number. Given {pixel_size!r}.")
+    (a, b), batched, block, dev = _spectral_inputs("frc_sectors", (("a", a), ("b", b)), block)
+    n_img, S, smooth = a.shape[0], int(sectors), int(smooth)
+    sums = ops.frc_sectors_u8(a, b, block, S, window).cpu().numpy().reshape(n_img, -1, block // 2 + 1, S, 3)
+    pop = ops.frc_sector_pop(block, S)
+    items = [[_frc_resolve_sector(sums[i, :, :, s], pop[:, s], block, float(threshold), smooth, float(pixel_size)) for s in range(S)]
+             for i in range(n_img)]
+    curve = np.stack([np.stack([it[0] for it in item]) for item in items])
+    resolution = np.array([[it[1] for it in item] for item in items], dtype=np.float64)
+    crossed = np.array([[it[2] for it in item] for item in items], dtype=bool)
+    anisotropy = resolution.max(axis=1) / resolution.min(axis=1)
+    freq = np.arange(block // 2 + 1, dtype=np.float64) / block
+    angles = np.arange(S, dtype=np.float64) * 180.0 / S
+    if not batched:
+        curve, resolution, crossed, anisotropy = curve[0], resolution[0], crossed[0], float(anisotropy[0])
+    return SectorFRC(curve if to_numpy else torch.from_numpy(curve).to(dev), freq, resolution, crossed, angles, anisotropy, block)
 
 
 Decorr = namedtuple("Decorr", "resolution found peak amplitude curves freq block")
@@ -911,18 +1003,19 @@ def _decorr_peak(d):
     return None
 
 
-def _decorr_resolve(sums, n: int, filters: int, pixel_size: float):
+def _decorr_resolve(sums, n: int, filters: int, pixel_size: float, pop=None):
     """``(resolution, found, peak, amplitude, curves, chosen)`` of one item (or one block) from the ring sums of the spectra it pools
     (``sums``: float64 [..., n // 2 + 1, 2], the layout of ``pssr_decorr_rings_u8``; every leading axis pools), in exactly the expressions of
     steps 3 - 7 of include/pssr_mi355.h: the sums add ring by ring, ``d_g(r) = sum_{1..r} g A / sqrt(sum_{1..R} g^2 P . M(r))`` for the
     unfiltered curve and the ``filters`` high-passed ones, the peak rule on each, the largest refined peak position ``p*`` (``chosen``: the
     index of its curve, ``None`` without one; ``peak`` is then NaN and ``amplitude`` 0) and ``resolution = pixel_size n / p*``, or the
-    sampling limit ``2 pixel_size`` where no curve peaks.  No device involved."""
+    sampling limit ``2 pixel_size`` where no curve peaks.  ``pop``: the coefficients per ring of one spectrum, [n // 2 + 1] (``None``: the
+    whole rings; ``decorr_sectors`` gives a sector's).  No device involved."""
     R = n // 2
     flat = np.asarray(sums, dtype=np.float64).reshape(-1, R + 1, 2)
     pooled = flat.sum(axis=0)
     A, P = pooled[1:, 0], pooled[1:, 1]
-    M = flat.shape[0] * np.cumsum(_decorr_pop(n)[1:])
+    M = flat.shape[0] * np.cumsum((_decorr_pop(n) if pop is None else np.asarray(pop, dtype=np.float64))[1:])
     rho2 = (np.arange(1, R + 1, dtype=np.float64) / R) ** 2
 
     def curve(g):
@@ -950,16 +1043,16 @@ def _decorr_resolve(sums, n: int, filters: int, pixel_size: float):
     return pixel_size * n / p, True, p, amplitude, curves, chosen
 
 
-def _decorr_assemble(sums, n_img: int, c: int, nby: int, nbx: int, n: int, filters: int, pool: str, pixel_size: float, batched: bool):
+def _decorr_assemble(sums, n_img: int, c: int, nby: int, nbx: int, n: int, filters: int, pool: str, pixel_size: float, batched: bool, pop=None):
     """The host half of ``decorr``: ``_decorr_resolve`` per item (``pool="item"``) or per block of the grid (``"block"``; the item's planes
-    pool either way) of the ring sums of a batch, and the result arrays in their shapes."""
+    pool either way) of the ring sums of a batch, and the result arrays in their shapes.  ``pop`` goes to ``_decorr_resolve``."""
     R = n // 2
     sums = np.asarray(sums, dtype=np.float64).reshape(n_img, c, nby * nbx, R + 1, 2)
     if pool == "item":
-        items = [_decorr_resolve(sums[i], n, filters, pixel_size) for i in range(n_img)]
+        items = [_decorr_resolve(sums[i], n, filters, pixel_size, pop) for i in range(n_img)]
         shape = (n_img,)
     else:
-        items = [_decorr_resolve(sums[i, :, k], n, filters, pixel_size) for i in range(n_img) for k in range(nby * nbx)]
+        items = [_decorr_resolve(sums[i, :, k], n, filters, pixel_size, pop) for i in range(n_img) for k in range(nby * nbx)]
         shape = (n_img, nby, nbx)
     resolution = np.array([it[0] for it in items], dtype=np.float64).reshape(shape)
     found = np.array([it[1] for it in items], dtype=bool).reshape(shape)
@@ -1001,32 +1094,51 @@ def decorr(img, *, block=None, window: str = "hann", filters: int = 10, pool: st
         raise ValueError(f"pool must be one of {DECORR_POOLS}. Given {pool!r}.")
     if isinstance(pixel_size, bool) or not isinstance(pixel_size, (int, float, np.integer, np.floating)) or not pixel_size > 0:
         raise ValueError(f"pixel_size must be a positive number. Given {pixel_size!r}.")
-    host = torch.is_tensor(img) and not img.is_cuda
-    a = img if torch.is_tensor(img) else torch.as_tensor(np.ascontiguousarray(img))
-    if a.dtype != torch.uint8:
-        raise TypeError(f"decorr takes uint8 images; img is {a.dtype}")
-    if host:
-        raise RuntimeError("pssr2_amd.util.decorr runs on an MI355X (HIP) device only; there is no CPU fallback")
-    if a.dim() not in (2, 3, 4):
-        raise ValueError(f"img must be [images, planes, height, width] or one [planes, height, width] or [height, width] image. The shape is {tuple(a.shape)}.")
-    batched = a.dim() == 4
-    a = a.reshape((1,) * (4 - a.dim()) + tuple(a.shape))
-    n_img, c, H, W = a.shape
-    if min(n_img, c) < 1 or min(H, W) < ops.FRC_MIN_BLOCK:
-        raise ValueError(f"decorr needs at least one plane of at least {ops.FRC_MIN_BLOCK}x{ops.FRC_MIN_BLOCK} pixels. The shape is {tuple(a.shape)}.")
-    if block is None:
-        block = min(H, W, ops.FRC_MAX_BLOCK) // 2 * 2
-    elif isinstance(block, bool) or not isinstance(block, (int, np.integer)) or block % 2 or not ops.FRC_MIN_BLOCK <= block <= min(H, W, ops.FRC_MAX_BLOCK):
-        raise ValueError(f"block must be an even int from {ops.FRC_MIN_BLOCK} to {min(H, W, ops.FRC_MAX_BLOCK)} (the smaller side, at most "
-                         f"{ops.FRC_MAX_BLOCK}). Given {block!r}.")
-    block, filters, pixel_size = int(block), int(filters), float(pixel_size)
-    if not (a.is_cuda or torch.cuda.is_available()):
-        raise RuntimeError("pssr2_amd.util.decorr needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
-    dev = a.device if a.is_cuda else "cuda"
-    sums = ops.decorr_rings_u8(a.to(dev), block, window).cpu().numpy()
+    (a,), batched, block, dev = _spectral_inputs("decorr", (("img", img),), block)
+    (n_img, c, H, W), filters, pixel_size = a.shape, int(filters), float(pixel_size)
+    sums = ops.decorr_rings_u8(a, block, window).cpu().numpy()
     resolution, found, peak, amplitude, curves = _decorr_assemble(sums, n_img, c, H // block, W // block, block, filters, pool, pixel_size, batched)
     freq = np.arange(block // 2 + 1, dtype=np.float64) / (block * pixel_size)
     return Decorr(resolution, found, peak, amplitude, curves if to_numpy else torch.from_numpy(curves).to(dev), freq, block)
+
+
+SectorDecorr = namedtuple("SectorDecorr", "resolution found peak amplitude curves freq angles anisotropy block")
+
+
+def decorr_sectors(img, *, sectors: int = 2, block=None, window: str = "hann", filters: int = 10, pool: str = "item", pixel_size: float = 1.0,
+                   to_numpy: bool = True):
+    r"""``decorr`` per direction: the rings cut into ``sectors`` (1 .. 16) sectors as in ``frc_sectors`` (sector 0: frequencies along ``x``),
+    and the curves, the peak rule and the filter family of ``decorr`` run on each sector's two sums, with the sector's own coefficient
+    counts in the normalisation (include/pssr_mi355.h, "Directional resolution").  Inputs and the other arguments are ``decorr``'s.  Returns
+    ``SectorDecorr(resolution, found, peak, amplitude, curves, freq, angles, anisotropy, block)``: the fields of ``Decorr`` with a sector axis
+    after the item axis (``pool="block"``: after the item and the two block axes, a directional local-resolution map) -- ``resolution``
+    [N, sectors] or [N, nby, nbx, sectors], ``curves`` [N, sectors, filters + 1, block // 2 + 1] -- ``angles`` float64 [sectors] in degrees,
+    and ``anisotropy`` [N] (or [N, nby, nbx]), the largest over the smallest sector resolution.  One sums launch sequence for the whole batch
+    (``pssr_decorr_sectors_u8``); ``sectors=1`` is ``decorr``.  An image without the batch axis loses the leading axis everywhere."""
+    if window not in ops.FRC_WINDOWS:
+        raise ValueError(f"window must be one of {ops.FRC_WINDOWS}. Given {window!r}.")
+    _check_sectors(sectors)
+    if isinstance(filters, bool) or not isinstance(filters, (int, np.integer)) or not 0 <= filters <= DECORR_MAX_FILTERS:
+        raise ValueError(f"filters must be an int from 0 to {DECORR_MAX_FILTERS} (high-passed curves beside the plain one). Given {filters!r}.")
+    if pool not in DECORR_POOLS:
+        raise ValueError(f"pool must be one of {DECORR_POOLS}. Given {pool!r}.")
+    if isinstance(pixel_size, bool) or not isinstance(pixel_size, (int, float, np.integer, np.floating)) or not pixel_size > 0:
+        raise ValueError(f"pixel_size must be a positive number. Given {pixel_size!r}.")
+    (a,), batched, block, dev = _spectral_inputs("decorr_sectors", (("img", img),), block)
+    (n_img, c, H, W), S, filters, pixel_size = a.shape, int(sectors), int(filters), float(pixel_size)
+    sums = ops.decorr_sectors_u8(a, block, S, window).cpu().numpy()
+    pop = ops.frc_sector_pop(block, S)
+    parts = [_decorr_assemble(sums[..., s, :], n_img, c, H // block, W // block, block, filters, pool, pixel_size, True, pop[:, s]) for s in range(S)]
+    resolution, found, peak, amplitude = (np.stack([p[k] for p in parts], axis=-1) for k in range(4))
+    curves = np.stack([p[4] for p in parts], axis=resolution.ndim - 1)
+    anisotropy = resolution.max(axis=-1) / resolution.min(axis=-1)
+    freq = np.arange(block // 2 + 1, dtype=np.float64) / (block * pixel_size)
+    angles = np.arange(S, dtype=np.float64) * 180.0 / S
+    if not batched:
+        resolution, found, peak, amplitude, curves, anisotropy = resolution[0], found[0], peak[0], amplitude[0], curves[0], anisotropy[0]
+        if pool == "item":
+            anisotropy = float(anisotropy)
+    return SectorDecorr(resolution, found, peak, amplitude, curves if to_numpy else torch.from_numpy(curves).to(dev), freq, angles, anisotropy, block)
 
 
 def _sort_tiles(name: str):
