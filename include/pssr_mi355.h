@@ -1107,6 +1107,48 @@ int pssr_noise_profile_u8(const uint8_t* a, const uint8_t* b, int32_t* hist, dou
 int pssr_noise_profile_loss(const int32_t* pred_hist, const double* pred_sum, const int32_t* target_hist, const double* target_sum,
                             int images, int64_t per_image, int width, double* loss, double* terms, double* mean, pssr_stream_t stream);
 
+/* Scan phase of a bidirectional point scanner (pssr2_amd.crappifiers.ScanPhase, pssr2_amd.util.estimate_scan_phase /
+ * correct_scan_phase; csrc/scanline.hip, csrc/crappify.hip, csrc/shift_rows.h).  Every second line of a resonant or bidirectional scan
+ * is acquired on the way back, and a timing error moves all odd rows sideways against the even ones, usually by a fraction of a pixel
+ * to 3 pixels.  One definition of "row y moved by d / 256 pixels" serves the crappifier, the estimate and the correction.
+ *   D1. Row resampling.  X a plane [H][W], d[y] an int32 per row in 1/256 pixel, |d| <= 256 * 64 (an entry beyond it is clamped).  The
+ *       content of row y moves right by d[y] / 256, edge replicated:
+ *         p = 256 x - d[y],  i = p >> 8 (floor),  f = p & 255,  a = X[y][clamp(i, 0, W-1)],  b = X[y][clamp(i+1, 0, W-1)]
+ *       uint8:    out = ((256 - f) a + f b + 128) >> 8.
+ *       float32:  v = ((256 - f) a + f b) / 256 in float64 (both products and the division are exact and the sum rounds once, so a
+ *                 contraction cannot move it), then + gain, then the finish(flags) of every crappifier stage (bit 1: rint, half to even;
+ *                 bits 0 or 1: clip to [0, 255]), then float32.
+ *       On integer-valued input with gain = 0 and flags 0 the two agree up to the + 128 >> 8 rounding.
+ *   D2. The crappifier's row table, for tile t (the global index: tile_offset + the device tile_counter + the batch index, as in the
+ *       other stages), frame c and row y, from the Philox stream of (seed, t):
+ *         phi_t = intensity, or intensity + spread N(draw(seed, t, ~0, 7)) when spread > 0 -- NOT clamped at 0, the sign is the direction;
+ *         j     = jitter N(draw(seed, t, c H + y, 11)) when jitter > 0, else 0;
+ *         d     = rint(256 (phi_t (y & 1) + j)), clamped to +-256 * 64.
+ *   D3. Row sums.  X uint8 [planes][H][W], a radius R of 0 .. 16, T = 2R + 1; H >= 3, W >= T, H W <= 2^28.  For every interior row
+ *       y in 1 .. H-2, every column x in R .. W-R-1 and every k in -R .. R:  O_k = X[y][x + k],  E = X[y-1][x] + X[y+1][x].
+ *       One output row holds 3T + 2 exact unsigned 64-bit integers: (sum O_k, sum O_k^2, sum O_k E) for k = -R .. R, then sum E, sum E^2:
+ *       the layout of pssr_register_shifts_u8, per row.  The output is [planes][H-2][3T+2].
+ *   D4. The estimate (host, Python ints).  The rows of a pool (a plane, the planes of an item, or everything) add: odd rows add at k, even
+ *       interior rows at -k (an even row sits unmoved between two moved ones); n = the number of (row, column) pairs.  With D = O_k, L = E:
+ *       num_k = n Sdl - Sd Sl, den_k = n Sdd - Sd^2, denl = n Sll - Sl^2.  The score of k is the signed squared Pearson correlation
+ *       num_k |num_k| / (den_k denl), 0 where a variance is 0; candidates are compared by cross-multiplying integers; ties go to the
+ *       smaller |k|, then to the smaller k.  Sub-pixel step with the float correlations r-, r0, r+ at k-1, k, k+1: if |k| < R and
+ *       c = r- - 2 r0 + r+ < 0 then delta = 0.5 (r- - r+) / c clipped to +-0.5, else 0; phase = k + delta.
+ *   D5. The correction: D1 (uint8) on the odd rows with d = -floor(256 phase + 0.5), d = 0 on the even rows.
+ * pssr_line_moments_u8: D3 in one launch for all planes, integers only, every output slot written by one thread: no atomics, no fence, no
+ *   floating point, no workspace, the same bits on every run.
+ * pssr_shift_rows_u8 / pssr_shift_rows_f32: D1 for in, out [planes][H][W] (not in place) and a device table [planes][H], with 16-byte
+ *   stores where the rows are whole aligned pieces.  Nothing outside a row is read whatever the table holds.
+ * pssr_scan_rows_table: D2, table [tiles][frames][h]; tile_counter (or NULL) is a device uint64 added to tile_offset in the kernel.
+ * All four validate on the host before anything is launched (null pointers, planes or sizes < 1, H < 3, W < 2R + 1, R outside 0 .. 16,
+ * H W > 2^28, flags outside 0 .. 3, negative spread or jitter, in == out): PSSR_ERR_ARG with a message. */
+int pssr_line_moments_u8(const uint8_t* x, uint64_t* sums, int planes, int H, int W, int radius, pssr_stream_t stream);
+int pssr_shift_rows_u8(const uint8_t* in, uint8_t* out, const int32_t* table, int planes, int H, int W, pssr_stream_t stream);
+int pssr_shift_rows_f32(const float* in, float* out, const int32_t* table, int planes, int H, int W, float gain, int flags,
+                        pssr_stream_t stream);
+int pssr_scan_rows_table(int32_t* table, int tiles, int frames, int h, float intensity, float spread, float jitter, uint64_t seed,
+                         uint64_t tile_offset, const uint64_t* tile_counter, pssr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """pssr2_amd — MI355X-native hot path of PSSR2 (ResUNet train/infer, MS-SSIM+L1 loss, crappifiers)."""
 __version__ = "0.1.0"
 
-from .crappifiers import AdditiveGaussian, Blur, Crappifier, MultiCrappifier, Poisson, SaltPepper  # noqa: E402,F401
+from .crappifiers import AdditiveGaussian, Blur, Crappifier, MultiCrappifier, Poisson, SaltPepper, ScanPhase  # noqa: E402,F401
 
 
 def __getattr__(name):

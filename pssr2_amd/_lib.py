@@ -168,6 +168,11 @@ def lib():
         _lib.pssr_level_moments_workspace_bytes.restype = c_i64
         _lib.pssr_level_moments_workspace_bytes.argtypes = [c_int, c_i64]
         _lib.pssr_level_moments_u8.argtypes = [c_void_p] * 3 + [c_int, c_i64, c_void_p, c_i64, c_void_p]
+        # scan phase (csrc/scanline.hip, csrc/crappify.hip)
+        _lib.pssr_line_moments_u8.argtypes = [c_void_p] * 2 + [c_int] * 4 + [c_void_p]
+        _lib.pssr_shift_rows_u8.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_void_p]
+        _lib.pssr_shift_rows_f32.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_float, c_int, c_void_p]
+        _lib.pssr_scan_rows_table.argtypes = [c_void_p] + [c_int] * 3 + [c_float] * 3 + [C.c_uint64] * 2 + [c_void_p] * 2
         # one-pass backward of a flat-K source (csrc/pre_xcol_bwd.hip)
         _lib.pssr_flatk_bwd_pair_supported.argtypes = [c_int] * 3
         _lib.pssr_flatk_bwd_pair_parts.argtypes = [c_i64]

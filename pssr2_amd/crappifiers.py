@@ -23,7 +23,7 @@ class Crappifier(ABC):
     def __call__(self, image: np.ndarray):
         return self.crappify(image)
 
-    # device-side description consumed by csrc/crappify.hip: (kind, intensity, gain, spread)
+    # device-side description consumed by csrc/crappify.hip: (kind, intensity, gain, spread), for ScanPhase with a fifth field (jitter)
     def device_spec(self):
         raise NotImplementedError(f"{type(self).__name__} has no MI355X device path; it runs on the host through crappify()")
 
@@ -129,3 +129,42 @@ class Blur(Crappifier):
 
     def device_spec(self):
         return ("blur", float(self.intensity), float(self.gain), float(self.spread))
+
+
+SCAN_MAX_SHIFT = 256 * 64        # |d| of a row's displacement, in 1/256 pixel
+
+
+def shift_rows(image, d):
+    """Row resampling on the host (include/pssr_mi355.h, D1, the float form without gain): ``image`` [..., H, W], ``d`` integers
+    [..., H] in 1/256 pixel; the content of every row moves right by ``d / 256`` with edge replication.  -> float64."""
+    img = np.asarray(image, dtype=np.float64)
+    w = img.shape[-1]
+    p = 256 * np.arange(w, dtype=np.int64) - np.clip(np.asarray(d, dtype=np.int64), -SCAN_MAX_SHIFT, SCAN_MAX_SHIFT)[..., None]
+    i, f = p >> 8, (p & 255).astype(np.float64)
+    a = np.take_along_axis(img, np.clip(i, 0, w - 1), axis=-1)
+    b = np.take_along_axis(img, np.clip(i + 1, 0, w - 1), axis=-1)
+    return ((256.0 - f) * a + f * b) / 256.0
+
+
+class ScanPhase(Crappifier):
+    def __init__(self, intensity: float = 1.0, gain: float = 0, spread: float = 0, *, jitter: float = 0.0):
+        r"""Bidirectional scan phase: every odd row moves sideways by ``intensity`` pixels (negative: to the left) against the even
+        rows, the comb a resonant scanner draws on vertical edges when the return sweep is mistimed.  ``spread`` randomises the phase
+        per call (it is not clamped at 0: the sign is the direction); ``jitter`` is the sigma in pixels of an independent displacement
+        of every line.  Rows are resampled linearly in steps of 1/256 pixel with edge replication."""
+        if spread < 0 or jitter < 0:
+            raise ValueError(f"ScanPhase: spread and jitter must not be negative. Given {spread!r} and {jitter!r}.")
+        self.intensity, self.gain, self.spread, self.jitter = intensity, gain, spread, jitter
+
+    def crappify(self, image: np.ndarray, *, table=None):
+        """``image`` [C, H, W].  ``table``: the rows' displacements [C, H] in 1/256 pixel, in place of the draws."""
+        if table is None:
+            c, h = image.shape[0], image.shape[-2]
+            phase = np.random.normal(self.intensity, self.spread) if self.spread > 0 else self.intensity      # scalar first, then the rows
+            j = np.random.normal(0, self.jitter, (c, h)) if self.jitter > 0 else 0.0
+            table = np.clip(np.rint(256.0 * (phase * (np.arange(h) & 1) + j)), -SCAN_MAX_SHIFT, SCAN_MAX_SHIFT)
+            table = np.broadcast_to(table, (c, h))
+        return shift_rows(image.astype(np.float32), table) + self.gain
+
+    def device_spec(self):
+        return ("scanphase", float(self.intensity), float(self.gain), float(self.spread), float(self.jitter))

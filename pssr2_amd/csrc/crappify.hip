@@ -4,6 +4,7 @@
 // _gen_pair.  All HBM-bound byte/float work: one thread per output element, coalesced rows.
 #include "common.h"
 #include "pil_taps.h"      // Taps / pil_taps / clip8: shared with consistency.hip
+#include "shift_rows.h"    // shift_rows_kernel: shared with scanline.hip
 
 namespace {
 
@@ -255,6 +256,34 @@ __global__ void gen_pair_geometry_kernel(const GatherItem* __restrict__ items, u
     }
 }
 
+// ScanPhase (bidirectional scan phase; D1 and D2 of the scan-phase block of include/pssr_mi355.h).  The row table, one thread per row of
+// [tiles][frames][h]: d = rint(256 (phi_t (y & 1) + j)) clamped to +-256 * 64, phi_t = intensity (+ spread N of the tile's scalar draw, NOT
+// clamped at 0: the sign is the direction), j = jitter N(draw(seed, tile, c h + y, 11)).
+__global__ void scan_rows_table_kernel(int* __restrict__ table, int tiles, int frames, int h, float intensity, float spread, float jitter,
+                                       uint64_t seed, uint64_t tile_offset, const uint64_t* __restrict__ tile_counter) {
+    if (tile_counter) tile_offset += tile_counter[0];
+    const long per_tile = (long)frames * h, total = (long)tiles * per_tile;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long tile = i / per_tile, row = i % per_tile;     // row = c h + y
+        const Philox ph(seed, tile_offset + tile);
+        double phi = (double)intensity;
+        if (spread > 0.f) phi += (double)spread * normal_from(ph(~0ull, 7u));
+        const double j = jitter > 0.f ? (double)jitter * normal_from(ph((uint64_t)row, 11u)) : 0.0;
+        double d = rint(256.0 * (((row % h) & 1 ? phi : 0.0) + j));
+        d = d < -(double)SCAN_MAX_D ? -(double)SCAN_MAX_D : (d > (double)SCAN_MAX_D ? (double)SCAN_MAX_D : d);
+        table[i] = (int)d;
+    }
+}
+// the float form of D1: ((256 - f) a + f b) / 256 in float64 (both products and the division are exact, the sum rounds once whether or
+// not it is contracted), + gain, finish, float32
+struct MixF32 {
+    double gain; int flags;
+    __device__ __forceinline__ float operator()(float a, float b, int f) const {
+        const double v = ((double)(256 - f) * (double)a + (double)f * (double)b) * (1.0 / 256.0);
+        return (float)finish(v + gain, flags);
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -355,6 +384,29 @@ int pssr_gen_pair_geometry_u8(const pssr_gather_item* items_dev, int n_items, ui
     const long per_tile = (long)c * res * res;
     long gx = (per_tile + 255) / 256; if (gx > 256) gx = 256;
     hipLaunchKernelGGL(gen_pair_geometry_kernel, dim3((unsigned)gx, n_items), dim3(256), 0, (hipStream_t)s, (const GatherItem*)items_dev, out, c, res);
+    PSSR_LAUNCH_CHECK();
+    return PSSR_OK;
+}
+
+int pssr_scan_rows_table(int32_t* table, int tiles, int frames, int h, float intensity, float spread, float jitter, uint64_t seed,
+                         uint64_t tile_offset, const uint64_t* tile_counter, pssr_stream_t s) {
+    PSSR_CHECK(table != nullptr, PSSR_ERR_ARG, "scan_rows_table: null pointer");
+    PSSR_CHECK(tiles > 0 && frames > 0 && h > 0, PSSR_ERR_ARG, "scan_rows_table: tiles, frames and h must be positive (%d, %d, %d)", tiles, frames, h);
+    PSSR_CHECK(spread >= 0.f && jitter >= 0.f && intensity == intensity, PSSR_ERR_ARG, "scan_rows_table: spread and jitter must not be negative (%g, %g)",
+               (double)spread, (double)jitter);
+    hipLaunchKernelGGL(scan_rows_table_kernel, dim3(grid1d((long)tiles * frames * h, 8192)), dim3(256), 0, (hipStream_t)s, (int*)table, tiles, frames, h,
+                       intensity, spread, jitter, seed, tile_offset, tile_counter);
+    PSSR_LAUNCH_CHECK();
+    return PSSR_OK;
+}
+
+int pssr_shift_rows_f32(const float* in, float* out, const int32_t* table, int planes, int H, int W, float gain, int flags, pssr_stream_t s) {
+    PSSR_CHECK(in && out && table, PSSR_ERR_ARG, "shift_rows_f32: null pointer");
+    PSSR_CHECK(in != out, PSSR_ERR_ARG, "shift_rows_f32: in place is not supported (a row is read while it is written)");
+    PSSR_CHECK(planes > 0 && H > 0 && W > 0, PSSR_ERR_ARG, "shift_rows_f32: planes, H and W must be positive (%d, %d, %d)", planes, H, W);
+    PSSR_CHECK((long)H * W <= (1L << 28), PSSR_ERR_ARG, "shift_rows_f32: %ld pixels per plane (at most 2^28)", (long)H * W);
+    PSSR_CHECK(flags >= 0 && flags <= 3, PSSR_ERR_ARG, "shift_rows_f32: flags must be 0 .. 3, given %d", flags);
+    launch_shift_rows<float>(in, out, (const int*)table, (long)planes * H, W, MixF32{(double)gain, flags}, (hipStream_t)s);
     PSSR_LAUNCH_CHECK();
     return PSSR_OK;
 }

@@ -750,7 +750,7 @@ class DevicePairGenerator:
 
     def _stage(self, x, spec, seed, tile_offset, flags):
         from . import ops
-        kind, intensity, gain, spread = spec
+        kind, intensity, gain, spread, *more = spec       # a fifth field: ScanPhase's jitter
         if kind == "gaussian":
             return ops.crappify_gaussian(x, intensity, gain, spread, seed, tile_offset, flags, tile_counter=self.tile_counter)
         if kind == "poisson":
@@ -761,6 +761,11 @@ class DevicePairGenerator:
             return ops.gaussian_blur(x, intensity, gain, flags)
         if kind == "saltpepper":
             return ops.crappify_saltpepper(x, intensity, gain, spread, seed, tile_offset, flags, tile_counter=self.tile_counter)
+        if kind == "scanphase":     # a row table from the tile's Philox stream, then the resampling of the rows
+            tiles, h = x.shape[0], x.shape[-2]
+            table = ops.scan_rows_table(tiles, x.numel() // (tiles * h * x.shape[-1]), h, intensity, spread, more[0], seed, tile_offset,
+                                        tile_counter=self.tile_counter)
+            return ops.shift_rows_f32(x, table, gain, flags)
         raise NotImplementedError(kind)
 
     def __call__(self, hr_u8: torch.Tensor, tile_offset: int = 0):

@@ -1554,3 +1554,70 @@ def decorr_sectors_u8(a, block, sectors, window="hann"):
     L.check(lib.pssr_decorr_sectors_u8(L.ptr(a), L.ptr(ct), L.ptr(st), L.ptr(bx), L.ptr(by), L.ptr(sums), planes, H, W, block, sectors, L.ptr(ws),
                                        nbytes, L.stream_ptr()), "pssr_decorr_sectors_u8")
     return sums
+
+
+# ----------------------------------------------------------------------------------------------
+# scan phase of a bidirectional scanner (csrc/scanline.hip, csrc/crappify.hip; definitions in include/pssr_mi355.h)
+MAX_SCAN_RADIUS = 16
+
+
+def line_moments_u8(x, radius):
+    """uint8 device tensor ``x`` [..., H, W] (a non-contiguous one is copied), ``H >= 3``, ``W >= T = 2 radius + 1``, ``radius`` an int in
+    0 .. 16 -> int64 [planes, H - 2, 3 T + 2]: per interior row ``y`` the exact ``sum O_k, sum O_k**2, sum O_k E`` for ``k = -radius ..
+    radius`` with ``O_k = x[y, c + k]`` and ``E = x[y - 1, c] + x[y + 1, c]`` over the columns ``c`` in ``radius .. W - radius - 1``, then
+    ``sum E, sum E**2``.  One launch for all planes."""
+    if not torch.is_tensor(x) or x.dtype != torch.uint8 or not x.is_cuda or x.dim() < 2:
+        raise ValueError("line_moments_u8 needs a uint8 device tensor [..., H, W]")
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= MAX_SCAN_RADIUS:
+        raise ValueError(f"line_moments_u8: the radius must be an int in 0 .. {MAX_SCAN_RADIUS} pixels. Given {radius!r}.")
+    H, W = x.shape[-2:]
+    T = 2 * radius + 1
+    planes = x.numel() // (H * W) if H * W else 0
+    if planes < 1 or H < 3 or W < T or H * W > 1 << 28:
+        raise ValueError(f"line_moments_u8: {planes} planes of {H}x{W} (at least 3 rows, at least {T} columns for radius={radius}, at most 2**28 pixels)")
+    x = x.contiguous()
+    sums = torch.empty(planes, H - 2, 3 * T + 2, dtype=torch.int64, device=x.device)
+    L.check(L.lib().pssr_line_moments_u8(L.ptr(x), L.ptr(sums), planes, H, W, radius, L.stream_ptr()), "pssr_line_moments_u8")
+    return sums
+
+
+def _shift_rows_args(who, x, table, dtype):
+    if not torch.is_tensor(x) or x.dtype != dtype or not x.is_cuda or x.dim() < 2:
+        raise ValueError(f"{who} needs a {dtype} device tensor [..., H, W]")
+    H, W = x.shape[-2:]
+    planes = x.numel() // (H * W) if H * W else 0
+    if planes < 1 or H * W > 1 << 28:
+        raise ValueError(f"{who}: {planes} planes of {H}x{W} (at least one pixel, at most 2**28 per plane)")
+    if not torch.is_tensor(table) or table.dtype != torch.int32 or not table.is_cuda or table.numel() != planes * H or not table.is_contiguous():
+        raise ValueError(f"{who} needs a contiguous int32 device table of {planes * H} entries, one per plane and row")
+    return x.contiguous(), planes, H, W
+
+
+def shift_rows_u8(x, table):
+    """uint8 device tensor ``x`` [..., H, W] and an int32 device ``table`` with one entry ``d`` per (plane, row), in 1/256 pixel -> uint8
+    like ``x``: the content of every row moved right by ``d / 256`` with edge replication, ``((256 - f) a + f b + 128) >> 8``."""
+    x, planes, H, W = _shift_rows_args("shift_rows_u8", x, table, torch.uint8)
+    out = torch.empty_like(x)
+    L.check(L.lib().pssr_shift_rows_u8(L.ptr(x), L.ptr(out), L.ptr(table), planes, H, W, L.stream_ptr()), "pssr_shift_rows_u8")
+    return out
+
+
+def shift_rows_f32(x, table, gain, flags):
+    """float32 device tensor ``x`` [..., H, W] and a row ``table`` as for :func:`shift_rows_u8` -> float32 like ``x``: the rows moved,
+    ``((256 - f) a + f b) / 256`` in float64, then ``+ gain`` and the crappifier stages' round / clip by ``flags``."""
+    x, planes, H, W = _shift_rows_args("shift_rows_f32", x, table, torch.float32)
+    out = torch.empty_like(x)
+    L.check(L.lib().pssr_shift_rows_f32(L.ptr(x), L.ptr(out), L.ptr(table), planes, H, W, C.c_float(gain), flags, L.stream_ptr()),
+            "pssr_shift_rows_f32")
+    return out
+
+
+def scan_rows_table(tiles, frames, h, intensity, spread, jitter, seed, tile_offset, tile_counter=None):
+    """The ScanPhase crappifier's row table, int32 [tiles, frames, h] on the current device: ``rint(256 (phi_t (y & 1) + j))`` clamped to
+    +-256 * 64 with the tile's phase ``phi_t = intensity (+ spread N)`` and the row's ``j = jitter N`` from the Philox stream of
+    ``(seed, tile_offset + tile_counter + tile)``."""
+    table = torch.empty(tiles, frames, h, dtype=torch.int32, device="cuda")
+    L.check(L.lib().pssr_scan_rows_table(L.ptr(table), tiles, frames, h, C.c_float(intensity), C.c_float(spread), C.c_float(jitter),
+                                         C.c_uint64(seed), C.c_uint64(tile_offset), L.ptr(tile_counter), L.stream_ptr()),
+            "pssr_scan_rows_table")
+    return table

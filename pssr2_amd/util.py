@@ -784,6 +784,172 @@ def register_pairs(hr, lr, *, radius: int = 8, to_numpy: bool = True):
     return Registration(hr_out, lr_out, shift, score, m)
 
 
+SCAN_POOLS = ("all", "item", "plane")                # estimate_scan_phase's ``pool``
+
+
+class ScanPhaseFit(namedtuple("ScanPhaseFit", "phase shift score curve radius")):
+    """What :func:`estimate_scan_phase` returns: ``phase`` (pixels, float), ``shift`` (the integer candidate ``k``), ``score`` (the
+    Pearson correlation at ``k``), ``curve`` (the ``2 radius + 1`` correlations, ``k = -radius .. radius``) and ``radius``."""
+    __slots__ = ()
+
+    def crappifier(self, spread: float = 0, jitter: float = 0):
+        """A :class:`pssr2_amd.crappifiers.ScanPhase` that plants the measured phase (the mean over the pool's items)."""
+        from .crappifiers import ScanPhase
+        phase = self.phase.cpu().numpy() if torch.is_tensor(self.phase) else self.phase
+        return ScanPhase(float(np.mean(phase)), spread=spread, jitter=jitter)
+
+
+def _check_scan_radius(radius):
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= ops.MAX_SCAN_RADIUS:
+        raise ValueError(f"radius must be an int from 0 to {ops.MAX_SCAN_RADIUS} (the search radius in pixels). Given {radius!r}.")
+    return int(radius)
+
+
+def _check_scan_pool(pool):
+    if pool not in SCAN_POOLS:
+        raise ValueError(f"pool must be one of {SCAN_POOLS}. Given {pool!r}.")
+
+
+def _scan_image(who, lr, radius):
+    """The checks of the scan-phase entry points' image: a uint8 array or device tensor [N, c, h, w] or [c, h, w], ``h >= 3``,
+    ``w >= 2 radius + 1``, at most 2**28 pixels per plane.  -> ``(4-D tensor where it was, batched)``."""
+    if not torch.is_tensor(lr):
+        lr = torch.as_tensor(np.ascontiguousarray(lr))
+    elif not lr.is_cuda:
+        raise RuntimeError(f"pssr2_amd.util.{who} runs on an MI355X (HIP) device only; there is no CPU fallback")
+    if lr.dtype != torch.uint8:
+        raise TypeError(f"{who} takes uint8 images; lr is {lr.dtype}")
+    if lr.dim() not in (3, 4):
+        raise ValueError(f"lr must be 4-D, [images, frames, height, width], or 3-D without the batch axis. Its shape is {tuple(lr.shape)}.")
+    batched = lr.dim() == 4
+    if not batched:
+        lr = lr[None]
+    n_img, c, h, w = lr.shape
+    if min(n_img, c) < 1 or h < 3 or w < 2 * radius + 1:
+        raise ValueError(f"lr needs at least one plane of at least 3 rows and 2 * radius + 1 = {2 * radius + 1} columns. Its shape is {tuple(lr.shape)}.")
+    if h * w > 1 << 28:
+        raise ValueError(f"A plane of lr of {h * w} pixels is above the 2**28 up to which the sums are exact.")
+    return lr, batched
+
+
+def _scan_choose(n: int, sums, radius: int):
+    """``(k, phase, score, curve)`` of one pool from its ``3 T + 2`` exact pooled sums (Python ints: ``T`` triples ``sum O_k, sum O_k**2,
+    sum O_k E``, then ``sum E, sum E**2``) over ``n`` (row, column) pairs, in exactly the expressions of include/pssr_mi355.h (D4): the
+    score of ``k`` is the signed squared Pearson correlation ``num |num| / (den denl)`` (0 when ``den`` or ``denl`` is 0), compared by
+    cross-multiplying Python ints; ties go to the smaller ``|k|``, then the smaller ``k``; then the parabola through the float
+    correlations at ``k - 1, k, k + 1``."""
+    T = 2 * radius + 1
+    sl, sll = int(sums[3 * T]), int(sums[3 * T + 1])
+    best, curve = None, []
+    for t in range(T):
+        sd, sdd, sdl = (int(v) for v in sums[3 * t:3 * t + 3])
+        k = t - radius
+        num, den, denl, r = _pearson_terms(n, sd, sl, sdd, sdl, sll)
+        curve.append(r)
+        p, q = (num * abs(num), den) if den > 0 and denl > 0 else (0, 1)
+        key = (abs(k), k)
+        if best is None or p * best[1] > best[0] * q or (p * best[1] == best[0] * q and key < best[2]):
+            best = (p, q, key)
+    k = best[2][1]
+    delta = 0.0
+    if abs(k) < radius:
+        rm, r0, rp = curve[k + radius - 1], curve[k + radius], curve[k + radius + 1]
+        c = rm - 2.0 * r0 + rp
+        if c < 0.0:
+            delta = min(max(0.5 * (rm - rp) / c, -0.5), 0.5)
+    return k, k + delta, curve[k + radius], curve
+
+
+def estimate_scan_phase(lr, *, radius: int = 8, pool: str = "all", to_numpy: bool = True):
+    r"""Measures the scan phase of bidirectionally scanned images: the sideways offset, in pixels, of the odd rows against the even ones
+    that a mistimed return sweep leaves (a comb on every vertical edge; it lowers the resolution along x and leaves y alone).  ``lr``:
+    uint8 array or device tensor [N, c, h, w] (or 3-D, without the batch axis).  Every interior row, moved by each integer
+    ``k = -radius .. radius`` (``radius`` 0 .. 16), is correlated with the sum of its two neighbours; odd rows count at ``k``, even rows
+    at ``-k``; the ``k`` with the largest signed squared Pearson correlation wins and a parabola through its neighbours gives the
+    fraction (include/pssr_mi355.h has the definitions, exact integers up to the choice).  ``pool``: one estimate for ``"all"`` planes,
+    per ``"item"`` or per ``"plane"``.  Returns ``ScanPhaseFit(phase, shift, score, curve, radius)``: scalars and a curve [T] for
+    ``pool="all"``, arrays [N] / [N, T] for ``"item"`` and [N, c] / [N, c, T] for ``"plane"`` (without the leading axis for a 3-D input).
+
+    One launch (``pssr_line_moments_u8``), exact int64 pooling on the device, one copy to the host, the choice in Python ints.  A chosen
+    ``|k| == radius > 0`` emits a ``UserWarning`` (the optimum may lie outside the window), and so does an image without any
+    correlation to choose by (a constant image), whose phase is 0.0.  ``to_numpy=False`` returns the arrays as float64 / int64 tensors."""
+    import warnings
+    radius = _check_scan_radius(radius)
+    _check_scan_pool(pool)
+    lr, batched = _scan_image("estimate_scan_phase", lr, radius)
+    if not (lr.is_cuda or torch.cuda.is_available()):
+        raise RuntimeError("pssr2_amd.util.estimate_scan_phase needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
+    n_img, c, h, w = lr.shape
+    T = 2 * radius + 1
+    sums = ops.line_moments_u8(lr.to("cuda") if not lr.is_cuda else lr, radius)          # [planes, h - 2, 3 T + 2]
+    odd, even = sums[:, 0::2].sum(1), sums[:, 1::2].sum(1)                                # rows y = 1, 3, ..  and  y = 2, 4, ..
+    even = torch.cat([even[:, :3 * T].reshape(-1, T, 3).flip(1).reshape(-1, 3 * T), even[:, 3 * T:]], 1)      # an even row counts at -k
+    pooled = (odd + even).reshape(n_img, c, 3 * T + 2)
+    n = (h - 2) * (w - 2 * radius)
+    if pool == "all":
+        pooled, n, shape = pooled.sum((0, 1))[None], n * n_img * c, ()
+    elif pool == "item":
+        pooled, n, shape = pooled.sum(1), n * c, (n_img,)
+    else:
+        pooled, shape = pooled.reshape(n_img * c, -1), (n_img, c)
+    chosen = [_scan_choose(n, row, radius) for row in pooled.cpu().tolist()]
+    edge = [i for i, ch in enumerate(chosen) if radius > 0 and abs(ch[0]) == radius]
+    if edge:
+        warnings.warn(f"estimate_scan_phase: the chosen shift of pool item(s) {edge} lies on the edge of the search window (radius={radius}); "
+                      "the optimum may lie outside it", UserWarning, stacklevel=2)
+    flat = [i for i, ch in enumerate(chosen) if not any(ch[3])]
+    if flat:
+        warnings.warn(f"estimate_scan_phase: pool item(s) {flat} show no correlation between neighbouring rows at any shift (a constant image?); "
+                      "their phase is 0.0", UserWarning, stacklevel=2)
+    if not batched and shape:
+        shape = shape[1:]
+    phase = np.array([ch[1] for ch in chosen], dtype=np.float64).reshape(shape)
+    shift = np.array([ch[0] for ch in chosen], dtype=np.int64).reshape(shape)
+    score = np.array([ch[2] for ch in chosen], dtype=np.float64).reshape(shape)
+    curve = np.array([ch[3] for ch in chosen], dtype=np.float64).reshape(shape + (T,))
+    if not to_numpy:
+        phase, shift, score, curve = (torch.from_numpy(v) for v in (phase, shift, score, curve))
+    if not shape:
+        phase, shift, score = float(phase), int(shift), float(score)
+    return ScanPhaseFit(phase, shift, score, curve, radius)
+
+
+def correct_scan_phase(lr, phase=None, *, radius: int = 8, pool: str = "all", to_numpy: bool = True):
+    r"""Removes the scan phase of bidirectionally scanned images: the odd rows of every plane move back by ``phase`` pixels (linear
+    resampling in steps of 1/256 pixel with edge replication, ``d = -floor(256 phase + 0.5)``: include/pssr_mi355.h, D1 and D5); the even
+    rows are copied.  ``lr`` as for :func:`estimate_scan_phase`.  ``phase=None`` estimates it first with ``radius`` and ``pool``; else a
+    number, or one value per item of ``pool`` (``"all"``: one; ``"item"``: [N]; ``"plane"``: [N, c]).  Returns ``(corrected, phase)``:
+    uint8 of the shape of ``lr`` (a device tensor for ``to_numpy=False``) and the phase that was applied.  Run it in front of
+    ``estimate_noise``, ``register_pairs`` or a prediction: a comb biases all three."""
+    radius = _check_scan_radius(radius)
+    _check_scan_pool(pool)
+    lr, batched = _scan_image("correct_scan_phase", lr, 0)
+    n_img, c, h, w = lr.shape
+    if phase is not None:
+        ph = np.asarray(phase.cpu() if torch.is_tensor(phase) else phase, dtype=np.float64)
+        want = {"all": (), "item": (n_img,), "plane": (n_img, c)}[pool]
+        if not batched:
+            want = want[1:]
+        if ph.shape not in ((), want) or not np.all(np.isfinite(ph)) or np.any(np.abs(ph) > 64):
+            raise ValueError(f"phase must be a finite number of at most 64 pixels, or one per item of pool={pool!r} (shape {want}). Given {phase!r}.")
+    if not (lr.is_cuda or torch.cuda.is_available()):
+        raise RuntimeError("pssr2_amd.util.correct_scan_phase needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
+    lr = lr.to("cuda") if not lr.is_cuda else lr
+    if phase is None:
+        if w < 2 * radius + 1:
+            raise ValueError(f"lr needs at least 2 * radius + 1 = {2 * radius + 1} columns for the estimate. Its shape is {tuple(lr.shape)}.")
+        phase = estimate_scan_phase(lr if batched else lr[0], radius=radius, pool=pool).phase
+        ph = np.asarray(phase, dtype=np.float64)
+    per_plane = np.broadcast_to(ph if ph.ndim == 0 else ph.reshape(n_img, -1), (n_img, c))       # [N] -> [N, 1], [c] -> [1, c]
+    d = -np.floor(256.0 * per_plane + 0.5).astype(np.int64)
+    table = np.zeros((n_img, c, h), dtype=np.int32)
+    table[:, :, 1::2] = d[:, :, None]
+    out = ops.shift_rows_u8(lr, torch.from_numpy(table).to(lr.device))
+    if not batched:
+        out = out[0]
+    return (out.cpu().numpy() if to_numpy else out), phase
+
+
 def _spectral_inputs(who: str, named, block):
     """The checks of the images and the block side that ``frc``, ``decorr`` and their sectorial forms share, in their order (``named``:
     ``(name, image)`` pairs) -> ``(device tensors [N, C, H, W], batched, block, device)``."""
