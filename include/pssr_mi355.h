@@ -1149,6 +1149,46 @@ int pssr_shift_rows_f32(const float* in, float* out, const int32_t* table, int p
 int pssr_scan_rows_table(int32_t* table, int tiles, int frames, int h, float intensity, float spread, float jitter, uint64_t seed,
                          uint64_t tile_offset, const uint64_t* tile_counter, pssr_stream_t stream);
 
+/* Classical baselines: the model-free rows of a super-resolution table, the LR image enlarged and the LR image denoised and then
+ * enlarged (pssr2_amd.util.upsample / nlm_denoise, pssr2_amd.baselines.Baseline; csrc/baseline.hip, csrc/pil_taps.h).  Both are defined
+ * in integers, so that a device result is compared with ==.
+ *   B1. Enlargement: Pillow's 8-bit Image.resize with BILINEAR or BICUBIC, bit for bit.  X a uint8 plane [h][w], r an integer 1 .. 8,
+ *       the output is [h r][w r].  filter 0 = bilinear (triangle, support S = 1), 1 = bicubic (Keys, A = -0.5, S = 2):
+ *         f(a) = ((A + 2) a - (A + 3)) a^2 + 1 for |a| < 1,  (((a - 5) a + 8) a - 4) A for |a| < 2,  else 0.
+ *       The taps of output index xx of an axis in -> out are Pillow's precompute_coeffs + normalize_coeffs_8bpc, in double, in Pillow's
+ *       operation order and without fused multiply-adds:
+ *         scale = in / out,  filterscale = max(scale, 1),  support = S filterscale,  center = (xx + 0.5) scale,
+ *         xmin = max((int)(center - support + 0.5), 0),  xmax = min((int)(center + support + 0.5), in),  n = xmax - xmin,
+ *         w[x] = f((x + xmin - center + 0.5) / filterscale),  x < n;  w[x] /= sum w (added in the order of x);
+ *         k[x] = (int)(0.5 + w[x] 2^22) for w[x] >= 0, (int)(-0.5 + w[x] 2^22) below 0   (PRECISION_BITS = 22).
+ *       Two passes, as Pillow runs them: along x into a uint8 intermediate [h][w r],  mid = clip8((sum_x k[x] X[xmin + x] + 2^21) >> 22)
+ *       (arithmetic shift, then clipped to 0 .. 255); then along y from that intermediate by the same rule.  The rounding and clipping
+ *       between the passes is part of the definition: bicubic overshoot clips in both.
+ *   B2. Non-local means (Buades et al.) in integers.  X a uint8 plane [H][W]; patch radius p in 1 .. 3, P = 2p + 1; search radius s in
+ *       1 .. 10; strength h in grey levels, 0.5 <= h <= 255; noise level sigma >= 0.  The host turns the last two into three integers:
+ *         bias = rint(2 P^2 sigma^2);  qshift = the largest of 0 .. 31 with rint(32 2^qshift / (P^2 h^2)) <= 1023;  qmul = that value
+ *         (qmul < 1: no such h is representable, an error).
+ *       For the output pixel (y, x) and every offset (dy, dx) in [-s, s]^2 whose centre (y + dy, x + dx) lies inside the plane (the others
+ *       are skipped, not clamped), with cy / cx clamping a coordinate into the plane on its own:
+ *         ssd  = sum over (py, px) in [-p, p]^2 of (X[cy(y + py)][cx(x + px)] - X[cy(y + dy + py)][cx(x + dx + px)])^2
+ *         q    = min((max(ssd - bias, 0) qmul) >> qshift, 255),   wgt = LUT[q],   v = X[y + dy][x + dx]
+ *         LUT[q] = rint(16383 exp(-(q + 0.5) / 32)) for q < 255, LUT[255] = 0: a fixed table of the library (pssr_nlm_lut); h enters only
+ *         through qmul and qshift.
+ *       out = (sum wgt v + (sum wgt >> 1)) / sum wgt (integer division).  The centre candidate has ssd = 0, so sum wgt >= LUT[0] > 0.
+ *       Everything fits uint32: ssd <= 49 255^2 < 2^22, ssd qmul < 2^32, 441 16383 255 + 441 16383 / 2 < 2^32 (static_asserts of
+ *       csrc/baseline.hip).
+ * pssr_nlm_u8: B2 for x, out [planes][H][W] in one launch; pssr_upsample_u8: B1 for x [planes][h][w] -> out [planes][h r][w r] in one
+ *   launch, both passes fused, the intermediate in LDS.  No floating point beyond B1's taps, no atomics, no workspace: the same bits on
+ *   every run.  16-byte stores where the output rows are whole aligned pieces.
+ * pssr_nlm_lut: copies LUT to a host table of 256 int32.
+ * All validate on the host before anything is launched (null pointers, planes or sizes < 1, p outside 1 .. 3, s outside 1 .. 10, r
+ * outside 1 .. 8, an unknown filter, qmul outside 1 .. 1023, qshift outside 0 .. 31, bias < 0, more than 2^28 input or output pixels per
+ * plane, x == out): PSSR_ERR_ARG with a message. */
+int pssr_nlm_lut(int32_t* table);
+int pssr_nlm_u8(const uint8_t* x, uint8_t* out, int planes, int H, int W, int p, int s, int qmul, int qshift, int bias,
+                pssr_stream_t stream);
+int pssr_upsample_u8(const uint8_t* x, uint8_t* out, int planes, int h, int w, int r, int filter, pssr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

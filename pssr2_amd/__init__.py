@@ -67,6 +67,12 @@ def __getattr__(name):
     if name in ("estimate_noise",):
         from .util import estimate_noise
         return estimate_noise
+    if name in ("Baseline",):
+        from .baselines import Baseline
+        return Baseline
+    if name in ("upsample", "nlm_denoise"):
+        from . import util
+        return getattr(util, name)
     if name in ("FusedAdamW",):
         from .optim import FusedAdamW
         return FusedAdamW

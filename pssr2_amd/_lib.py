@@ -173,6 +173,10 @@ def lib():
         _lib.pssr_shift_rows_u8.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_void_p]
         _lib.pssr_shift_rows_f32.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_float, c_int, c_void_p]
         _lib.pssr_scan_rows_table.argtypes = [c_void_p] + [c_int] * 3 + [c_float] * 3 + [C.c_uint64] * 2 + [c_void_p] * 2
+        # classical baselines (csrc/baseline.hip)
+        _lib.pssr_nlm_lut.argtypes = [c_void_p]
+        _lib.pssr_nlm_u8.argtypes = [c_void_p] * 2 + [c_int] * 8 + [c_void_p]
+        _lib.pssr_upsample_u8.argtypes = [c_void_p] * 2 + [c_int] * 5 + [c_void_p]
         # one-pass backward of a flat-K source (csrc/pre_xcol_bwd.hip)
         _lib.pssr_flatk_bwd_pair_supported.argtypes = [c_int] * 3
         _lib.pssr_flatk_bwd_pair_parts.argtypes = [c_i64]

@@ -1621,3 +1621,64 @@ def scan_rows_table(tiles, frames, h, intensity, spread, jitter, seed, tile_offs
                                          C.c_uint64(seed), C.c_uint64(tile_offset), L.ptr(tile_counter), L.stream_ptr()),
             "pssr_scan_rows_table")
     return table
+
+
+# ----------------------------------------------------------------------------------------------
+# classical baselines (csrc/baseline.hip; definitions B1 and B2 in include/pssr_mi355.h)
+MAX_NLM_PATCH = 3
+MAX_NLM_SEARCH = 10
+MAX_UPSAMPLE = 8
+UPSAMPLE_FILTERS = ("bilinear", "bicubic")
+
+
+def __getattr__(name):
+    if name == "NLM_LUT":                       # the library's table of 256 weights, read once
+        table = (C.c_int32 * 256)()
+        L.check(L.lib().pssr_nlm_lut(table), "pssr_nlm_lut")
+        globals()["NLM_LUT"] = tuple(table)
+        return globals()["NLM_LUT"]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def _u8_planes_args(who, x):
+    if not torch.is_tensor(x) or x.dtype != torch.uint8 or not x.is_cuda or x.dim() < 2:
+        raise ValueError(f"{who} needs a uint8 device tensor [..., H, W]")
+    H, W = x.shape[-2:]
+    planes = x.numel() // (H * W) if H * W else 0
+    if planes < 1 or H * W > 1 << 28:
+        raise ValueError(f"{who}: {planes} planes of {H}x{W} (at least one pixel, at most 2**28 per plane)")
+    return x.contiguous(), planes, H, W
+
+
+def _int_in(v, lo, hi):
+    return not isinstance(v, bool) and isinstance(v, int) and lo <= v <= hi
+
+
+def nlm_u8(x, p, s, qmul, qshift, bias):
+    """uint8 device tensor ``x`` [..., H, W] (a non-contiguous one is copied) -> uint8 like ``x``: the integer non-local means B2 of
+    include/pssr_mi355.h with patch radius ``p`` (1 .. 3), search radius ``s`` (1 .. 10) and the three integers of
+    ``util._nlm_params``.  One launch for all planes; the same bits on every run."""
+    x, planes, H, W = _u8_planes_args("nlm_u8", x)
+    if not _int_in(p, 1, MAX_NLM_PATCH) or not _int_in(s, 1, MAX_NLM_SEARCH):
+        raise ValueError(f"nlm_u8: p must be an int in 1 .. {MAX_NLM_PATCH} and s one in 1 .. {MAX_NLM_SEARCH}. Given {p!r} and {s!r}.")
+    if not _int_in(qmul, 1, 1023) or not _int_in(qshift, 0, 31) or not _int_in(bias, 0, (1 << 31) - 1):
+        raise ValueError(f"nlm_u8: qmul must be an int in 1 .. 1023, qshift in 0 .. 31, bias in 0 .. 2**31 - 1. Given {qmul!r}, {qshift!r}, {bias!r}.")
+    out = torch.empty_like(x)
+    L.check(L.lib().pssr_nlm_u8(L.ptr(x), L.ptr(out), planes, H, W, p, s, qmul, qshift, bias, L.stream_ptr()), "pssr_nlm_u8")
+    return out
+
+
+def upsample_u8(x, r, filter):
+    """uint8 device tensor ``x`` [..., h, w] (a non-contiguous one is copied) -> uint8 [..., h r, w r]: Pillow's 8-bit ``Image.resize``
+    with ``filter`` ``"bilinear"`` or ``"bicubic"``, bit for bit (B1 of include/pssr_mi355.h), ``r`` an int in 1 .. 8.  One launch for
+    all planes, both passes fused."""
+    x, planes, h, w = _u8_planes_args("upsample_u8", x)
+    if not _int_in(r, 1, MAX_UPSAMPLE):
+        raise ValueError(f"upsample_u8: r must be an int in 1 .. {MAX_UPSAMPLE}. Given {r!r}.")
+    if filter not in UPSAMPLE_FILTERS:
+        raise ValueError(f"upsample_u8: filter must be one of {UPSAMPLE_FILTERS}. Given {filter!r}.")
+    if h * r * w * r > 1 << 28:
+        raise ValueError(f"upsample_u8: {h * r}x{w * r} output pixels per plane (at most 2**28)")
+    out = torch.empty(*x.shape[:-2], h * r, w * r, dtype=torch.uint8, device=x.device)
+    L.check(L.lib().pssr_upsample_u8(L.ptr(x), L.ptr(out), planes, h, w, r, UPSAMPLE_FILTERS.index(filter), L.stream_ptr()), "pssr_upsample_u8")
+    return out

@@ -950,6 +950,102 @@ def correct_scan_phase(lr, phase=None, *, radius: int = 8, pool: str = "all", to
     return (out.cpu().numpy() if to_numpy else out), phase
 
 
+def _baseline_image(who, lr):
+    """The checks of the classical baselines' image, in ``_scan_image``'s order: a uint8 array or device tensor [N, c, h, w] or
+    [c, h, w] with at least one pixel and at most 2**28 per plane.  -> ``(4-D tensor where it was, batched)``."""
+    if not torch.is_tensor(lr):
+        lr = torch.as_tensor(np.ascontiguousarray(lr))
+    elif not lr.is_cuda:
+        raise RuntimeError(f"pssr2_amd.util.{who} runs on an MI355X (HIP) device only; there is no CPU fallback")
+    if lr.dtype != torch.uint8:
+        raise TypeError(f"{who} takes uint8 images; lr is {lr.dtype}")
+    if lr.dim() not in (3, 4):
+        raise ValueError(f"lr must be 4-D, [images, frames, height, width], or 3-D without the batch axis. Its shape is {tuple(lr.shape)}.")
+    batched = lr.dim() == 4
+    if not batched:
+        lr = lr[None]
+    if min(lr.shape) < 1:
+        raise ValueError(f"lr needs at least one plane of at least one pixel. Its shape is {tuple(lr.shape)}.")
+    if lr.shape[-2] * lr.shape[-1] > 1 << 28:
+        raise ValueError(f"A plane of lr of {lr.shape[-2] * lr.shape[-1]} pixels is above the 2**28 that a launch takes.")
+    return lr, batched
+
+
+def _baseline_device(who, lr):
+    if not (lr.is_cuda or torch.cuda.is_available()):
+        raise RuntimeError(f"pssr2_amd.util.{who} needs an MI355X (HIP) device, and none is available; there is no CPU fallback")
+    return lr if lr.is_cuda else lr.to("cuda")
+
+
+def _check_upsample(scale, filter):
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or not 1 <= scale <= ops.MAX_UPSAMPLE:
+        raise ValueError(f"scale must be an int from 1 to {ops.MAX_UPSAMPLE}. Given {scale!r}.")
+    if filter not in ops.UPSAMPLE_FILTERS:
+        raise ValueError(f"filter must be one of {ops.UPSAMPLE_FILTERS}. Given {filter!r}.")
+    return int(scale)
+
+
+def upsample(lr, scale, *, filter: str = "bicubic", to_numpy: bool = True):
+    r"""The "LR-bicubic" row of a super-resolution table: ``lr`` enlarged by the integer ``scale`` (1 .. 8) exactly as Pillow's 8-bit
+    ``Image.resize`` enlarges it with ``filter`` ``"bicubic"`` (Keys, a = -0.5) or ``"bilinear"``: the same bytes (B1 of
+    include/pssr_mi355.h: 22-bit fixed-point taps, the x pass rounded and clipped to uint8, then the y pass).  ``lr``: uint8 array or
+    device tensor [N, c, h, w] (or 3-D, without the batch axis); returns uint8 [..., h scale, w scale], a device tensor for
+    ``to_numpy=False``.  One launch (``pssr_upsample_u8``) for all planes."""
+    scale = _check_upsample(scale, filter)
+    lr, batched = _baseline_image("upsample", lr)
+    if lr.shape[-2] * scale * lr.shape[-1] * scale > 1 << 28:
+        raise ValueError(f"A plane of lr enlarged {scale} times has {lr.shape[-2] * scale * lr.shape[-1] * scale} pixels, above the 2**28 that a launch takes.")
+    out = ops.upsample_u8(_baseline_device("upsample", lr), scale, filter)
+    if not batched:
+        out = out[0]
+    return out.cpu().numpy() if to_numpy else out
+
+
+def _nlm_params(h, sigma, P):
+    """``(qmul, qshift, bias)`` of the integer non-local means (B2 of include/pssr_mi355.h) for ``P x P`` patches:
+    ``bias = rint(2 P**2 sigma**2)``; ``qshift`` the largest of 0 .. 31 with ``qmul = rint(32 * 2**qshift / (P**2 h**2)) <= 1023``."""
+    if isinstance(h, bool) or not isinstance(h, (int, float, np.integer, np.floating)) or not 0.5 <= h <= 255:
+        raise ValueError(f"h must be a number from 0.5 to 255 (the filter strength in grey levels). Given {h!r}.")
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating)) or not 0 <= sigma <= 255:
+        raise ValueError(f"sigma must be a number from 0 to 255 (the noise level in grey levels). Given {sigma!r}.")
+    h, sigma = float(h), float(sigma)
+    bias = int(np.rint(2.0 * P * P * sigma * sigma))
+    for qshift in range(31, -1, -1):
+        qmul = int(np.rint(32.0 * 2.0 ** qshift / (P * P * h * h)))
+        if qmul <= 1023:
+            break
+    if qmul < 1:
+        raise ValueError(f"h = {h} is too large for {P} x {P} patches: the weights' scale rounds to zero.")
+    return qmul, qshift, bias
+
+
+def _check_nlm(h, sigma, patch_radius, search_radius):
+    for name, v, hi in (("patch_radius", patch_radius, ops.MAX_NLM_PATCH), ("search_radius", search_radius, ops.MAX_NLM_SEARCH)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
+            raise ValueError(f"{name} must be an int from 1 to {hi}. Given {v!r}.")
+    return (int(patch_radius), int(search_radius)) + _nlm_params(h, sigma, 2 * int(patch_radius) + 1)
+
+
+def nlm_denoise(lr, *, h, sigma: float = 0.0, patch_radius: int = 2, search_radius: int = 7, to_numpy: bool = True):
+    r"""Non-local means (Buades et al.; the algorithm of scikit-image's ``denoise_nl_means``) for the "LR-denoised" row of a table, in
+    integers (B2 of include/pssr_mi355.h), so every run and every machine gives the same bytes.  ``lr``: uint8 array or device tensor
+    [N, c, h, w] (or 3-D); every plane is denoised on its own.  A pixel becomes the weighted mean of the pixels within
+    ``search_radius`` (1 .. 10) of it; a candidate's weight falls off as ``exp(-max(d - 2 sigma**2, 0) / h**2)`` with ``d`` the mean
+    squared difference of the two ``(2 patch_radius + 1)**2`` patches (``patch_radius`` 1 .. 3), quantised to a table of 256 weights.
+
+    ``h`` (grey levels, 0.5 .. 255; keyword-only and required: there is no honest default) is the strength: larger smooths more.
+    ``sigma`` is the noise level in grey levels; with it given, scikit-image's guidance is ``h`` of about 0.6 to 0.8 ``sigma``, without it
+    somewhat above the noise level.  Nothing here chooses ``h``: ``util.estimate_noise(...).sigma`` measures a pair's noise level, and
+    passing it on as ``sigma`` is the caller's step.  Returns uint8 of the shape of ``lr`` (a device tensor for ``to_numpy=False``).
+    One launch (``pssr_nlm_u8``) for all planes."""
+    p, s, qmul, qshift, bias = _check_nlm(h, sigma, patch_radius, search_radius)
+    lr, batched = _baseline_image("nlm_denoise", lr)
+    out = ops.nlm_u8(_baseline_device("nlm_denoise", lr), p, s, qmul, qshift, bias)
+    if not batched:
+        out = out[0]
+    return out.cpu().numpy() if to_numpy else out
+
+
 def _spectral_inputs(who: str, named, block):
     """The checks of the images and the block side that ``frc``, ``decorr`` and their sectorial forms share, in their order (``named``:
     ``(name, image)`` pairs) -> ``(device tensors [N, C, H, W], batched, block, device)``."""
